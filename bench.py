@@ -1,7 +1,12 @@
 """Headline benchmark: 64^3 cubes/s through compress_hyper + decompress_hyper (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`).
+--full adds everything below that takes runs of its own: N = 1 the roofline, the other operating points, the file-level,
+stream-of-clouds and large-cloud figures, the training step, the CPU baseline and the parity block; N > 1 the collectives,
+strong scaling and independent clouds.  --dump-outputs DIR writes what the last timed step returned (see _dump_outputs).
 
 Workload (`config.workload`): a seeded synthetic stand-in for BASELINE.json configs[1]
 (longdress_vox10_1300, --mode=hyper --cube_size=64): synthetic.make_cloud(seed 1300, 1024^3 grid)
@@ -20,7 +25,7 @@ blocks: sharding.decode_ranges) and the bit-packed occupancy masks are gathered 
 over the N ranks, `independent_clouds` N clouds of 205 cubes, one per rank, with the single-GPU codec (no collective, N z
 strings: what the format's one sequential z stream per cloud costs the sharded figure).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     — the conv kernel instantiation with the largest share of GPU time, timed with hipEvents
                  on the launch stream (pcgc_net_set_profiling) in extra steps right after the timed ones;
                  achieved = 2*MACs of that layer per launch / mean launch time, peak = 157.3 TFLOP/s fp32 MFMA.
@@ -64,13 +69,63 @@ def parse():
                          "Trainer, tools/train_ckpt.py; the default when present), or a seeded synthetic profile: sparse, mid, dense")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the second operating point and the file-level figure")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, operating points, file level, stream / large "
+                         "cloud, training step, CPU baseline + parity (N = 1); collectives, strong scaling, independent clouds (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _stream_crc(stream):
     """CRC-32 of a cloud's coded bytes (y strings in cube order, then the z string): equal across process counts"""
     import zlib
     return zlib.crc32(b"".join(bytes(s_) for s_ in stream[0]) + bytes(stream[4])) & 0xFFFFFFFF
+
+
+DUMP_SAMPLE = 1 << 23          # elements kept of a larger output: 32 MB of float32
+
+
+def _sample(flat):
+    """a fixed, seeded sample of a large flat tensor (sorted positions; the same ones for the same size), else all of it"""
+    import torch
+    n = int(flat.numel())
+    if n <= DUMP_SAMPLE:
+        return flat.cpu().numpy()
+    idx = np.sort(np.random.default_rng(1300).choice(n, DUMP_SAMPLE, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+
+def _dump_outputs(d, stream, decoded):
+    """--dump-outputs: what the last timed step returned to its caller (rank 0), as DIR/<name>.npy in float32 / float64.
+    The stream of compress_hyper: y_strings (bytes of all cubes' strings in cube order) + y_string_lengths, y_min_vs,
+    y_max_vs, y_shape, z_string, z_min_v, z_max_v, z_shape.  N = 1, decompress_hyper's logits [B,64,64,64,1]:
+    logits_cube_sums (float64 sum per cube) and logits_sample (DUMP_SAMPLE seeded positions of the flattened batch).
+    N > 1, the top-k masks gathered bit-packed to rank 0: occupied_voxels_per_cube and occupancy_packed (bytes; sampled
+    like the logits when larger)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    y_strings = [bytes(s_) for s_ in stream[0]]
+    arrays = {"y_strings": np.frombuffer(b"".join(y_strings), np.uint8).astype(np.float32),
+              "y_string_lengths": np.array([len(s_) for s_ in y_strings], np.float64),
+              "y_min_vs": np.asarray(stream[1], np.float64), "y_max_vs": np.asarray(stream[2], np.float64),
+              "y_shape": np.asarray(stream[3], np.float64),
+              "z_string": np.frombuffer(bytes(stream[4]), np.uint8).astype(np.float32),
+              "z_min_v": np.asarray(stream[5], np.float64), "z_max_v": np.asarray(stream[6], np.float64),
+              "z_shape": np.asarray(stream[7], np.float64)}
+    if torch.is_tensor(decoded):
+        arrays["logits_cube_sums"] = decoded.reshape(decoded.shape[0], -1).sum(dim=1, dtype=torch.float64).cpu().numpy()
+        arrays["logits_sample"] = _sample(decoded.reshape(-1)).astype(np.float32)
+    else:
+        packed = decoded[0]
+        ones = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.float64, device=packed.device)
+        arrays["occupied_voxels_per_cube"] = ones[packed.long()].sum(dim=1).cpu().numpy()
+        arrays["occupancy_packed"] = _sample(packed.reshape(-1)).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _self_launch(args):
@@ -177,13 +232,17 @@ def main():
     gc.freeze()          # a full Python collection over the set-up's objects (weights, golden tables) takes about 50 ms — one
                          # whole step — and would land in the timed region at random
     barrier()
-    clock = _ClockSampler(torch.cuda.current_device()) if rank == 0 and os.environ.get("PCGC_BENCH_CLOCK", "1") != "0" else None
+    # the clock samples only feed the roofline block (--full)
+    clock = (_ClockSampler(torch.cuda.current_device())
+             if rank == 0 and args.full and os.environ.get("PCGC_BENCH_CLOCK", "1") != "0" else None)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out, xs = step()
     barrier()
     dt = time.perf_counter() - t0
     clock_report = clock.stop() if clock else None
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, out, xs)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -202,7 +261,8 @@ def main():
                                   "; %d such blocks = one %d-cube cloud sharded over %d ranks (sharding.py: RCCL all_reduce / "
                                   "gather / broadcast), decode ends with top-k masks gathered bit-packed to rank 0"
                                   % (world, world * B, world)),
-                   "cubes_per_rank": B, "host_threads": __import__("pcgcv1_amd._lib", fromlist=["x"]).host_threads()},
+                   "cubes_per_rank": B, "host_threads": __import__("pcgcv1_amd._lib", fromlist=["x"]).host_threads(),
+                   "host_pipelines": transform._PIPES},
         "path_tflops": round(value * GFLOP_PER_CUBE / 1e3, 3),
         "ranks": {"world_size": dist.get_world_size() if world > 1 else 1, "backend": (dist.get_backend() if world > 1 else None),
                   "devices_visible": torch.cuda.device_count()},
@@ -215,7 +275,7 @@ def main():
             result["config"]["stream_crc32"] = _stream_crc(out)
 
     # ---------------------------------------------------------------- N > 1: collectives of one step, strong scaling
-    if world > 1:
+    if world > 1 and args.full:
         ex = sharding.Exchange(timing=True)
         step_sharded(cubes, world * B, nums, ex)
         barrier()
@@ -255,7 +315,7 @@ def main():
                                             "ms_per_step": round(1e3 * float(di.item()) / 3, 3)}
 
     # ---------------------------------------------------------------- roofline (dominant conv kernel)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         c = transform.get_codec(model, "bench")
         nets = {"analysis_transform": c.analysis_transform, "synthesis_transform": c.synthesis_transform,
                 "hyper_encoder": c.hyper_encoder, "hyper_decoder": c.hyper_decoder}
@@ -270,7 +330,6 @@ def main():
             step_local()            # rank 0 alone runs this block: never the sharded step (its collectives would hang)
         torch.cuda.synchronize()
         transform._PIPES = pipes
-        result["config"]["host_pipelines"] = pipes
         agg = {}
         # empty-space skipping (analysis, 64^3 stage): those launches compute only the tiles whose receptive field holds an
         # occupied voxel — their FLOPs are counted for the computed tiles only, under keys of their own, and never make the
@@ -384,7 +443,7 @@ def main():
         result["stage_seconds"] = {k: round(v, 4) for k, v in _stage_times(transform, model, cubes).items()}
 
     # ---------------------------------------------------------------- second operating point + file level (N = 1)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         def sym_range(o_):
             return "y-hat in [%d, %d] per cube" % (int(np.min(o_[1])), int(np.max(o_[2])))
         result["operating_points"] = [{"profile": args.profile, "headline": True, "symbols": sym_range(out), "cubes_per_s": round(value, 1),
@@ -423,11 +482,11 @@ def main():
         result["large_cloud"] = _large_block(transform, model, cubes, B)
 
     # ---------------------------------------------------------------- config 4: one train_hyper step (N = 1, rank 0)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         result["train"] = _train_block()
 
     # ---------------------------------------------------------------- CPU baseline (oracle port), rank 0, N=1
-    if rank == 0 and world == 1 and args.cpu_cubes > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_cubes > 0:
         from oracle import transform as otransform
         from oracle import points as opoints
         from pcgcv1_amd import metrics

@@ -170,7 +170,7 @@ def test_cli_under_torchrun_writes_the_same_files(tmp_path):
 
 
 def test_bench_two_ranks_prints_one_json_line():
-    """bench.py --gpus 2 exactly as the driver launches it (torchrun, default flags apart from a short run): both ranks
+    """bench.py --gpus 2 --full as the driver launches it (torchrun, default flags apart from a short run): both ranks
     exit 0 and rank 0 prints the contract's JSON line with the sharded-path extras.  The ranks share this box's one
     GPU over gloo (RCCL refuses two ranks on one device); the rank-0-only roofline block after the timed region must not
     enter a collective."""
@@ -178,7 +178,8 @@ def test_bench_two_ranks_prints_one_json_line():
     root = os.path.dirname(HERE)
     env = dict(os.environ, PCGC_BENCH_BACKEND="gloo", PYTHONPATH=root)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -191,20 +192,59 @@ def test_bench_two_ranks_prints_one_json_line():
     assert d["ranks"] == {"world_size": 2, "backend": "gloo", "devices_visible": 1}
 
 
-def test_bare_bench_gpus_2_starts_its_own_ranks():
+def test_bare_bench_gpus_2_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE (the form of the driver's N = 1 command) starts its two
-    ranks itself instead of failing an assert, relays rank 0's JSON line and exits 0."""
+    ranks itself instead of failing an assert, relays rank 0's JSON line and exits 0; --dump-outputs writes rank 0's
+    stream and gathered top-k masks."""
     import json
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PCGC_BENCH_BACKEND="gloo", PYTHONPATH=root)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--no-roofline"], cwd=root, env=env, capture_output=True, timeout=900)
+                        "--no-roofline", "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["ranks"]["world_size"] == 2 and d["value"] > 0
+    arrays = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    n = 2 * d["config"]["cubes_per_rank"]
+    assert arrays["y_string_lengths"].shape == (n,) and arrays["y_string_lengths"].sum() == arrays["y_strings"].size
+    counts = arrays["occupied_voxels_per_cube"]
+    assert counts.shape == (n,) and (counts > 0).all() and (counts <= 64 ** 3).all()
+
+
+def test_plain_bench_dumps_the_timed_step(tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` without --full prints the headline line only (no roofline, operating
+    points or CPU baseline) and writes what the last timed step returned: float32 / float64 .npy files, 64 MB at most, whose
+    coded bytes are the stream the line's config.stream_crc32 names.  A second run writes the same arrays."""
+    import json
+    import zlib
+    root = os.path.dirname(HERE)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=root, capture_output=True, timeout=900)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert not {"roofline", "operating_points", "train", "cpu_baseline", "parity_vs_cpu_oracle"} & set(line)
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64e6
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith(".npy") for f in files) and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        B = line["config"]["cubes_per_rank"]
+        assert arrays["logits_cube_sums"].shape == (B,) and arrays["y_string_lengths"].sum() == arrays["y_strings"].size
+        coded = arrays["y_strings"].astype(np.uint8).tobytes() + arrays["z_string"].astype(np.uint8).tobytes()
+        assert zlib.crc32(coded) & 0xFFFFFFFF == line["config"]["stream_crc32"]
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_sharded_codec_on_eight_ranks(tmp_path):
@@ -241,7 +281,7 @@ def test_sharded_codec_on_eight_ranks(tmp_path):
 def test_bench_eight_ranks_dry_run():
     """The driver's SCALE command at N = 8, as far as one GPU can rehearse it: `python bench.py --gpus 8` bare (its own
     --standalone launcher; children only — nothing re-execs a process that touched the GPU) over gloo on the one device.
-    Every rank exits 0, rank 0 prints ONE JSON line with world_size 8 and the collectives of a step, and the strong-scaling
+    Every rank exits 0, rank 0 prints ONE JSON line with world_size 8 and (--full) the collectives of a step, and the strong-scaling
     leg (the one 205-cube cloud cut into eight blocks) codes the bytes the single-process codec codes (CRC-32 of the y strings
     + z string, printed by the N = 1 line as config.stream_crc32).  NOT a scaling number: eight processes share one GPU."""
     import json
@@ -249,7 +289,7 @@ def test_bench_eight_ranks_dry_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PCGC_BENCH_BACKEND="gloo", PYTHONPATH=root)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--no-extras", "--cpu-cubes", "0"], cwd=root, env=env, capture_output=True, timeout=1500)
+                        "--full", "--no-extras", "--cpu-cubes", "0"], cwd=root, env=env, capture_output=True, timeout=1500)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -1,5 +1,5 @@
 """Markdown table of every conv kernel of one bench step from a bench.py JSON line produced with PCGC_BENCH_TOP=40:
-    PCGC_BENCH_TOP=40 python bench.py --no-extras --cpu-cubes 0 --steps 10 > b.json ; python tools/roofline_table.py b.json"""
+    PCGC_BENCH_TOP=40 python bench.py --full --no-extras --cpu-cubes 0 --steps 10 > b.json ; python tools/roofline_table.py b.json"""
 import json
 import sys
 
@@ -10,7 +10,7 @@ def main(path):
     peak = r["peak"]
     clock = r.get("clock") or {}
     out = ["# Per-kernel table of one bench step (%s cubes, encode + decode)" % d["config"].get("cubes", "205"), "",
-           "`PCGC_BENCH_TOP=40 python bench.py --no-extras --cpu-cubes 0 --steps %d` on one MI355X: %.0f cubes/s, %.2f ms per step; per-launch"
+           "`PCGC_BENCH_TOP=40 python bench.py --full --no-extras --cpu-cubes 0 --steps %d` on one MI355X: %.0f cubes/s, %.2f ms per step; per-launch"
            % (d["steps"], d["value"], d["ms_per_step"]),
            "hipEvent times of two single-pipeline steps (`roofline` block of bench.py).  fp32 MFMA peak %.1f TFLOP/s; HBM-bound" % peak,
            "layers are marked with their algorithmic GB/s instead.  All conv kernels together: %.1f TFLOP/s, %.2f ms per step."
