@@ -263,6 +263,45 @@ int pcgc_voxelize(const int32_t* cube_xyz, int64_t n, int cube_size, float* cube
 int pcgc_voxelize_points(const int32_t* points, const int32_t* cube_of_point, int64_t n, int cube_size,
                          int cube_lo, int cube_hi, float* cubes, pcgc_stream_t stream);
 
+/* ---- mesh -> point cloud with normals (dataprocess/mesh2pc_open3d.py:55-85) ---- */
+/* sample_points_uniformly + np.dot(points, get_rotate_matrix()) (mesh2pc_open3d.py:57-66).  vertices double [V,3],
+ * triangles int32 [T,3], area_cdf double [T] = inclusive running sum of the triangle areas (pcgc_mesh_area_cdf), all on
+ * the device; points double [n_points,3].  rotation: a row-major 3x3 double matrix on the device, or NULL for none.
+ * Sample i draws u_k = (h_k >> 11) * 2^-53, k = 0, 1, 2, where h_k is the (3i + k + 1)-th output of splitmix64 seeded
+ * with `seed`:  z = seed + (3i + k + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  h = z ^ (z >> 31)  (all mod 2^64).
+ * Triangle t = upper_bound(area_cdf, u0 * area_cdf[T-1]) (zero-area triangles are never chosen; a target that rounds
+ * up to the total takes the last triangle of positive area).  s = sqrt(u1), a = 1 - s, b = s (1 - u2), c = s u2,
+ * p = (a v0 + b v1) + c v2 per coordinate; rotated as a row vector: p'_k = (p_x m_0k + p_y m_1k) + p_z m_2k.
+ * Every step is one IEEE double operation in this order, without contraction. */
+int pcgc_mesh_sample(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                     const double* area_cdf, int64_t n_points, uint64_t seed, const double* rotation, double* points,
+                     pcgc_stream_t stream);
+/* The voxelisation of mesh2pc_open3d.py:67-73 + np.unique(points, axis=0): m = min over all 3n coordinates,
+ * M = max of p - m, q = rint((p - m) / M * resolution) (half to even; M == 0 gives 0), then the distinct q in
+ * lexicographic order, int32 [n_out,3].  cap >= n (the output never holds more than n rows); *n_out (DEVICE int64)
+ * receives the count.  1 <= resolution <= 4095; workspace holds a (resolution+1)^3 bit set. */
+size_t pcgc_mesh_voxelize_workspace_bytes(int resolution);
+int pcgc_mesh_voxelize(const double* points, int64_t n, int resolution, int32_t* out, int64_t cap, int64_t* n_out,
+                       void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+/* estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (mesh2pc_open3d.py:75-78) on a voxel grid.
+ * points int32 [n,3], any order, 0 <= coordinate < res <= 4096; radius <= 16, 1 <= max_nn <= 64; normals float32 [n,3]
+ * in input order (duplicate points share a cell and its normal).
+ *   neighbours: the first max_nn occupied cells of the offset table = every integer offset d with |d|^2 <= radius^2
+ *     ("<=": whether Open3D's radius test is inclusive could not be checked), sorted by (|d|^2, dx, dy, dz); offset 0,
+ *     the point itself, counts.  K = their number.
+ *   C = K sum d d^T - (sum d)(sum d)^T, exact in int64 (d = the offsets, not the absolute coordinates).
+ *   normal: the eigenvector of the smallest eigenvalue of C (cyclic Jacobi in double); K < 3: (0,0,1); C of rank <= 1
+ *     (every 2x2 minor 0: collinear neighbours): u = the row of C with the largest diagonal entry (lowest index on
+ *     ties), j = the axis of u's smallest |component| (lowest index on ties), normal = normalize(u x e_j).
+ *   sign: flipped so that the first component with |c| > 1e-6 is positive (Open3D leaves it arbitrary).
+ * cov int64 [n,6] (c00 c01 c02 c11 c12 c22) and n_neighbours int32 [n]: optional debug outputs (both or neither).
+ * pcgc_normals_table_size: the number of offsets within `radius` (4169 at radius 10), -1 for a bad radius. */
+int pcgc_normals_table_size(double radius);
+size_t pcgc_normals_workspace_bytes(int res, int64_t n, double radius);
+int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radius, int max_nn, float* normals, int64_t* cov,
+                          int32_t* n_neighbours, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what
@@ -548,6 +587,20 @@ int pcgc_parse_ply_points(const char* text, int64_t len, int32_t* out, int64_t c
  * as Python's str(int).  *out_len always receives the exact text length (never more than 63 bytes per point); with a
  * smaller cap (or out == NULL) nothing is written and the call returns -2. */
 int pcgc_format_points_int(const int64_t* pts, int64_t n, char* out, int64_t cap, int64_t* out_len);
+
+/* o3d.io.read_triangle_mesh (mesh2pc_open3d.py:58) for the two formats the reference feeds it: format 0 = OFF
+ * (ModelNet40, including its "OFF490 518 0" first line with the counts glued to the magic; extra per-vertex or per-face
+ * values are ignored), 1 = OBJ (ShapeNet: `v x y z`, `f` with a, a/b, a//c, a/b/c corners and negative indices relative
+ * to the vertices read so far; '#' starts a comment; other records are skipped).  Polygons are fan-triangulated
+ * (0, i, i+1); faces with fewer than three corners add nothing; an index outside the vertices is an error (-3).
+ * vertices double [vcap,3], triangles int32 [tcap,3]; *n_vertices / *n_triangles always receive the counts, and with
+ * too small a capacity (or NULL outputs) nothing is written and the call returns -2. */
+int pcgc_parse_mesh(const char* text, int64_t len, int format, double* vertices, int64_t vcap, int32_t* triangles,
+                    int64_t tcap, int64_t* n_vertices, int64_t* n_triangles);
+/* Triangle areas and their inclusive running sum in double, sequential like np.cumsum (sample_points_uniformly's
+ * area weights): e = v1 - v0, f = v2 - v0, c = e x f (cx = ey fz - ez fy, ...), area = 0.5 sqrt((cx^2 + cy^2) + cz^2).
+ * A total area of 0 is an error (-3). */
+int pcgc_mesh_area_cdf(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, double* cdf);
 
 /* CRC-32C (Castagnoli, reflected 0x82F63B78), the checksum of TensorFlow's tensor-bundle checkpoints
  * (tf.train.Checkpoint files restored at transform.py:107-112; written at train_hyper.py:255-268).

@@ -51,6 +51,12 @@ HIP_API = {
     "pcgc_focal_loss_bwd": (c_int, [c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "pcgc_voxelize": (c_int, [c_vp, c_i64, c_int, c_vp, c_int, c_vp]),
     "pcgc_voxelize_points": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
+    "pcgc_mesh_sample": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.c_uint64, c_vp, c_vp, c_vp]),
+    "pcgc_mesh_voxelize_workspace_bytes": (c_sz, [c_int]),
+    "pcgc_mesh_voxelize": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_normals_table_size": (c_int, [ctypes.c_double]),
+    "pcgc_normals_workspace_bytes": (c_sz, [c_int, c_i64, ctypes.c_double]),
+    "pcgc_estimate_normals": (c_int, [c_vp, c_i64, c_int, ctypes.c_double, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d1_workspace_bytes": (c_sz, [c_int]),
     "pcgc_d1_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),
@@ -123,6 +129,8 @@ HOST_API = {
     "pcgc_host_repro_eval": (c_int, [c_int, c_vp, c_vp, c_i64]),
     "pcgc_format_points_int": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pcgc_parse_ply_points": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int]),
+    "pcgc_parse_mesh": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "pcgc_mesh_area_cdf": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
 
 _hip = None

@@ -35,6 +35,7 @@ HIP_SOURCES = {
     "train_dw.hip": [],
     "train_plan.hip": [],
     "hyper_row.hip": [],
+    "mesh.hip": ["-ffp-contract=off"],
 }
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-fno-gpu-rdc"]

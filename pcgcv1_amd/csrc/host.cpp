@@ -759,6 +759,201 @@ int pcgc_format_points_int(const int64_t* pts, int64_t n, char* out, int64_t cap
   return 0;
 }
 
+// ---------------------------------------------------------------- mesh text (OFF / OBJ)
+struct MeshText {
+  const char* p;
+  const char* end;
+  int64_t line = 0;
+  // the whitespace-separated tokens of the next line that has any ('#' starts a comment); false at the end of the text
+  bool next(std::vector<std::pair<const char*, const char*>>& tok) {
+    tok.clear();
+    while (p < end && tok.empty()) {
+      const char* nl = static_cast<const char*>(std::memchr(p, '\n', size_t(end - p)));
+      const char* le = nl ? nl : end;
+      ++line;
+      const char* q = p;
+      while (q < le && *q != '#') {
+        while (q < le && (*q == ' ' || (*q >= 9 && *q <= 13))) ++q;
+        if (q >= le || *q == '#') break;
+        const char* b = q;
+        while (q < le && !(*q == ' ' || (*q >= 9 && *q <= 13)) && *q != '#') ++q;
+        tok.emplace_back(b, q);
+      }
+      p = nl ? nl + 1 : end;
+    }
+    return !tok.empty();
+  }
+};
+
+static bool parse_int_token(const char* b, const char* e, int64_t* out) {
+  bool neg = false;
+  if (b < e && (*b == '+' || *b == '-')) { neg = *b == '-'; ++b; }
+  if (b == e || e - b > 18) return false;
+  int64_t v = 0;
+  for (; b < e; ++b) {
+    if (*b < '0' || *b > '9') return false;
+    v = v * 10 + (*b - '0');
+  }
+  *out = neg ? -v : v;
+  return true;
+}
+
+static void fan(const std::vector<int64_t>& corner, std::vector<int32_t>& tris) {
+  for (size_t i = 1; i + 1 < corner.size(); ++i) {
+    tris.push_back(int32_t(corner[0]));
+    tris.push_back(int32_t(corner[i]));
+    tris.push_back(int32_t(corner[i + 1]));
+  }
+}
+
+static int parse_off(MeshText& in, std::vector<double>& verts, std::vector<int32_t>& tris) {
+  std::vector<std::pair<const char*, const char*>> tok;
+  if (!in.next(tok) || tok[0].second - tok[0].first < 3 || std::memcmp(tok[0].first, "OFF", 3) != 0) {
+    set_error("pcgc_parse_mesh: OFF text does not start with OFF");
+    return -4;
+  }
+  std::vector<std::pair<const char*, const char*>> counts;
+  if (tok[0].second - tok[0].first > 3) counts.emplace_back(tok[0].first + 3, tok[0].second);   // "OFF490 518 0"
+  counts.insert(counts.end(), tok.begin() + 1, tok.end());
+  if (counts.empty()) {
+    if (!in.next(tok)) { set_error("pcgc_parse_mesh: OFF header without counts"); return -4; }
+    counts = tok;
+  }
+  int64_t nv, nf;
+  if (counts.size() < 2 || !parse_int_token(counts[0].first, counts[0].second, &nv) ||
+      !parse_int_token(counts[1].first, counts[1].second, &nf) || nv < 0 || nf < 0) {
+    set_error("pcgc_parse_mesh: bad OFF counts (line %lld)", (long long)in.line);
+    return -4;
+  }
+  verts.reserve(size_t(nv) * 3);
+  for (int64_t i = 0; i < nv; ++i) {
+    double x[3];
+    if (!in.next(tok) || tok.size() < 3 || !parse_float_token(tok[0].first, tok[0].second, &x[0]) ||
+        !parse_float_token(tok[1].first, tok[1].second, &x[1]) || !parse_float_token(tok[2].first, tok[2].second, &x[2])) {
+      set_error("pcgc_parse_mesh: bad OFF vertex %lld (line %lld)", (long long)i, (long long)in.line);
+      return -4;
+    }
+    verts.insert(verts.end(), x, x + 3);
+  }
+  std::vector<int64_t> corner;
+  for (int64_t f = 0; f < nf; ++f) {
+    int64_t k;
+    if (!in.next(tok) || !parse_int_token(tok[0].first, tok[0].second, &k) || k < 0 || int64_t(tok.size()) < k + 1) {
+      set_error("pcgc_parse_mesh: bad OFF face %lld (line %lld)", (long long)f, (long long)in.line);
+      return -4;
+    }
+    corner.clear();
+    for (int64_t c = 0; c < k; ++c) {
+      int64_t idx;
+      if (!parse_int_token(tok[size_t(c + 1)].first, tok[size_t(c + 1)].second, &idx)) {
+        set_error("pcgc_parse_mesh: bad OFF face %lld (line %lld)", (long long)f, (long long)in.line);
+        return -4;
+      }
+      if (idx < 0 || idx >= nv) {
+        set_error("pcgc_parse_mesh: OFF face %lld (line %lld) indexes vertex %lld of %lld", (long long)f, (long long)in.line,
+                  (long long)idx, (long long)nv);
+        return -3;
+      }
+      corner.push_back(idx);
+    }
+    fan(corner, tris);
+  }
+  return 0;
+}
+
+static int parse_obj(MeshText& in, std::vector<double>& verts, std::vector<int32_t>& tris) {
+  std::vector<std::pair<const char*, const char*>> tok;
+  std::vector<int64_t> corner;
+  std::vector<int64_t> line_of;                // source line of each triangle's face, for the error after the last vertex
+  while (in.next(tok)) {
+    const size_t n0 = size_t(tok[0].second - tok[0].first);
+    if (n0 == 1 && tok[0].first[0] == 'v') {
+      double x[3];
+      if (tok.size() < 4 || !parse_float_token(tok[1].first, tok[1].second, &x[0]) ||
+          !parse_float_token(tok[2].first, tok[2].second, &x[1]) || !parse_float_token(tok[3].first, tok[3].second, &x[2])) {
+        set_error("pcgc_parse_mesh: bad OBJ vertex (line %lld)", (long long)in.line);
+        return -4;
+      }
+      verts.insert(verts.end(), x, x + 3);
+    } else if (n0 == 1 && tok[0].first[0] == 'f') {
+      const int64_t nv = int64_t(verts.size() / 3);
+      corner.clear();
+      for (size_t c = 1; c < tok.size(); ++c) {
+        const char* slash = static_cast<const char*>(std::memchr(tok[c].first, '/', size_t(tok[c].second - tok[c].first)));
+        int64_t idx;
+        if (!parse_int_token(tok[c].first, slash ? slash : tok[c].second, &idx)) {
+          set_error("pcgc_parse_mesh: bad OBJ face corner (line %lld)", (long long)in.line);
+          return -4;
+        }
+        idx = idx > 0 ? idx - 1 : idx < 0 ? nv + idx : -1;        // 1-based; negative: relative to the vertices so far
+        if (idx < 0) {
+          set_error("pcgc_parse_mesh: OBJ face (line %lld) indexes a vertex outside the %lld read so far", (long long)in.line,
+                    (long long)nv);
+          return -3;
+        }
+        corner.push_back(idx);
+      }
+      const size_t before = tris.size();
+      fan(corner, tris);
+      line_of.resize(line_of.size() + (tris.size() - before) / 3, in.line);
+    }
+  }
+  const int64_t nv = int64_t(verts.size() / 3);
+  for (size_t i = 0; i < tris.size(); ++i)
+    if (tris[i] >= nv) {
+      set_error("pcgc_parse_mesh: OBJ face (line %lld) indexes vertex %d of %lld", (long long)line_of[i / 3], tris[i] + 1,
+                (long long)nv);
+      return -3;
+    }
+  return 0;
+}
+
+int pcgc_parse_mesh(const char* text, int64_t len, int format, double* vertices, int64_t vcap, int32_t* triangles, int64_t tcap,
+                    int64_t* n_vertices, int64_t* n_triangles) {
+  if ((len > 0 && !text) || len < 0 || !n_vertices || !n_triangles || (format != 0 && format != 1)) {
+    set_error("pcgc_parse_mesh: bad arguments");
+    return -1;
+  }
+  MeshText in{text, text + len};
+  std::vector<double> verts;
+  std::vector<int32_t> tris;
+  const int rc = format == 0 ? parse_off(in, verts, tris) : parse_obj(in, verts, tris);
+  if (rc) return rc;
+  if (verts.size() / 3 > size_t(std::numeric_limits<int32_t>::max())) { set_error("pcgc_parse_mesh: too many vertices"); return -4; }
+  *n_vertices = int64_t(verts.size() / 3);
+  *n_triangles = int64_t(tris.size() / 3);
+  if (!vertices || !triangles || vcap < *n_vertices || tcap < *n_triangles) {
+    set_error("pcgc_parse_mesh: %lld vertices / %lld triangles, buffers hold %lld / %lld", (long long)*n_vertices,
+              (long long)*n_triangles, (long long)vcap, (long long)tcap);
+    return -2;
+  }
+  if (!verts.empty()) std::memcpy(vertices, verts.data(), verts.size() * sizeof(double));
+  if (!tris.empty()) std::memcpy(triangles, tris.data(), tris.size() * sizeof(int32_t));
+  return 0;
+}
+
+int pcgc_mesh_area_cdf(const double* v, int64_t n_vertices, const int32_t* t, int64_t n_triangles, double* cdf) {
+  if (n_triangles < 1 || n_vertices < 1 || !v || !t || !cdf) { set_error("pcgc_mesh_area_cdf: empty mesh or NULL argument"); return -1; }
+  double acc = 0.0;
+  for (int64_t i = 0; i < n_triangles; ++i) {
+    const int32_t a = t[i * 3], b = t[i * 3 + 1], c = t[i * 3 + 2];
+    if (a < 0 || b < 0 || c < 0 || a >= n_vertices || b >= n_vertices || c >= n_vertices) {
+      set_error("pcgc_mesh_area_cdf: triangle %lld indexes a vertex outside [0, %lld)", (long long)i, (long long)n_vertices);
+      return -3;
+    }
+    const double* p0 = v + int64_t(a) * 3;
+    const double* p1 = v + int64_t(b) * 3;
+    const double* p2 = v + int64_t(c) * 3;
+    const double ex = p1[0] - p0[0], ey = p1[1] - p0[1], ez = p1[2] - p0[2];
+    const double fx = p2[0] - p0[0], fy = p2[1] - p0[1], fz = p2[2] - p0[2];
+    const double cx = ey * fz - ez * fy, cy = ez * fx - ex * fz, cz = ex * fy - ey * fx;
+    acc += 0.5 * std::sqrt((cx * cx + cy * cy) + cz * cz);
+    cdf[i] = acc;
+  }
+  if (!(acc > 0.0)) { set_error("pcgc_mesh_area_cdf: the mesh has no area"); return -3; }
+  return 0;
+}
+
 // ---------------------------------------------------------------- reproducible elementary functions (repro_math.h)
 int pcgc_host_repro_eval(int fn, const float* x, float* y, int64_t n) {
   if (fn < 0 || fn > 4 || n < 0 || (n > 0 && (!x || !y))) { set_error("pcgc_host_repro_eval: bad arguments"); return -1; }

@@ -1,0 +1,523 @@
+// Mesh -> point cloud with normals (gfx950): the data preparation of dataprocess/mesh2pc_open3d.py:55-85.
+//
+//   mesh2pc_open3d.py:57-63   read_triangle_mesh + sample_points_uniformly   -> mesh_sample_kernel
+//   mesh2pc_open3d.py:64-67   np.dot(points, get_rotate_matrix())            -> mesh_sample_kernel
+//   mesh2pc_open3d.py:68-73   min / max / round voxelisation, np.unique       -> mesh_minmax_*, mesh_quantize_kernel, bitset scan
+//   mesh2pc_open3d.py:75-78   estimate_normals(KDTreeSearchParamHybrid(10, 20)) -> normals_kernel
+//
+// Every floating-point step of the sampler and the voxeliser is one IEEE double operation in a fixed order (the file is
+// built with -ffp-contract=off), so tests/_mesh_ref.py restates them in numpy bit for bit.  Integer sets are formed as
+// an occupancy bit set, and np.unique's lexicographic order is the bit order: a two-pass scan over per-word popcounts
+// compacts the set bits in linear-key order.
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <map>
+#include <mutex>
+#include <vector>
+#include "common.h"
+
+namespace pcgc {
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- sampling
+__device__ __forceinline__ uint64_t splitmix_out(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// draw k of sample i: the (3 i + k + 1)-th output of splitmix64 seeded with `seed`, as a double in [0, 1)
+__device__ __forceinline__ double mesh_uniform(uint64_t seed, int64_t i, int k) {
+  const uint64_t h = splitmix_out(seed + (uint64_t)(3 * i + k + 1) * 0x9E3779B97F4A7C15ull);
+  return (double)(h >> 11) * 0x1.0p-53;
+}
+
+__global__ void __launch_bounds__(256) mesh_sample_kernel(const double* v, const int32_t* tri, const double* cdf, int64_t T,
+                                                          int64_t n, uint64_t seed, const double* rot, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double u0 = mesh_uniform(seed, i, 0), u1 = mesh_uniform(seed, i, 1), u2 = mesh_uniform(seed, i, 2);
+  const double total = cdf[T - 1];
+  const double target = u0 * total;
+  int64_t lo = 0, hi = T;                        // upper_bound: first t with cdf[t] > target
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (cdf[mid] <= target) lo = mid + 1; else hi = mid;
+  }
+  if (lo == T) {                                 // target rounded up to the total: the last triangle of positive area
+    lo = 0; hi = T;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (cdf[mid] < total) lo = mid + 1; else hi = mid;
+    }
+  }
+  const int32_t* t = tri + lo * 3;
+  const double s = sqrt(u1);
+  const double a = 1.0 - s, b = s * (1.0 - u2), c = s * u2;
+  double p[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double ab = a * v[(int64_t)t[0] * 3 + k] + b * v[(int64_t)t[1] * 3 + k];
+    p[k] = ab + c * v[(int64_t)t[2] * 3 + k];
+  }
+  if (rot) {                                     // row vector times m: x'_k = (x m0k + y m1k) + z m2k
+    double q[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = (p[0] * rot[k] + p[1] * rot[3 + k]) + p[2] * rot[6 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = q[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[i * 3 + k] = p[k];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- voxelising
+constexpr int kMinMaxBlocks = 512;
+
+__global__ void __launch_bounds__(256) mesh_minmax_partial_kernel(const double* p, int64_t m, double* partial) {
+  __shared__ double smin[256], smax[256];
+  double lo = INFINITY, hi = -INFINITY;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+    lo = fmin(lo, p[i]);
+    hi = fmax(hi, p[i]);
+  }
+  smin[threadIdx.x] = lo;
+  smax[threadIdx.x] = hi;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + o]);
+      smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + o]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { partial[blockIdx.x * 2] = smin[0]; partial[blockIdx.x * 2 + 1] = smax[0]; }
+}
+
+// mm[0] = m = min of all coordinates, mm[1] = M = max of the shifted coordinates.  fl(x - m) is monotone in x, so the
+// largest shifted coordinate is fl(max - m): one pass finds both.
+__global__ void mesh_minmax_final_kernel(const double* partial, int nb, double* mm) {
+  if (threadIdx.x == 0) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int b = 0; b < nb; ++b) { lo = fmin(lo, partial[b * 2]); hi = fmax(hi, partial[b * 2 + 1]); }
+    mm[0] = lo;
+    mm[1] = hi - lo;
+  }
+}
+
+// q = rint((p - m) / M * resolution) (np.round: half to even), one bit per cell of the (resolution + 1)^3 grid
+__global__ void __launch_bounds__(256) mesh_quantize_kernel(const double* p, int64_t n, const double* mm, int resolution,
+                                                            unsigned* bits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double m = mm[0], M = mm[1];
+  const int64_t G = resolution + 1;
+  int64_t q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double r = M > 0.0 ? rint((p[i * 3 + k] - m) / M * (double)resolution) : 0.0;   // M == 0: one point, every coordinate 0
+    q[k] = (int64_t)r;
+    if (!(r >= 0.0 && r <= (double)resolution)) return;                                     // unreachable for finite input
+  }
+  const int64_t key = (q[0] * G + q[1]) * G + q[2];
+  atomicOr(&bits[key >> 5], 1u << (key & 31));
+}
+
+// ---------------------------------------------------------------------------------------------------------------- bit set scan
+// The bit set is padded to a whole number of scan blocks (kScanWords words each) and zeroed, so the scan reads no bound.
+constexpr int kScanThreads = 256, kWordsPerThread = 16, kScanWords = kScanThreads * kWordsPerThread;
+
+__device__ __forceinline__ void load_words(const unsigned* bits, int64_t blk, unsigned w[kWordsPerThread]) {
+  const uint4* src = reinterpret_cast<const uint4*>(bits + blk * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread / 4; ++k) {
+    const uint4 u = src[k];
+    w[4 * k] = u.x; w[4 * k + 1] = u.y; w[4 * k + 2] = u.z; w[4 * k + 3] = u.w;
+  }
+}
+
+// exclusive prefix of v over the workgroup's threads (in thread order) and the workgroup total
+__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* total) {
+  __shared__ unsigned wsum[kScanThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kScanThreads / 64; ++k) {
+    before += k < wave ? wsum[k] : 0u;
+    all += wsum[k];
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kScanThreads) bits_count_kernel(const unsigned* bits, int64_t* block_count) {
+  unsigned w[kWordsPerThread];
+  load_words(bits, blockIdx.x, w);
+  unsigned c = 0;
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread; ++k) c += __popc(w[k]);
+  unsigned total;
+  block_scan(c, &total);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// exclusive prefix of the per-block counts in place, the sum in *n_set: one workgroup, each thread a contiguous run
+__global__ void __launch_bounds__(1024) bits_block_scan_kernel(int64_t* block_count, int64_t nblk, int64_t* n_set) {
+  __shared__ int64_t part[1024];
+  const int64_t per = (nblk + 1023) / 1024;
+  const int64_t b0 = std::min<int64_t>(nblk, (int64_t)threadIdx.x * per), b1 = std::min<int64_t>(nblk, b0 + per);
+  int64_t s = 0;
+  for (int64_t b = b0; b < b1; ++b) s += block_count[b];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t acc = 0;
+    for (int t = 0; t < 1024; ++t) { const int64_t x = part[t]; part[t] = acc; acc += x; }
+    *n_set = acc;
+  }
+  __syncthreads();
+  int64_t acc = part[threadIdx.x];
+  for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
+}
+
+// every set bit in key order: voxelize writes the cell's coordinates (int32 x, y, z of the G^3 grid), the normals path
+// its key.  Writes stop at cap (the callers size cap to the number of input points, which bounds the set bits).
+template <bool kCoords>
+__global__ void __launch_bounds__(kScanThreads) bits_compact_kernel(const unsigned* bits, const int64_t* block_offset, int64_t G,
+                                                                    int64_t cap, int32_t* coords, int64_t* keys) {
+  unsigned w[kWordsPerThread];
+  load_words(bits, blockIdx.x, w);
+  unsigned c = 0;
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread; ++k) c += __popc(w[k]);
+  unsigned total;
+  int64_t o = block_offset[blockIdx.x] + block_scan(c, &total);
+  if (c == 0) return;
+  const int64_t word0 = (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread;
+  for (int k = 0; k < kWordsPerThread; ++k) {
+    unsigned x = w[k];
+    while (x) {
+      const int b = __ffs(x) - 1;
+      x &= x - 1;
+      const int64_t key = (word0 + k) * 32 + b;
+      if (o < cap) {
+        if (kCoords) {
+          coords[o * 3] = (int32_t)(key / (G * G));
+          coords[o * 3 + 1] = (int32_t)((key / G) % G);
+          coords[o * 3 + 2] = (int32_t)(key % G);
+        } else {
+          keys[o] = key;
+        }
+      }
+      ++o;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- normals
+__global__ void __launch_bounds__(256) normals_bitset_kernel(const int32_t* p, int64_t n, int res, unsigned* bits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+  if ((unsigned)x >= (unsigned)res || (unsigned)y >= (unsigned)res || (unsigned)z >= (unsigned)res) return;
+  const int64_t key = ((int64_t)x * res + y) * res + z;
+  atomicOr(&bits[key >> 5], 1u << (key & 31));
+}
+
+__device__ __forceinline__ bool occupied(const unsigned* bits, int res, int x, int y, int z) {
+  if ((unsigned)x >= (unsigned)res || (unsigned)y >= (unsigned)res || (unsigned)z >= (unsigned)res) return false;
+  const int64_t key = ((int64_t)x * res + y) * res + z;
+  return (bits[key >> 5] >> (key & 31)) & 1u;
+}
+
+// cyclic Jacobi on the symmetric 3x3 a (destroyed): eigenvalues on the diagonal, eigenvectors in the columns of v
+__device__ void jacobi3(double a[3][3], double v[3][3]) {
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) v[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    if (a[0][1] == 0.0 && a[0][2] == 0.0 && a[1][2] == 0.0) break;
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+      const double apq = a[p][q];
+      if (apq == 0.0) continue;
+      const double g = 100.0 * fabs(apq);
+      if (sweep > 3 && fabs(a[p][p]) + g == fabs(a[p][p]) && fabs(a[q][q]) + g == fabs(a[q][q])) {
+        a[p][q] = a[q][p] = 0.0;                 // below the diagonal's precision
+        continue;
+      }
+      const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+      const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+      for (int k = 0; k < 3; ++k) {              // a <- a J (columns p, q)
+        const double akp = a[k][p], akq = a[k][q];
+        a[k][p] = c * akp - s * akq;
+        a[k][q] = s * akp + c * akq;
+      }
+      for (int k = 0; k < 3; ++k) {              // a <- J^T a (rows p, q)
+        const double apk = a[p][k], aqk = a[q][k];
+        a[p][k] = c * apk - s * aqk;
+        a[q][k] = s * apk + c * aqk;
+      }
+      a[p][q] = a[q][p] = 0.0;
+      for (int k = 0; k < 3; ++k) {
+        const double vkp = v[k][p], vkq = v[k][q];
+        v[k][p] = c * vkp - s * vkq;
+        v[k][q] = s * vkp + c * vkq;
+      }
+    }
+  }
+}
+
+// normal of one occupied cell from its integer neighbour sums (K, S = sum d, Q = sum d d^T); see include/pcgc.h
+__device__ void normal_from_sums(int K, const int64_t S[3], const int64_t Q[6], int64_t C[6], float out[3]) {
+  // C = K Q - S S^T: c00 c01 c02 c11 c12 c22
+  C[0] = K * Q[0] - S[0] * S[0]; C[1] = K * Q[1] - S[0] * S[1]; C[2] = K * Q[2] - S[0] * S[2];
+  C[3] = K * Q[3] - S[1] * S[1]; C[4] = K * Q[4] - S[1] * S[2]; C[5] = K * Q[5] - S[2] * S[2];
+  double n[3];
+  if (K < 3) {
+    n[0] = 0.0; n[1] = 0.0; n[2] = 1.0;
+  } else {
+    const int64_t m[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
+    bool rank_le1 = true;                         // every 2x2 minor zero
+    for (int r0 = 0; r0 < 3; ++r0)
+      for (int r1 = r0 + 1; r1 < 3; ++r1)
+        for (int c0 = 0; c0 < 3; ++c0)
+          for (int c1 = c0 + 1; c1 < 3; ++c1)
+            rank_le1 = rank_le1 && m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0] == 0;
+    if (rank_le1) {
+      // collinear neighbours: u = the row of C with the largest diagonal entry, normal = normalize(u x e_j)
+      int r = 0;
+      for (int k = 1; k < 3; ++k) if (m[k][k] > m[r][r]) r = k;
+      const double u[3] = {(double)m[r][0], (double)m[r][1], (double)m[r][2]};
+      int j = 0;
+      for (int k = 1; k < 3; ++k) if (fabs(u[k]) < fabs(u[j])) j = k;
+      if (j == 0) { n[0] = 0.0; n[1] = u[2]; n[2] = -u[1]; }
+      else if (j == 1) { n[0] = -u[2]; n[1] = 0.0; n[2] = u[0]; }
+      else { n[0] = u[1]; n[1] = -u[0]; n[2] = 0.0; }
+    } else {
+      double a[3][3], v[3][3];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) a[r][c] = (double)m[r][c];
+      jacobi3(a, v);
+      const int j = a[1][1] < a[0][0] ? (a[2][2] < a[1][1] ? 2 : 1) : (a[2][2] < a[0][0] ? 2 : 0);
+      for (int k = 0; k < 3; ++k) n[k] = j == 0 ? v[k][0] : j == 1 ? v[k][1] : v[k][2];
+    }
+    const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    for (int k = 0; k < 3; ++k) n[k] /= len;
+    for (int k = 0; k < 3; ++k)                   // sign: the first component with |c| > 1e-6 is positive
+      if (fabs(n[k]) > 1e-6) {
+        if (n[k] < 0.0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
+        break;
+      }
+  }
+  for (int k = 0; k < 3; ++k) out[k] = (float)n[k];
+}
+
+// One lane per occupied cell, cells in key order (a wave's probes then share bit-set words).  The lanes of a wave walk
+// the offset table together; the table index is wave-uniform, so its entries come through the scalar cache, and the
+// wave leaves when every lane has max_nn neighbours or the table ends.
+__global__ void __launch_bounds__(256) normals_kernel(const unsigned* bits, const int64_t* ukeys, const int64_t* n_cells, int res,
+                                                      const int32_t* table, int n_table, int max_nn, float* unormals,
+                                                      int64_t* ucov, int32_t* uk) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t nc = *n_cells;
+  if ((int64_t)blockIdx.x * 256 >= nc) return;            // whole workgroup past the end (uniform)
+  const bool live = i < nc;
+  const int64_t key = live ? ukeys[i] : 0;
+  const int x = (int)(key / ((int64_t)res * res)), y = (int)((key / res) % res), z = (int)(key % res);
+  int K = 0;
+  int sx = 0, sy = 0, sz = 0, qxx = 0, qxy = 0, qxz = 0, qyy = 0, qyz = 0, qzz = 0;
+  for (int j = 0; j < n_table; ++j) {
+    const bool need = live && K < max_nn;
+    if (!__any(need)) break;
+    const int e = table[j];
+    const int dx = (e & 63) - 32, dy = ((e >> 6) & 63) - 32, dz = ((e >> 12) & 63) - 32;
+    if (need && occupied(bits, res, x + dx, y + dy, z + dz)) {
+      ++K;
+      sx += dx; sy += dy; sz += dz;
+      qxx += dx * dx; qxy += dx * dy; qxz += dx * dz; qyy += dy * dy; qyz += dy * dz; qzz += dz * dz;
+    }
+  }
+  if (!live) return;
+  const int64_t S[3] = {sx, sy, sz}, Q[6] = {qxx, qxy, qxz, qyy, qyz, qzz};
+  int64_t C[6];
+  float nrm[3];
+  normal_from_sums(K, S, Q, C, nrm);
+  for (int k = 0; k < 3; ++k) unormals[i * 3 + k] = nrm[k];
+  if (ucov) {
+    for (int k = 0; k < 6; ++k) ucov[i * 6 + k] = C[k];
+    uk[i] = K;
+  }
+}
+
+// input order: each point finds its cell among the sorted keys (duplicates share it)
+__global__ void __launch_bounds__(256) normals_gather_kernel(const int32_t* p, int64_t n, int res, const int64_t* ukeys,
+                                                             const int64_t* n_cells, const float* unormals, const int64_t* ucov,
+                                                             const int32_t* uk, float* normals, int64_t* cov, int32_t* nn) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+  const int64_t key = ((int64_t)x * res + y) * res + z;
+  const int64_t nc = *n_cells;
+  int64_t lo = 0, hi = nc;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ukeys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  const bool found = (unsigned)x < (unsigned)res && (unsigned)y < (unsigned)res && (unsigned)z < (unsigned)res && lo < nc &&
+                     ukeys[lo] == key;
+  for (int k = 0; k < 3; ++k) normals[i * 3 + k] = found ? unormals[lo * 3 + k] : 0.f;
+  if (cov) {
+    for (int k = 0; k < 6; ++k) cov[i * 6 + k] = found ? ucov[lo * 6 + k] : 0;
+    nn[i] = found ? uk[lo] : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+// offsets with dx^2 + dy^2 + dz^2 <= r2, sorted by (d^2, dx, dy, dz), packed as (dx+32) | (dy+32) << 6 | (dz+32) << 12.
+// Built once per r2 and kept for the process (the copy to the device reads it asynchronously).
+const std::vector<int32_t>& offset_table(int r2) {
+  static std::mutex mu;
+  static std::map<int, std::vector<int32_t>> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(r2);
+  if (it != cache.end()) return it->second;
+  int r = 0;
+  while ((r + 1) * (r + 1) <= r2) ++r;
+  std::vector<std::array<int, 4>> e;
+  for (int dx = -r; dx <= r; ++dx)
+    for (int dy = -r; dy <= r; ++dy)
+      for (int dz = -r; dz <= r; ++dz) {
+        const int d2 = dx * dx + dy * dy + dz * dz;
+        if (d2 <= r2) e.push_back({d2, dx, dy, dz});
+      }
+  std::sort(e.begin(), e.end());
+  std::vector<int32_t> t(e.size());
+  for (size_t k = 0; k < e.size(); ++k) t[k] = (e[k][1] + 32) | ((e[k][2] + 32) << 6) | ((e[k][3] + 32) << 12);
+  return cache.emplace(r2, std::move(t)).first->second;
+}
+
+int radius2(double radius) { return (int)std::floor(radius * radius); }
+
+int64_t scan_blocks(int64_t cells) { return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32); }
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+}  // namespace pcgc
+
+using namespace pcgc;
+
+extern "C" {
+
+int pcgc_mesh_sample(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                     const double* area_cdf, int64_t n_points, uint64_t seed, const double* rotation, double* points,
+                     pcgc_stream_t stream) {
+  PCGC_REQUIRE(n_points >= 0 && (n_points == 0 || (vertices && n_vertices > 0 && triangles && n_triangles > 0 && area_cdf && points)),
+               "pcgc_mesh_sample: bad arguments");
+  if (n_points == 0) return 0;
+  hipLaunchKernelGGL(mesh_sample_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vertices,
+                     triangles, area_cdf, n_triangles, n_points, seed, rotation, points);
+  return launch_ok("mesh_sample_kernel");
+}
+
+size_t pcgc_mesh_voxelize_workspace_bytes(int resolution) {
+  if (resolution < 1 || resolution > 4095) return 0;
+  const int64_t G = resolution + 1, nblk = scan_blocks(G * G * G);
+  return align256((size_t)nblk * kScanWords * sizeof(unsigned)) + align256((size_t)nblk * sizeof(int64_t)) +
+         align256(2 * kMinMaxBlocks * sizeof(double)) + 256;
+}
+
+int pcgc_mesh_voxelize(const double* points, int64_t n, int resolution, int32_t* out, int64_t cap, int64_t* n_out,
+                       void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(points && out && n_out && n > 0 && resolution >= 1 && resolution <= 4095 && workspace,
+               "pcgc_mesh_voxelize: bad arguments");
+  PCGC_REQUIRE(cap >= n, "pcgc_mesh_voxelize: capacity %lld below the %lld input points", (long long)cap, (long long)n);
+  PCGC_REQUIRE(workspace_bytes >= pcgc_mesh_voxelize_workspace_bytes(resolution), "pcgc_mesh_voxelize: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t G = resolution + 1, nblk = scan_blocks(G * G * G);
+  char* w = static_cast<char*>(workspace);
+  unsigned* bits = reinterpret_cast<unsigned*>(w);
+  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  int64_t* block_count = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)nblk * sizeof(int64_t));
+  double* partial = reinterpret_cast<double*>(w);
+  w += align256(2 * kMinMaxBlocks * sizeof(double));
+  double* mm = reinterpret_cast<double*>(w);
+  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)nblk * kScanWords * sizeof(unsigned), s));
+  const int64_t m = 3 * n;
+  const int nb = (int)std::min<int64_t>(kMinMaxBlocks, (m + 255) / 256);
+  hipLaunchKernelGGL(mesh_minmax_partial_kernel, dim3(nb), dim3(256), 0, s, points, m, partial);
+  hipLaunchKernelGGL(mesh_minmax_final_kernel, dim3(1), dim3(64), 0, s, partial, nb, mm);
+  hipLaunchKernelGGL(mesh_quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, mm, resolution, bits);
+  hipLaunchKernelGGL(bits_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
+  hipLaunchKernelGGL(bits_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_out);
+  hipLaunchKernelGGL(bits_compact_kernel<true>, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count, G, cap, out,
+                     (int64_t*)nullptr);
+  return launch_ok("mesh voxelize kernels");
+}
+
+int pcgc_normals_table_size(double radius) {
+  if (!(radius >= 0.0 && radius <= 16.0)) return -1;
+  return (int)offset_table(radius2(radius)).size();
+}
+
+size_t pcgc_normals_workspace_bytes(int res, int64_t n, double radius) {
+  if (res < 1 || res > 4096 || n < 0 || !(radius >= 0.0 && radius <= 16.0)) return 0;
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  const size_t nt = offset_table(radius2(radius)).size();
+  return align256((size_t)nblk * kScanWords * sizeof(unsigned)) + align256((size_t)nblk * sizeof(int64_t)) + 256 +
+         align256((size_t)n * sizeof(int64_t)) + align256((size_t)n * 3 * sizeof(float)) +
+         align256((size_t)n * 6 * sizeof(int64_t)) + align256((size_t)n * sizeof(int32_t)) + align256(nt * sizeof(int32_t));
+}
+
+int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radius, int max_nn, float* normals, int64_t* cov,
+                          int32_t* n_neighbours, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(points && normals && n > 0 && res >= 1 && res <= 4096 && radius >= 0.0 && radius <= 16.0 && max_nn >= 1 &&
+               max_nn <= 64 && workspace && (cov == nullptr) == (n_neighbours == nullptr),
+               "pcgc_estimate_normals: bad arguments");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_normals_workspace_bytes(res, n, radius), "pcgc_estimate_normals: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const std::vector<int32_t>& table = offset_table(radius2(radius));
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  char* w = static_cast<char*>(workspace);
+  unsigned* bits = reinterpret_cast<unsigned*>(w);
+  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  int64_t* block_count = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)nblk * sizeof(int64_t));
+  int64_t* n_cells = reinterpret_cast<int64_t*>(w);
+  w += 256;
+  int64_t* ukeys = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)n * sizeof(int64_t));
+  float* unormals = reinterpret_cast<float*>(w);
+  w += align256((size_t)n * 3 * sizeof(float));
+  int64_t* ucov = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)n * 6 * sizeof(int64_t));
+  int32_t* uk = reinterpret_cast<int32_t*>(w);
+  w += align256((size_t)n * sizeof(int32_t));
+  int32_t* dtable = reinterpret_cast<int32_t*>(w);
+  PCGC_CHECK_HIP(hipMemcpyAsync(dtable, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)nblk * kScanWords * sizeof(unsigned), s));
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(normals_bitset_kernel, dim3(grid), dim3(256), 0, s, points, n, res, bits);
+  hipLaunchKernelGGL(bits_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
+  hipLaunchKernelGGL(bits_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_cells);
+  hipLaunchKernelGGL(bits_compact_kernel<false>, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count, (int64_t)res, n,
+                     (int32_t*)nullptr, ukeys);
+  hipLaunchKernelGGL(normals_kernel, dim3(grid), dim3(256), 0, s, bits, ukeys, n_cells, res, dtable, (int)table.size(), max_nn,
+                     unormals, cov ? ucov : nullptr, uk);
+  hipLaunchKernelGGL(normals_gather_kernel, dim3(grid), dim3(256), 0, s, points, n, res, ukeys, n_cells, unormals, ucov, uk, normals,
+                     cov, n_neighbours);
+  return launch_ok("normal estimation kernels");
+}
+
+}  // extern "C"

@@ -194,6 +194,37 @@ def write_ply_data(filename, points):
         f.write(body)
 
 
+
+def write_ply_normals(filename, points, normals):
+    """The writer of dataprocess/mesh2pc_open3d.py:26-47: `x y z nx ny nz` float properties, each line
+    str(int) of the coordinates and str(round(v, 6)) of the normal's float64 components.  load_ply_normals reads it back,
+    load_ply_data / generate_dataset take its first three columns."""
+    points = np.asarray(points).astype("int").reshape(-1, 3)
+    normals = np.asarray(normals).astype("float").reshape(-1, 3)
+    if len(points) != len(normals):
+        raise ValueError("write_ply_normals: %d points, %d normals" % (len(points), len(normals)))
+    head = ("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property float nx\nproperty float ny\nproperty float nz\nend_header\n" % len(points))
+    with open(filename, "w") as f:
+        f.write(head)
+        if len(points):
+            # str() of every distinct value once (np.round is what round(np.float64, 6) calls)
+            cols = [_str_table(points[:, k]) for k in range(3)] + [_str_table(np.round(normals[:, k], 6)) for k in range(3)]
+            line = cols[0]
+            for c in cols[1:]:
+                line = np.char.add(np.char.add(line, " "), c)
+            f.write("\n".join(line.tolist()))
+            f.write("\n")
+
+
+def _str_table(v):
+    """str() of each element, formed once per distinct value (floats by bit pattern: -0.0 prints apart from 0.0)"""
+    v = np.ascontiguousarray(v)
+    key = v.view(np.int64) if v.dtype == np.float64 else v
+    uniq, inv = np.unique(key, return_inverse=True)
+    vals = uniq.view(np.float64) if v.dtype == np.float64 else uniq
+    return np.array([str(x) for x in vals])[inv.reshape(-1)]
+
 # ---------------------------------------------------------------------------- partition
 def _order_key(cube_positions):
     cube_positions = np.asarray(cube_positions).astype(np.int64)

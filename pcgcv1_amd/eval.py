@@ -210,14 +210,19 @@ def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None,
 
 
 def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname="pcgcv1_amd.models.model_voxception",
-         fixed_thres=None, postfix=""):
+         fixed_thres=None, postfix="", estimate_normals=False):
     """eval.py:160-215.  The config .ini has DEFAULT {cube_size, min_num} and one section per rate with
-    {scale, ckpt_dir, rho_d1, rho_d2} (eval.py:170-183).  Returns the list of result rows (dicts)."""
+    {scale, ckpt_dir, rho_d1, rho_d2} (eval.py:170-183).  Returns the list of result rows (dicts).
+    estimate_normals=True: an input ply without normals gets them from metrics.estimate_normals(points, 10, 20) (the
+    radius / max_nn with which mesh2pc_open3d.py:75-78 wrote the reference's test sets), so D2 and the rho_d2 search run
+    as for a ply that carries normals.  A ply with normals keeps its own either way."""
     if mode not in ("hyper", "factorized"):
         raise ValueError("eval: mode must be 'hyper' or 'factorized' (got %r)" % (mode,))
     hyper = mode == "hyper"
     model = importlib.import_module("pcgcv1_amd." + modelname if modelname.startswith("models.") else modelname)
     points, normals = iop.load_ply_normals(input_file)
+    if normals is None and estimate_normals:
+        normals = metrics.estimate_normals(points, radius=10, max_nn=20)
     filename = os.path.split(input_file)[-1][:-4]
     os.makedirs(rootdir, exist_ok=True)
     config = configparser.ConfigParser()
@@ -289,9 +294,12 @@ def main(argv=None):
     ap.add_argument("--modelname", type=str, default="pcgcv1_amd.models.model_voxception")
     ap.add_argument("--fixed_thres", type=float, default=None)
     ap.add_argument("--postfix", type=str, default="")
+    ap.add_argument("--estimate_normals", action="store_true",
+                    help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
-        for r in eval(input_file, a.rootdir, a.cfgdir, a.res, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix):
+        for r in eval(input_file, a.rootdir, a.cfgdir, a.res, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix,
+                      a.estimate_normals):
             print(r)
 
 

@@ -10,13 +10,13 @@ import os
 from . import eval as rd
 
 
-def eval(input_file, rootdir, resolution, mode, cube_size, modelname, fixed_thres, postfix, ckpt_root=None):
+def eval(input_file, rootdir, resolution, mode, cube_size, modelname, fixed_thres, postfix, ckpt_root=None, estimate_normals=False):
     csv_rootdir = os.path.join(rootdir, "csv")
     cfg_rootdir = os.path.join(rootdir, "cfg")
     os.makedirs(csv_rootdir, exist_ok=True)
     _, config_file = rd.set_default_config(input_file, cfg_rootdir, resolution, mode, cube_size, ckpt_root=ckpt_root, modelname=modelname)
     return rd.eval(input_file, csv_rootdir, config_file, resolution, mode=mode, cube_size=cube_size, modelname=modelname,
-                   fixed_thres=fixed_thres, postfix=postfix)
+                   fixed_thres=fixed_thres, postfix=postfix, estimate_normals=estimate_normals)
 
 
 def main(argv=None):
@@ -32,9 +32,12 @@ def main(argv=None):
     ap.add_argument("--postfix", type=str, default="", dest="postfix")
     ap.add_argument("--ckpt_root", type=str, default=None, help="where the default config looks for a<alpha>b3 directories "
                                                                 "(default ./checkpoints/<mode>)")
+    ap.add_argument("--estimate_normals", action="store_true",
+                    help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
-        for row in eval(input_file, a.rootdir, a.resolution, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix, a.ckpt_root):
+        for row in eval(input_file, a.rootdir, a.resolution, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix, a.ckpt_root,
+                        a.estimate_normals):
             print(row)
 
 

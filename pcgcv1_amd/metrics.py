@@ -84,6 +84,38 @@ def d2_metrics(points_a, normals_a, points_b, resolution):
             "h.       1(p2plane)": h1, "h.       2(p2plane)": h2, "h.        (p2plane)": max(h1, h2)}
 
 
+
+def estimate_normals(points, radius=10, max_nn=20, return_cov=False):
+    """Normals of a voxelised cloud, as mesh2pc_open3d.py:75-78 writes them with
+    estimate_normals(KDTreeSearchParamHybrid(radius=10, max_nn=20)): the first max_nn occupied cells of the offsets
+    within `radius` sorted by (|d|^2, dx, dy, dz), the smallest eigenvector of their integer covariance, first
+    significant component positive (include/pcgc.h, pcgc_estimate_normals).  points: int [N,3] >= 0 (numpy, or an int32
+    device tensor); -> float32 [N,3] numpy in input order.  return_cov=True also returns the covariance matrices
+    K sum d d^T - (sum d)(sum d)^T as int64 [N,6] (c00 c01 c02 c11 c12 c22) and the neighbour counts K int32 [N]."""
+    dev = _lib.require_gpu()
+    lib = _lib.hip()
+    p_d = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points, np.int32).reshape(-1, 3))
+    p_d = p_d.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    n = int(p_d.shape[0])
+    if not (0.0 <= float(radius) <= 16.0) or not (1 <= int(max_nn) <= 64):
+        raise ValueError("estimate_normals: radius must be within [0, 16] and max_nn within [1, 64]")
+    if n == 0:
+        empty = np.zeros((0, 3), np.float32)
+        return (empty, np.zeros((0, 6), np.int64), np.zeros(0, np.int32)) if return_cov else empty
+    lo, hi = (int(v) for v in torch.stack([p_d.min(), p_d.max()]).cpu())
+    if lo < 0 or hi >= 4096:
+        raise ValueError("estimate_normals: coordinates must lie within [0, 4096) (got %d .. %d)" % (lo, hi))
+    res = hi + 1
+    ws = torch.empty(int(lib.pcgc_normals_workspace_bytes(res, n, float(radius))), dtype=torch.uint8, device=dev)
+    nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    cov = torch.empty((n, 6), dtype=torch.int64, device=dev) if return_cov else None
+    k = torch.empty(n, dtype=torch.int32, device=dev) if return_cov else None
+    _lib.check(lib.pcgc_estimate_normals(_lib.dptr(p_d), n, res, float(radius), int(max_nn), _lib.dptr(nrm), _lib.dptr(cov),
+                                         _lib.dptr(k), _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_estimate_normals")
+    if return_cov:
+        return nrm.cpu().numpy(), cov.cpu().numpy(), k.cpu().numpy()
+    return nrm.cpu().numpy()
+
 def _off_grid(points):
     p = np.asarray(points)
     return np.issubdtype(p.dtype, np.floating) and bool((p != np.rint(p)).any())
