@@ -263,6 +263,41 @@ int pcgc_voxelize(const int32_t* cube_xyz, int64_t n, int cube_size, float* cube
 int pcgc_voxelize_points(const int32_t* points, const int32_t* cube_of_point, int64_t n, int cube_size,
                          int cube_lo, int cube_hi, float* cubes, pcgc_stream_t stream);
 
+/* ---- encoder-side point counts (.pointnums) for the smallest cube-local D1 ----------------------------------------
+ * The decoder keeps, per cube, the voxels whose logit is >= the k-th largest, ties included, with k = the stored count
+ * (select_voxels / get_adaptive_thres, dataprocess/inout_points.py:147-179; pcgc_topk_threshold).  eval's rho search
+ * (eval_ablation_studies.py:152-205) picks one rho for the whole cloud with the original at hand; these entry points let
+ * the encoder pick every cube's k instead.  cubes: x float32 [B, cs, cs, cs] (occupied: x > 0), logits the same shape,
+ * both on the device; cs <= 256.  Coordinates are the voxel indices inside the cube; distances squared, in integers.
+ *
+ * pcgc_pointnums_count: k_max int32 [B] (1 <= k_max <= cs^3) -> thresholds[b] = the k_max-th largest logit,
+ * n_pts[b] = #occupied voxels, n_seg[b] = #voxels with logit >= thresholds[b] (all device).
+ *
+ * pcgc_pointnums_curves: for cubes whose counts came from pcgc_pointnums_count, with device int64 offsets pts_off /
+ * seg_off / curve_off [B+1] (prefix sums of n_pts, n_seg and k_max, starting at 0; total_seg / total_pts their last
+ * entries) and block lists seg_blocks / pts_blocks (int32 pairs (cube, first element) cutting every cube's n_seg /
+ * n_pts elements into pieces of 256): for k = 1 .. k_max[b], at curve_off[b] + k - 1,
+ *   m = |S(k)|, S(k) = { v : logit[v] >= the k-th largest logit }  (-0.0 == +0.0),
+ *   A = sum over occupied p of min over v in S(k) |p - v|^2,   B = sum over v in S(k) of min over occupied p |v - p|^2
+ * (B = 0 for a cube without occupied voxels).  Exact integers; the memory of one call grows with total_seg: call it on
+ * chunks of cubes (pcgcv1_amd/pointnums.py).
+ *
+ * pcgc_pointnums_sweep: the curves above -> for assignment a < J + 1 and every cube, k_out[a B + b] = argmin over k of
+ * a A(k) + (J - a) B(k) in int64 (ties: the smallest k); for a = J + 1 + l, k_out = fixed_k[l B + b] clamped to
+ * 1 .. k_max[b].  sums[3 a + {0, 1, 2}] = sum over the cubes of A, B, m at the assignment's k (device int64). */
+int pcgc_pointnums_count(const float* x, const float* logits, const int32_t* k_max, int B, int cube_size,
+                         float* thresholds, int32_t* n_pts, int32_t* n_seg, pcgc_stream_t stream);
+size_t pcgc_pointnums_curves_workspace_bytes(int64_t total_seg, int64_t total_pts);
+int pcgc_pointnums_curves(const float* x, const float* logits, const float* thresholds, int B, int cube_size,
+                          const int64_t* pts_off, const int64_t* seg_off, const int64_t* curve_off, int64_t total_seg,
+                          int64_t total_pts, const int32_t* seg_blocks, int n_seg_blocks, const int32_t* pts_blocks,
+                          int n_pts_blocks, int32_t* m, int64_t* A, int64_t* Bc, void* workspace,
+                          size_t workspace_bytes, pcgc_stream_t stream);
+size_t pcgc_pointnums_sweep_workspace_bytes(int B, int n_assign);
+int pcgc_pointnums_sweep(const int32_t* m, const int64_t* A, const int64_t* Bc, const int64_t* curve_off, int B, int J,
+                         const int32_t* fixed_k, int L, int32_t* k_out, int64_t* sums, void* workspace,
+                         size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- mesh -> point cloud with normals (dataprocess/mesh2pc_open3d.py:55-85) ---- */
 /* sample_points_uniformly + np.dot(points, get_rotate_matrix()) (mesh2pc_open3d.py:57-66).  vertices double [V,3],
  * triangles int32 [T,3], area_cdf double [T] = inclusive running sum of the triangle areas (pcgc_mesh_area_cdf), all on

@@ -51,6 +51,12 @@ HIP_API = {
     "pcgc_focal_loss_bwd": (c_int, [c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "pcgc_voxelize": (c_int, [c_vp, c_i64, c_int, c_vp, c_int, c_vp]),
     "pcgc_voxelize_points": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
+    "pcgc_pointnums_count": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "pcgc_pointnums_curves_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcgc_pointnums_curves": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_vp, c_int,
+                                      c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_pointnums_sweep_workspace_bytes": (c_sz, [c_int, c_int]),
+    "pcgc_pointnums_sweep": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_mesh_sample": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.c_uint64, c_vp, c_vp, c_vp]),
     "pcgc_mesh_voxelize_workspace_bytes": (c_sz, [c_int]),
     "pcgc_mesh_voxelize": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),

@@ -36,6 +36,7 @@ HIP_SOURCES = {
     "train_plan.hip": [],
     "hyper_row.hip": [],
     "mesh.hip": ["-ffp-contract=off"],
+    "pointnums.hip": ["-ffp-contract=off"],
 }
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-fno-gpu-rdc"]

@@ -159,11 +159,18 @@ def start_rate_point(points, model, ckpt_dir, scale, cube_size, min_num):
     return cube_positions, points_numbers, compress_hyper_ahead(cubes, model, ckpt_dir)
 
 
-def _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None):
+def _d1_counts(cubes, logits, points_numbers):
+    from .pointnums import optimize_points_numbers
+    return optimize_points_numbers(cubes, logits, points_numbers)[0]
+
+
+def _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, pointnums="count"):
     """eval.py:45-75 without the metrics: compress_factorized, the three-file container written and read back,
     decompress_factorized.  bpps like rate_point's, the hyper and head terms 0 (eval.py:69-71)."""
     cubes, cube_positions, points_numbers = preprocess_points(points, scale, cube_size, min_num)
     strings, min_v, max_v, shape = compress_factorized(cubes, model, ckpt_dir)
+    if pointnums == "d1":
+        points_numbers = _d1_counts(cubes, decompress_factorized(strings, min_v, max_v, shape, model, ckpt_dir), points_numbers)
     own_tmp = rootdir is None
     rootdir = rootdir or tempfile.mkdtemp(prefix="pcgc_eval_")
     sizes = bs.write_binary_files_factorized("x", strings, points_numbers, cube_positions, min_v, max_v, shape, rootdir=rootdir,
@@ -180,13 +187,19 @@ def _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, r
     return cubes_d, pos_d, nums_d, int(n), bpps
 
 
-def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, started=None, mode="hyper"):
+def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, started=None, mode="hyper", pointnums="count"):
     """eval.py:77-113 (hyper) / 45-75 (factorized) without the metrics: returns (decoded cubes, cube_positions,
     points_numbers, N, bpps) with bpps = [total, strings, strings_hyper, strings_head, pointnums, cubepos] rounded to
-    4 decimals like the reference."""
+    4 decimals like the reference.  pointnums="d1": the container holds pointnums.optimize_points_numbers' counts (the
+    encoder-side reconstruction's; `started` is not used then)."""
     if mode == "factorized":
-        return _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir)
-    if started is not None:
+        return _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir, pointnums)
+    if pointnums == "d1":
+        cubes, cube_positions, points_numbers = preprocess_points(points, scale, cube_size, min_num)
+        out = compress_hyper(cubes, model, ckpt_dir, decompress=True)
+        points_numbers = _d1_counts(cubes, out[8], points_numbers)
+        stream = out[:8]
+    elif started is not None:
         cube_positions, points_numbers, ahead = started
         stream = ahead.result()
     else:
@@ -210,12 +223,14 @@ def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None,
 
 
 def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname="pcgcv1_amd.models.model_voxception",
-         fixed_thres=None, postfix="", estimate_normals=False):
+         fixed_thres=None, postfix="", estimate_normals=False, pointnums="count"):
     """eval.py:160-215.  The config .ini has DEFAULT {cube_size, min_num} and one section per rate with
     {scale, ckpt_dir, rho_d1, rho_d2} (eval.py:170-183).  Returns the list of result rows (dicts).
     estimate_normals=True: an input ply without normals gets them from metrics.estimate_normals(points, 10, 20) (the
     radius / max_nn with which mesh2pc_open3d.py:75-78 wrote the reference's test sets), so D2 and the rho_d2 search run
-    as for a ply that carries normals.  A ply with normals keeps its own either way."""
+    as for a ply that carries normals.  A ply with normals keeps its own either way.
+    pointnums="d1": every rate point writes the encoder's D1-optimised counts (pointnums.py) instead of the true ones; the
+    rest of the row (rho search, the three reconstructions) is computed the same way on that container."""
     if mode not in ("hyper", "factorized"):
         raise ValueError("eval: mode must be 'hyper' or 'factorized' (got %r)" % (mode,))
     hyper = mode == "hyper"
@@ -237,11 +252,15 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
 
     def start(rate):
         return start_rate_point(points, model, str(config.get(rate, "ckpt_dir")), float(config.get(rate, "scale")), cube_size, min_num)
-    started = start(rates[0]) if rates and hyper else None
+    ahead = hyper and pointnums == "count"                   # d1 needs the cubes at the encoder: no encode ahead
+    started = start(rates[0]) if rates and ahead else None
     for k, rate in enumerate(rates):
         scale = float(config.get(rate, "scale"))
         ckpt_dir = str(config.get(rate, "ckpt_dir"))
-        if hyper:
+        if hyper and not ahead:
+            cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num,
+                                                                          pointnums=pointnums)
+        elif hyper:
             cur, started = started, None
             cur[2].result()                                   # this rate's strings exist (rate_point picks them up below)
             if k + 1 < len(rates):
@@ -249,7 +268,7 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
             cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num, started=cur)
         else:                                                 # eval.py:188-189: test_factorized (one stream per cloud, nothing to overlap)
             cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num,
-                                                                          mode="factorized")
+                                                                          mode="factorized", pointnums=pointnums)
 
         def measure(rho):
             rec = postprocess_points(cubes_d, points_numbers, cube_positions, scale, cube_size, rho, fixed_thres)
@@ -296,10 +315,12 @@ def main(argv=None):
     ap.add_argument("--postfix", type=str, default="")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
+    ap.add_argument("--pointnums", choices=("count", "d1"), default="count",
+                    help="what the container's .pointnums holds: the true counts, or the encoder's D1-optimised ones")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
         for r in eval(input_file, a.rootdir, a.cfgdir, a.res, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix,
-                      a.estimate_normals):
+                      a.estimate_normals, a.pointnums):
             print(r)
 
 

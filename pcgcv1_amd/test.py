@@ -23,6 +23,8 @@ _FLAGS = [
     ("cube_size", int, 64, "edge of the cubes the cloud is cut into"),
     ("min_num", int, 64, "cubes with fewer points are dropped"),
     ("rho", float, 1.0, "output points per cube = rho x the stored point count"),
+    ("pointnums", str, "count", "what .pointnums holds: 'count' = each cube's point count (the reference's); 'd1' = the counts "
+                                "that give the decoder at rho = 1 the smallest cube-local D1 (pcgcv1_amd/pointnums.py)"),
     ("gpu", int, 1, "GPUs to use: 1 = this process; N > 1 = the cube list sharded over N ranks, one per GPU (started here "
                     "unless a launcher already set WORLD_SIZE); 0 is refused: there is no CPU path"),
 ]
@@ -35,7 +37,8 @@ def parse_args(argv=None):
     ap.add_argument("input", nargs="?", help="point cloud (.ply) or compressed file stem")
     ap.add_argument("output", nargs="?", help="output stem / .ply (derived from the input when omitted)")
     for name, typ, default, meaning in _FLAGS:
-        ap.add_argument("--" + name, type=typ, default=default, help=meaning)
+        ap.add_argument("--" + name, type=typ, default=default, help=meaning,
+                        **({"choices": ("count", "d1")} if name == "pointnums" else {}))
     args = ap.parse_args(argv)
     print(args)
     return args
@@ -56,6 +59,15 @@ def _report(model, ckpt_dir, t0, also=""):
                                                            p.get("pipelines"), "" if p.get("pipelines") == 1 else "s"))
 
 
+def _d1_counts(cubes, logits, points_numbers):
+    """--pointnums=d1: the counts pointnums.optimize_points_numbers picks for these logits, with a line on what it chose"""
+    from .pointnums import optimize_points_numbers
+    counts, rep = optimize_points_numbers(cubes, logits, points_numbers)
+    print("pointnums d1: chose {} {}; cube-local D1 mse {:.6g} -> {:.6g} (PSNR {:.4f} -> {:.4f} dB at peak 1023)".format(
+        rep["choice"][0], rep["choice"][1], rep["F_count"], rep["F_chosen"], rep["psnr_count"], rep["psnr_chosen"]))
+    return counts
+
+
 def _main_sharded(args, world):
     """One process per GPU (`python -m torch.distributed.run --nproc-per-node N -m pcgcv1_amd.test ...`): the cube
     list is split over the ranks (pcgcv1_amd/sharding.py), rank 0 reads and writes the files.  Same files as one GPU."""
@@ -66,6 +78,8 @@ def _main_sharded(args, world):
     from .process import postprocess_masks, preprocess
     if args.mode != "hyper":
         raise SystemExit("multi-GPU runs are implemented for --mode=hyper")
+    if args.pointnums != "count":
+        raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 runs on one GPU)")
     rank = int(os.environ.get("RANK", "0"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     if not dist.is_initialized():
@@ -117,6 +131,8 @@ def main(argv=None):
     if args.gpu < 1:
         raise SystemExit("--gpu=0: this build runs the hot path on an MI355X only (no CPU fallback)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if (args.gpu > 1 or world > 1) and args.pointnums != "count":
+        raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 runs on one GPU)")
     if args.gpu > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(argv, args.gpu))
     if args.gpu > 1 and world != args.gpu:                 # e.g. --gpu=8 under `torchrun --nproc-per-node 1`: never silently one GPU
@@ -134,6 +150,9 @@ def main(argv=None):
         cubes, cube_positions, points_numbers = preprocess(args.input, args.scale, args.cube_size, args.min_num)
         if args.mode == "factorized":
             strings, min_v, max_v, shape = compress_factorized(cubes, model, args.ckpt_dir, verbose=True)
+            if args.pointnums == "d1":           # the decoder's logits: decode the strings as decompress does
+                logits = decompress_factorized(strings, min_v, max_v, shape, model, args.ckpt_dir)
+                points_numbers = _d1_counts(cubes, logits, points_numbers)
             bs.write_binary_files_factorized(args.output, strings, points_numbers, cube_positions, min_v, max_v, shape,
                                              rootdir='./compressed')
         else:
@@ -148,8 +167,13 @@ def main(argv=None):
                 time.sleep(0.003)
                 return bs.encode_cube_positions(cube_positions)
             cubepos = _lib.workers("job").submit(_cubepos)
-            (y_strings, y_min_vs, y_max_vs, y_shape, z_strings, z_min_v, z_max_v, z_shape) = compress_hyper(
-                cubes, model, args.ckpt_dir, verbose=stage_times)
+            if args.pointnums == "d1":           # the encoder-side reconstruction is what the decoder will compute
+                out = compress_hyper(cubes, model, args.ckpt_dir, decompress=True, verbose=stage_times)
+                points_numbers = _d1_counts(cubes, out[8], points_numbers)
+                out = out[:8]
+            else:
+                out = compress_hyper(cubes, model, args.ckpt_dir, verbose=stage_times)
+            (y_strings, y_min_vs, y_max_vs, y_shape, z_strings, z_min_v, z_max_v, z_shape) = out
             _report(model, args.ckpt_dir, t0)
             bs.write_binary_files_hyper(args.output, y_strings, z_strings, points_numbers, cube_positions, y_min_vs,
                                         y_max_vs, y_shape, z_min_v, z_max_v, z_shape, rootdir='./compressed',
