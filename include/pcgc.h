@@ -252,6 +252,29 @@ int pcgc_d2_transfer_normals(const int32_t* p, int64_t np, const float* normals_
 int pcgc_d2_mse(const int32_t* p, int64_t np, const int64_t* qkeys, int64_t nq, const float* normals_q, int res,
                 double* out2, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* Recolouring: the colours of the original cloud S (int32 xyz < res, unique, uint8 rgb per point) carried onto the decoded
+ * geometry T, passed like the D2 target as its linear keys (x*res + y)*res + z, int64, SORTED ascending and unique;
+ * target_colors uint8 [n_t,3] and backward_counts int32 [n_t] (may be NULL) are in that order.  With N_T(s) = all points
+ * of T at the minimal distance from s (ties kept) and B(t) = { s : t in N_T(s) }:
+ *   colour(t) = per channel (2 sum_{s in B(t)} c_s + |B(t)|) / (2 |B(t)|), the mean rounded half up,
+ *   over N_S(t), t's own nearest points of S, where B(t) is empty;  backward_counts[t] = |B(t)|.
+ * Integer arithmetic throughout (32-bit atomic sums: n_s <= 2^32 / 255), so the result is defined bit for bit.
+ * The workspace holds one occupancy bit set of res^3 cells and its rank table (popcount prefix per word). */
+size_t pcgc_recolor_workspace_bytes(int res, int64_t n_s, int64_t n_t);
+int pcgc_recolor(const int32_t* source_points, const uint8_t* source_colors, int64_t n_s, const int64_t* target_keys,
+                 int64_t n_t, int res, uint8_t* target_colors, int32_t* backward_counts, void* workspace,
+                 size_t workspace_bytes, pcgc_stream_t stream);
+
+/* Colour distortion of MPEG pc_error 0.13.4 (`--color=1`), one direction: out3[i] = "c[i],    1" = mean over the points a
+ * of A of (yuv_a[i] - yuv_m[i])^2, where m = per channel floor(mean of B's colours over ALL nearest points of B + 0.5)
+ * in integers and yuv = BT.709 of rgb / 255 in float64 (Y = .2126 R + .7152 G + .0722 B, U = -.1146 R - .3854 G + .5 B + .5,
+ * V = .5 R - .4542 G - .0458 B + .5).  Both clouds int32 xyz < res, unique, with uint8 rgb per point, in any order.  Call
+ * twice (A->B, B->A); PSNR = -10 log10(mse), the symmetric figure takes the larger mse.  Deterministic (fixed-order sums). */
+size_t pcgc_color_mse_workspace_bytes(int res, int64_t n_b);
+int pcgc_color_mse(const int32_t* points_a, const uint8_t* colors_a, int64_t n_a, const int32_t* points_b,
+                   const uint8_t* colors_b, int64_t n_b, int res, double* out3, void* workspace, size_t workspace_bytes,
+                   pcgc_stream_t stream);
+
 /* points2voxels (dataprocess/inout_points.py:116-132) on device: scatter
  * n points (cube index, x, y, z as int32 x4) into zero-initialised float cubes. */
 int pcgc_voxelize(const int32_t* cube_xyz, int64_t n, int cube_size, float* cubes,
@@ -622,6 +645,20 @@ int pcgc_parse_ply_points(const char* text, int64_t len, int32_t* out, int64_t c
  * as Python's str(int).  *out_len always receives the exact text length (never more than 63 bytes per point); with a
  * smaller cap (or out == NULL) nothing is written and the call returns -2. */
 int pcgc_format_points_int(const int64_t* pts, int64_t n, char* out, int64_t cap, int64_t* out_len);
+
+/* Named numeric columns of an ASCII ply body (what follows the end_header line): every line that is not blank is a row of
+ * whitespace-separated numbers, and out[row * k + j] receives the value of token columns[j] (0-based, in header order of
+ * the properties) as a double.  At most max_rows rows are read (< 0: all; the vertex count of the header, so that face
+ * lists are not taken for vertices).  out holds cap x k values; *n_rows always receives the count, and with a smaller
+ * cap nothing is written and the call returns -2.  A row with too few tokens, or a token that is not a number, is an
+ * error (-3) that names the line. */
+int pcgc_parse_ply_columns(const char* text, int64_t len, const int32_t* columns, int k, int64_t max_rows, double* out,
+                           int64_t cap, int64_t* n_rows, int n_threads);
+
+/* Body of a coloured ply for integer coordinates: "x y z r g b\n" per point, digits as Python's str(int); pts int64
+ * [n,3], colors uint8 [n,3].  Same protocol as pcgc_format_points_int. */
+int pcgc_format_points_colors_int(const int64_t* pts, const uint8_t* colors, int64_t n, char* out, int64_t cap,
+                                  int64_t* out_len);
 
 /* o3d.io.read_triangle_mesh (mesh2pc_open3d.py:58) for the two formats the reference feeds it: format 0 = OFF
  * (ModelNet40, including its "OFF490 518 0" first line with the counts glued to the magic; extra per-vertex or per-face

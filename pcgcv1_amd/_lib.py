@@ -68,6 +68,10 @@ HIP_API = {
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),
     "pcgc_d2_transfer_normals": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_recolor_workspace_bytes": (c_sz, [c_int, c_i64, c_i64]),
+    "pcgc_recolor": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_color_mse_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_color_mse": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_conv3d_bwd_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "pcgc_conv3d_bwd_data": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "pcgc_conv3d_bwd_data_fused": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
@@ -135,6 +139,8 @@ HOST_API = {
     "pcgc_host_repro_eval": (c_int, [c_int, c_vp, c_vp, c_i64]),
     "pcgc_format_points_int": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pcgc_parse_ply_points": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int]),
+    "pcgc_parse_ply_columns": (c_int, [c_vp, c_i64, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, c_int]),
+    "pcgc_format_points_colors_int": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pcgc_parse_mesh": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "pcgc_mesh_area_cdf": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
 }

@@ -37,6 +37,7 @@ HIP_SOURCES = {
     "hyper_row.hip": [],
     "mesh.hip": ["-ffp-contract=off"],
     "pointnums.hip": ["-ffp-contract=off"],
+    "color.hip": ["-ffp-contract=off"],
 }
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-fno-gpu-rdc"]

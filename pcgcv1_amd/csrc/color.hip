@@ -1,0 +1,408 @@
+// Colour kernels (gfx950): recolouring of a decoded cloud from the original, and the colour distortion of MPEG pc_error
+// 0.13.4 (`--color=1`).  DESIGN.md "Colours" states both rules; tests/_color_ref.py restates them in numpy.
+//
+// Clouds are voxelised (integer coordinates < res, unique).  The cloud that is SEARCHED becomes an occupancy bit set, as in
+// the D1 / D2 kernels of tail.hip, and every point of the other cloud walks Chebyshev shells of growing radius until no
+// unvisited cell can be nearer.  The index of an occupied cell among the cloud's points in key order (key = (x*res + y)*res
+// + z) comes from a rank structure over the bit set: the exclusive prefix of the words' popcounts, one 32-bit entry per
+// word, so a cell's index is rank[word] + popcount(bits below it) — two loads, no search, no hash table.
+//
+// Everything that decides an output is integer arithmetic (32-bit atomic adds of colours and counts: order-free), so
+// recolouring is defined bit for bit; the colour mse sums float64 terms in a fixed order (per thread, then a tree per
+// workgroup, then the workgroups in index order).
+#include <algorithm>
+#include "common.h"
+
+namespace pcgc {
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- bit set + rank
+// The bit set is padded to a whole number of scan blocks (kScanWords words each) and zeroed, so the scan reads no bound.
+constexpr int kScanThreads = 256, kWordsPerThread = 16, kScanWords = kScanThreads * kWordsPerThread;
+constexpr int kSumBlocks = 1024;
+constexpr int64_t kMaxSource = 0xFFFFFFFFll / 255;      // 255 * n_s fits the 32-bit sums of the scatter pass
+
+struct Grid {
+  const unsigned* bits;
+  const unsigned* rank;      // rank[w] = number of set bits in words 0 .. w-1
+  const int64_t* n_set;      // number of set bits (a search over an empty set would never end: it is skipped)
+  int res;
+};
+
+__device__ __forceinline__ int64_t cell_of(int res, int x, int y, int z) { return ((int64_t)x * res + y) * res + z; }
+
+__device__ __forceinline__ bool in_grid(int res, int x, int y, int z) {
+  return (unsigned)x < (unsigned)res && (unsigned)y < (unsigned)res && (unsigned)z < (unsigned)res;
+}
+
+__device__ __forceinline__ bool bit_at(const Grid& g, int x, int y, int z) {
+  if (!in_grid(g.res, x, y, z)) return false;
+  const int64_t idx = cell_of(g.res, x, y, z);
+  return (g.bits[idx >> 5] >> (idx & 31)) & 1u;
+}
+
+// index of the occupied cell idx among the set bits in key order
+__device__ __forceinline__ int64_t rank_of(const Grid& g, int64_t idx) {
+  const int64_t w = idx >> 5;
+  return (int64_t)g.rank[w] + __popc(g.bits[w] & ((1u << (idx & 31)) - 1u));
+}
+
+__global__ void bits_from_points_kernel(const int32_t* p, int64_t n, int res, unsigned* bits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+  if (!in_grid(res, x, y, z)) return;
+  const int64_t idx = cell_of(res, x, y, z);
+  atomicOr(&bits[idx >> 5], 1u << (idx & 31));
+}
+
+__global__ void bits_from_keys_kernel(const int64_t* keys, int64_t n, int64_t cells, unsigned* bits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t idx = keys[i];
+  if (idx < 0 || idx >= cells) return;
+  atomicOr(&bits[idx >> 5], 1u << (idx & 31));
+}
+
+__device__ __forceinline__ unsigned load_words(const unsigned* bits, int64_t blk, unsigned w[kWordsPerThread]) {
+  const uint4* src = reinterpret_cast<const uint4*>(bits + blk * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
+  unsigned c = 0;
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread / 4; ++k) {
+    const uint4 u = src[k];
+    w[4 * k] = u.x; w[4 * k + 1] = u.y; w[4 * k + 2] = u.z; w[4 * k + 3] = u.w;
+    c += __popc(u.x) + __popc(u.y) + __popc(u.z) + __popc(u.w);
+  }
+  return c;
+}
+
+// exclusive prefix of v over the workgroup's threads (in thread order) and the workgroup total
+__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* total) {
+  __shared__ unsigned wsum[kScanThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kScanThreads / 64; ++k) {
+    before += k < wave ? wsum[k] : 0u;
+    all += wsum[k];
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kScanThreads) rank_count_kernel(const unsigned* bits, int64_t* block_count) {
+  unsigned w[kWordsPerThread];
+  const unsigned c = load_words(bits, blockIdx.x, w);
+  unsigned total;
+  block_scan(c, &total);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// exclusive prefix of the per-block counts in place, the sum in *n_set: one workgroup, each thread a contiguous run
+__global__ void __launch_bounds__(1024) rank_block_scan_kernel(int64_t* block_count, int64_t nblk, int64_t* n_set) {
+  __shared__ int64_t part[1024];
+  const int64_t per = (nblk + 1023) / 1024;
+  const int64_t b0 = std::min<int64_t>(nblk, (int64_t)threadIdx.x * per), b1 = std::min<int64_t>(nblk, b0 + per);
+  int64_t s = 0;
+  for (int64_t b = b0; b < b1; ++b) s += block_count[b];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t acc = 0;
+    for (int t = 0; t < 1024; ++t) { const int64_t x = part[t]; part[t] = acc; acc += x; }
+    *n_set = acc;
+  }
+  __syncthreads();
+  int64_t acc = part[threadIdx.x];
+  for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
+}
+
+__global__ void __launch_bounds__(kScanThreads) rank_write_kernel(const unsigned* bits, const int64_t* block_offset, unsigned* rank) {
+  unsigned w[kWordsPerThread];
+  const unsigned c = load_words(bits, blockIdx.x, w);
+  unsigned total;
+  unsigned o = (unsigned)block_offset[blockIdx.x] + block_scan(c, &total);
+  uint4* dst = reinterpret_cast<uint4*>(rank + (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread / 4; ++k) {
+    uint4 r;
+    r.x = o; o += __popc(w[4 * k]);
+    r.y = o; o += __popc(w[4 * k + 1]);
+    r.z = o; o += __popc(w[4 * k + 2]);
+    r.w = o; o += __popc(w[4 * k + 3]);
+    dst[k] = r;
+  }
+}
+
+// the colours of a cloud in key order, one packed word (r | g << 8 | b << 16) per point
+__global__ void colors_to_rank_order_kernel(const int32_t* p, const uint8_t* colors, int64_t n, Grid g, unsigned* packed) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+  if (!in_grid(g.res, x, y, z)) return;
+  packed[rank_of(g, cell_of(g.res, x, y, z))] = (unsigned)colors[i * 3] | ((unsigned)colors[i * 3 + 1] << 8) | ((unsigned)colors[i * 3 + 2] << 16);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- search
+constexpr unsigned kNone = 0xFFFFFFFFu;
+
+// squared distance from (x, y, z) to the nearest occupied cell (the shell search of tail.hip's D1 / D2 kernels): after
+// shell w every unvisited cell is farther than w, so the search stops as soon as best <= (w+1)^2
+__device__ __forceinline__ unsigned nearest_d2(const Grid& g, int x, int y, int z) {
+  if (*g.n_set == 0) return kNone;
+  unsigned best = kNone;
+  for (int w = 0; w < 2 * g.res; ++w) {
+    for (int dx = -w; dx <= w; ++dx)
+      for (int dy = -w; dy <= w; ++dy) {
+        const bool edge = (dx == -w || dx == w || dy == -w || dy == w);
+        const unsigned dxy = (unsigned)(dx * dx + dy * dy);
+        if (dxy >= best) continue;
+        if (edge) {
+          for (int dz = -w; dz <= w; ++dz)
+            if (bit_at(g, x + dx, y + dy, z + dz)) best = min(best, dxy + (unsigned)(dz * dz));
+        } else {
+          if (bit_at(g, x + dx, y + dy, z - w)) best = min(best, dxy + (unsigned)(w * w));
+          if (bit_at(g, x + dx, y + dy, z + w)) best = min(best, dxy + (unsigned)(w * w));
+        }
+      }
+    if (best <= (unsigned)((w + 1) * (w + 1))) break;
+  }
+  return best;
+}
+
+// calls f(j) with the key-order index j of every occupied cell at squared distance `best` from (x, y, z): ties are kept
+template <typename F>
+__device__ __forceinline__ void for_each_nearest(const Grid& g, int x, int y, int z, unsigned best, F f) {
+  if (best == kNone) return;
+  const int r = (int)sqrtf((float)best) + 1;
+  for (int dx = -r; dx <= r; ++dx)
+    for (int dy = -r; dy <= r; ++dy) {
+      const int rest = (int)best - dx * dx - dy * dy;
+      if (rest < 0) continue;
+      int dz = (int)sqrtf((float)rest);
+      while (dz * dz > rest) --dz;
+      while ((dz + 1) * (dz + 1) <= rest) ++dz;
+      if (dz * dz != rest) continue;
+      for (int sgn = 0; sgn < (dz ? 2 : 1); ++sgn) {
+        const int qz = sgn ? z - dz : z + dz;
+        if (bit_at(g, x + dx, y + dy, qz)) f(rank_of(g, cell_of(g.res, x + dx, y + dy, qz)));
+      }
+    }
+}
+
+// mean rounded half up, in integers
+__device__ __forceinline__ int rounded_mean(unsigned sum, unsigned n) { return (int)((2ull * sum + n) / (2ull * n)); }
+
+// ---------------------------------------------------------------------------------------------------------------- recolouring
+// S -> T: every source point adds its colour and a one to each of its nearest target points.  acc[j] = (sum r, sum g,
+// sum b, |B(t_j)|) as four adjacent uint32, so the four adds of a pair touch one 16-byte slot.  A sum is at most 255 n_s:
+// pcgc_recolor refuses more source points than 2^32 / 255.
+__global__ void __launch_bounds__(256) recolor_scatter_kernel(const int32_t* ps, const uint8_t* cs, int64_t ns, Grid t, unsigned* acc) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ns; i += (int64_t)gridDim.x * 256) {
+    const int x = ps[i * 3], y = ps[i * 3 + 1], z = ps[i * 3 + 2];
+    const unsigned r = cs[i * 3], gch = cs[i * 3 + 1], b = cs[i * 3 + 2];
+    for_each_nearest(t, x, y, z, nearest_d2(t, x, y, z), [&](int64_t j) {
+      atomicAdd(&acc[j * 4], r);
+      atomicAdd(&acc[j * 4 + 1], gch);
+      atomicAdd(&acc[j * 4 + 2], b);
+      atomicAdd(&acc[j * 4 + 3], 1u);
+    });
+  }
+}
+
+// one thread per target point: the rounded mean of what the scatter left, or of the target's own nearest source points
+__global__ void __launch_bounds__(256) recolor_final_kernel(const int64_t* tkeys, int64_t nt, const uint4* acc, Grid s,
+                                                            const unsigned* scolors, uint8_t* out, int32_t* counts) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nt) return;
+  const uint4 a = acc[j];
+  unsigned sr = a.x, sg = a.y, sb = a.z, n = a.w;
+  if (counts) counts[j] = (int32_t)n;
+  if (n == 0) {
+    const int64_t key = tkeys[j], rr = (int64_t)s.res * s.res;
+    const int x = (int)(key / rr), y = (int)((key / s.res) % s.res), z = (int)(key % s.res);
+    for_each_nearest(s, x, y, z, nearest_d2(s, x, y, z), [&](int64_t i) {
+      const unsigned c = scolors[i];
+      sr += c & 255u; sg += (c >> 8) & 255u; sb += (c >> 16) & 255u;
+      ++n;
+    });
+  }
+  out[j * 3] = n ? (uint8_t)rounded_mean(sr, n) : 0;
+  out[j * 3 + 1] = n ? (uint8_t)rounded_mean(sg, n) : 0;
+  out[j * 3 + 2] = n ? (uint8_t)rounded_mean(sb, n) : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- colour mse
+// BT.709 of rgb / 255, written term by term in the order of the numpy statement (the file is built with -ffp-contract=off)
+__device__ __forceinline__ void yuv_bt709(int r8, int g8, int b8, double yuv[3]) {
+  const double r = (double)r8 / 255.0, g = (double)g8 / 255.0, b = (double)b8 / 255.0;
+  yuv[0] = 0.2126 * r + 0.7152 * g + 0.0722 * b;
+  yuv[1] = -0.1146 * r - 0.3854 * g + 0.5 * b + 0.5;
+  yuv[2] = 0.5 * r - 0.4542 * g - 0.0458 * b + 0.5;
+}
+
+__global__ void __launch_bounds__(256) color_mse_partial_kernel(const int32_t* pa, const uint8_t* ca, int64_t na, Grid b,
+                                                                const unsigned* bcolors, double* partial) {
+  __shared__ double sh[3][256];
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < na; i += (int64_t)gridDim.x * 256) {
+    const int x = pa[i * 3], y = pa[i * 3 + 1], z = pa[i * 3 + 2];
+    unsigned sr = 0, sg = 0, sb = 0, n = 0;
+    for_each_nearest(b, x, y, z, nearest_d2(b, x, y, z), [&](int64_t j) {
+      const unsigned c = bcolors[j];
+      sr += c & 255u; sg += (c >> 8) & 255u; sb += (c >> 16) & 255u;
+      ++n;
+    });
+    if (n == 0) continue;
+    double ya[3], yb[3];
+    yuv_bt709(ca[i * 3], ca[i * 3 + 1], ca[i * 3 + 2], ya);
+    yuv_bt709(rounded_mean(sr, n), rounded_mean(sg, n), rounded_mean(sb, n), yb);
+    for (int c = 0; c < 3; ++c) acc[c] += (ya[c] - yb[c]) * (ya[c] - yb[c]);
+  }
+  for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] = acc[c];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o)
+      for (int c = 0; c < 3; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) partial[blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ void color_mse_final_kernel(const double* partial, int nb, int64_t na, double* out3) {
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int i = 0; i < nb; ++i) s += partial[i * 3 + threadIdx.x];
+    out3[threadIdx.x] = s / (double)na;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+int64_t scan_blocks(int res) {
+  const int64_t cells = (int64_t)res * res * res;
+  return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32);
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct RankBuffers {
+  unsigned* bits;
+  unsigned* rank;
+  int64_t* block_count;
+  int64_t* n_set;
+  char* rest;                // what follows the rank structure in the workspace
+};
+
+size_t rank_bytes(int res) {
+  const int64_t nblk = scan_blocks(res);
+  return 2 * align256((size_t)nblk * kScanWords * sizeof(unsigned)) + align256((size_t)nblk * sizeof(int64_t)) + 256;
+}
+
+RankBuffers rank_layout(int res, void* workspace) {
+  const int64_t nblk = scan_blocks(res);
+  RankBuffers r;
+  char* w = static_cast<char*>(workspace);
+  r.bits = reinterpret_cast<unsigned*>(w);
+  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  r.rank = reinterpret_cast<unsigned*>(w);
+  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  r.block_count = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)nblk * sizeof(int64_t));
+  r.n_set = reinterpret_cast<int64_t*>(w);
+  r.rest = w + 256;
+  return r;
+}
+
+// bit set of a cloud given as points (keys == NULL) or as linear keys, and its rank structure
+int build_rank(const RankBuffers& r, int res, const int32_t* points, const int64_t* keys, int64_t n, hipStream_t s) {
+  const int64_t nblk = scan_blocks(res);
+  PCGC_CHECK_HIP(hipMemsetAsync(r.bits, 0, (size_t)nblk * kScanWords * sizeof(unsigned), s));
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (keys)
+    hipLaunchKernelGGL(bits_from_keys_kernel, dim3(grid), dim3(256), 0, s, keys, n, (int64_t)res * res * res, r.bits);
+  else
+    hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, r.bits);
+  hipLaunchKernelGGL(rank_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count);
+  hipLaunchKernelGGL(rank_block_scan_kernel, dim3(1), dim3(1024), 0, s, r.block_count, nblk, r.n_set);
+  hipLaunchKernelGGL(rank_write_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count, r.rank);
+  return 0;
+}
+
+bool sizes_ok(int res, int64_t a, int64_t b) {
+  return res > 0 && res <= 4096 && a > 0 && b > 0 && a <= 0x7FFFFFFF && b <= 0x7FFFFFFF;
+}
+
+}  // namespace
+}  // namespace pcgc
+
+using namespace pcgc;
+
+extern "C" {
+
+size_t pcgc_recolor_workspace_bytes(int res, int64_t n_s, int64_t n_t) {
+  if (!sizes_ok(res, n_s, n_t) || n_s > kMaxSource) return 0;
+  return rank_bytes(res) + align256((size_t)n_t * 4 * sizeof(unsigned)) + align256((size_t)n_s * sizeof(unsigned));
+}
+
+int pcgc_recolor(const int32_t* source_points, const uint8_t* source_colors, int64_t n_s, const int64_t* target_keys, int64_t n_t,
+                 int res, uint8_t* target_colors, int32_t* backward_counts, void* workspace, size_t workspace_bytes,
+                 pcgc_stream_t stream) {
+  PCGC_REQUIRE(source_points && source_colors && target_keys && target_colors && workspace && sizes_ok(res, n_s, n_t),
+               "pcgc_recolor: bad arguments");
+  PCGC_REQUIRE(n_s <= kMaxSource, "pcgc_recolor: %lld source points, the 32-bit colour sums hold %lld", (long long)n_s, (long long)kMaxSource);
+  PCGC_REQUIRE(workspace_bytes >= pcgc_recolor_workspace_bytes(res, n_s, n_t), "pcgc_recolor: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const RankBuffers r = rank_layout(res, workspace);
+  unsigned* acc = reinterpret_cast<unsigned*>(r.rest);
+  unsigned* scolors = reinterpret_cast<unsigned*>(r.rest + align256((size_t)n_t * 4 * sizeof(unsigned)));
+  const Grid g{r.bits, r.rank, r.n_set, res};
+  // the target's rank structure, then S -> T
+  int rc = build_rank(r, res, nullptr, target_keys, n_t, s);
+  if (rc) return rc;
+  PCGC_CHECK_HIP(hipMemsetAsync(acc, 0, (size_t)n_t * 4 * sizeof(unsigned), s));
+  const int blocks = (int)std::min<int64_t>((n_s + 255) / 256, 4096);
+  hipLaunchKernelGGL(recolor_scatter_kernel, dim3(blocks), dim3(256), 0, s, source_points, source_colors, n_s, g, acc);
+  // the same memory becomes the source's rank structure for the targets that nothing reached
+  rc = build_rank(r, res, source_points, nullptr, n_s, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(colors_to_rank_order_kernel, dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, s, source_points, source_colors,
+                     n_s, g, scolors);
+  hipLaunchKernelGGL(recolor_final_kernel, dim3((unsigned)((n_t + 255) / 256)), dim3(256), 0, s, target_keys, n_t,
+                     reinterpret_cast<const uint4*>(acc), g, scolors, target_colors, backward_counts);
+  return launch_ok("recolor kernels");
+}
+
+size_t pcgc_color_mse_workspace_bytes(int res, int64_t n_b) {
+  if (!sizes_ok(res, 1, n_b)) return 0;
+  return rank_bytes(res) + align256((size_t)n_b * sizeof(unsigned)) + align256(3 * kSumBlocks * sizeof(double));
+}
+
+int pcgc_color_mse(const int32_t* points_a, const uint8_t* colors_a, int64_t n_a, const int32_t* points_b, const uint8_t* colors_b,
+                   int64_t n_b, int res, double* out3, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(points_a && colors_a && points_b && colors_b && out3 && workspace && sizes_ok(res, n_a, n_b),
+               "pcgc_color_mse: bad arguments");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_color_mse_workspace_bytes(res, n_b), "pcgc_color_mse: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const RankBuffers r = rank_layout(res, workspace);
+  unsigned* bcolors = reinterpret_cast<unsigned*>(r.rest);
+  double* partial = reinterpret_cast<double*>(r.rest + align256((size_t)n_b * sizeof(unsigned)));
+  const Grid g{r.bits, r.rank, r.n_set, res};
+  int rc = build_rank(r, res, points_b, nullptr, n_b, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(colors_to_rank_order_kernel, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, s, points_b, colors_b, n_b, g,
+                     bcolors);
+  const int blocks = (int)std::min<int64_t>((n_a + 255) / 256, kSumBlocks);
+  hipLaunchKernelGGL(color_mse_partial_kernel, dim3(blocks), dim3(256), 0, s, points_a, colors_a, n_a, g, bcolors, partial);
+  hipLaunchKernelGGL(color_mse_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, n_a, out3);
+  return launch_ok("colour mse kernels");
+}
+
+}  // extern "C"

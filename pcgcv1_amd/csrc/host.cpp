@@ -759,6 +759,130 @@ int pcgc_format_points_int(const int64_t* pts, int64_t n, char* out, int64_t cap
   return 0;
 }
 
+// "x y z r g b\n" per point: the same two passes as pcgc_format_points_int
+int pcgc_format_points_colors_int(const int64_t* pts, const uint8_t* colors, int64_t n, char* out, int64_t cap, int64_t* out_len) {
+  if ((n > 0 && (!pts || !colors)) || !out_len) { set_error("pcgc_format_points_colors_int: NULL argument"); return -1; }
+  const int n_blocks = int(std::max<int64_t>(1, std::min<int64_t>(32, n / 16384)));
+  auto ndigits = [](uint64_t u) { int d = 1; while (u >= 10) { u /= 10; ++d; } return d; };
+  std::vector<int64_t> len(size_t(n_blocks), 0);
+  parallel_for(n_blocks, n_blocks, [&](int t) {
+    int64_t l = 0;
+    for (int64_t i = 3 * (n * t / n_blocks); i < 3 * (n * (t + 1) / n_blocks); ++i) {
+      const int64_t v = pts[i];
+      l += ndigits(v < 0 ? 0 - (uint64_t)v : (uint64_t)v) + (v < 0 ? 2 : 1) + ndigits(colors[i]) + 1;
+    }
+    len[size_t(t)] = l;
+  });
+  std::vector<int64_t> off(size_t(n_blocks) + 1, 0);
+  for (int t = 0; t < n_blocks; ++t) off[size_t(t) + 1] = off[size_t(t)] + len[size_t(t)];
+  const int64_t total = off[size_t(n_blocks)];
+  *out_len = total;
+  if (!out || cap < total) {
+    set_error("pcgc_format_points_colors_int: buffer of %lld bytes for %lld points (need %lld)", (long long)cap, (long long)n, (long long)total);
+    return -2;
+  }
+  parallel_for(n_blocks, n_blocks, [&](int t) {
+    char* p = out + off[size_t(t)];
+    char tmp[24];
+    auto put = [&](uint64_t u, char sep) {
+      int k = 0;
+      do { tmp[k++] = char('0' + u % 10); u /= 10; } while (u);
+      while (k) *p++ = tmp[--k];
+      *p++ = sep;
+    };
+    for (int64_t i = n * t / n_blocks; i < n * (t + 1) / n_blocks; ++i) {
+      for (int c = 0; c < 3; ++c) {
+        const int64_t v = pts[i * 3 + c];
+        if (v < 0) *p++ = '-';
+        put(v < 0 ? 0 - (uint64_t)v : (uint64_t)v, ' ');
+      }
+      for (int c = 0; c < 3; ++c) put(colors[i * 3 + c], c == 2 ? '\n' : ' ');
+    }
+  });
+  return 0;
+}
+
+// ---------------------------------------------------------------- ply text (named columns)
+int pcgc_parse_ply_columns(const char* text, int64_t len, const int32_t* columns, int k, int64_t max_rows, double* out, int64_t cap,
+                           int64_t* n_rows, int n_threads) {
+  if ((len > 0 && !text) || !columns || !n_rows || (cap > 0 && !out) || k < 1 || k > 16) {
+    set_error("pcgc_parse_ply_columns: bad arguments");
+    return -1;
+  }
+  int last = 0;
+  for (int j = 0; j < k; ++j) {
+    if (columns[j] < 0 || columns[j] > 255) { set_error("pcgc_parse_ply_columns: column %d outside [0, 255]", int(columns[j])); return -1; }
+    last = std::max(last, int(columns[j]));
+  }
+  n_threads = std::max(1, std::min(n_threads, 64));
+  std::vector<int64_t> cut(size_t(n_threads) + 1, len);      // chunk boundaries at line starts
+  cut[0] = 0;
+  for (int t = 1; t < n_threads; ++t) {
+    int64_t p = len * t / n_threads;
+    if (p < cut[t - 1]) p = cut[t - 1];
+    while (p < len && text[p] != '\n') ++p;
+    cut[t] = p < len ? p + 1 : len;
+  }
+  auto blank = [](char c) { return c == ' ' || (c >= 9 && c <= 13); };
+  std::vector<std::vector<double>> part(static_cast<size_t>(n_threads));
+  std::vector<int64_t> bad_at(size_t(n_threads), -1);         // text offset of the thread's first row that does not parse
+  parallel_for(n_threads, n_threads, [&](int t) {
+    std::vector<double>& v = part[size_t(t)];
+    v.reserve(size_t((cut[t + 1] - cut[t]) / 12) * size_t(k) / 2);
+    const char* p = text + cut[t];
+    const char* end = text + cut[t + 1];
+    std::vector<double> tok(size_t(last) + 1);
+    while (p < end) {
+      const char* nl = static_cast<const char*>(std::memchr(p, '\n', size_t(end - p)));
+      const char* le = nl ? nl : end;
+      const char* q = p;
+      int nt = 0;
+      bool ok = true;
+      while (ok && nt <= last) {
+        while (q < le && blank(*q)) ++q;
+        if (q >= le) break;
+        const char* b = q;
+        while (q < le && !blank(*q)) ++q;
+        ok = parse_float_token(b, q, &tok[size_t(nt)]);
+        ++nt;
+      }
+      if (nt > 0 || !ok) {                                   // a blank line is no row
+        if (!ok || nt <= last) { bad_at[size_t(t)] = p - text; return; }
+        for (int j = 0; j < k; ++j) v.push_back(tok[size_t(columns[j])]);
+      }
+      p = nl ? nl + 1 : end;
+    }
+  });
+  int64_t total = 0;
+  std::vector<int64_t> off(size_t(n_threads) + 1, 0);
+  for (int t = 0; t < n_threads; ++t) {
+    const int64_t rows = int64_t(part[size_t(t)].size()) / k;
+    if (bad_at[size_t(t)] >= 0 && (max_rows < 0 || total + rows < max_rows)) {   // the bad row is one the caller asked for
+      int64_t line = 1;
+      for (int64_t i = 0; i < bad_at[size_t(t)]; ++i) line += text[i] == '\n';
+      set_error("pcgc_parse_ply_columns: line %lld of the body does not hold %d numbers", (long long)line, last + 1);
+      return -3;
+    }
+    total += rows;
+    off[size_t(t) + 1] = total;
+    if (bad_at[size_t(t)] >= 0) {                            // everything behind it lies beyond max_rows
+      for (int u = t + 1; u < n_threads; ++u) off[size_t(u) + 1] = total;
+      break;
+    }
+  }
+  if (max_rows >= 0) {
+    total = std::min(total, max_rows);
+    for (auto& o : off) o = std::min(o, max_rows);
+  }
+  *n_rows = total;
+  if (total > cap) { set_error("pcgc_parse_ply_columns: %lld rows, buffer holds %lld", (long long)total, (long long)cap); return -2; }
+  parallel_for(n_threads, n_threads, [&](int t) {             // every thread's rows to their final place (file order)
+    const int64_t rows = off[size_t(t) + 1] - off[size_t(t)];
+    if (rows > 0) std::memcpy(out + off[size_t(t)] * k, part[size_t(t)].data(), size_t(rows) * size_t(k) * sizeof(double));
+  });
+  return 0;
+}
+
 // ---------------------------------------------------------------- mesh text (OFF / OBJ)
 struct MeshText {
   const char* p;

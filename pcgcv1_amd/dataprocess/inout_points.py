@@ -3,7 +3,7 @@ dataprocess/inout_points.py, vectorised / on the device instead of per-point Pyt
 
   load_ply_data 8-28, write_ply_data 30-46, load_points 50-90 (partition), save_points 92-112
   (merge), points2voxels 116-132, voxels2points 134-143, select_voxels 147-168,
-  get_adaptive_thres 170-179.
+  get_adaptive_thres 170-179.  load_ply_colors / write_ply_colors are the coloured forms of the first two.
 
 Bit-exact against the reference on the golden vectors (tests/golden/partition.npz, select.npz).
 Partition runs in libpcgc_host.so (`pcgc_partition`), voxelisation and the adaptive top-k
@@ -66,10 +66,11 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def _load_binary_ply(filename):
+def _load_binary_ply(filename, with_colors=False):
     """binary_little_endian / binary_big_endian ply (what MeshLab, Open3D and CloudCompare write by default) ->
     (points int32 [N,3] truncated like the ASCII path, normals float32 [N,3] or None).  Vertex properties must be scalars
-    (x, y, z and anything else: colours, normals); elements after the vertices are ignored, elements before them refused."""
+    (x, y, z and anything else: colours, normals); elements after the vertices are ignored, elements before them refused.
+    with_colors=True appends a third value: colors uint8 [N,3] or None (load_ply_colors)."""
     with open(filename, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -100,7 +101,92 @@ def _load_binary_ply(filename):
     nrm = None
     if all(k in v.dtype.names for k in ("nx", "ny", "nz")):
         nrm = np.stack([v["nx"], v["ny"], v["nz"]], -1).astype(np.float32)
-    return pts, nrm
+    if not with_colors:
+        return pts, nrm
+    names = _color_names(v.dtype.names)
+    return pts, nrm, (_as_uint8_colors(np.stack([v[k] for k in names], -1), filename) if names else None)
+
+
+_COLOR_NAMES = (("red", "green", "blue"), ("r", "g", "b"), ("diffuse_red", "diffuse_green", "diffuse_blue"))
+
+
+def _color_names(props):
+    """the three colour properties a ply declares (red green blue, r g b or diffuse_red ...), or None"""
+    for names in _COLOR_NAMES:
+        if all(k in props for k in names):
+            return names
+    return None
+
+
+def _as_uint8_colors(c, filename):
+    """uchar colours as they are; float colours are taken as 0..255 values and must be whole numbers in that range"""
+    c = np.asarray(c)
+    if c.dtype == np.uint8:
+        return np.ascontiguousarray(c)
+    c64 = c.astype(np.float64)
+    if c64.size and (c64.min() < 0 or c64.max() > 255 or (c64 != np.rint(c64)).any()):
+        raise ValueError("%s: colour values must be integers within 0..255" % filename)
+    return np.ascontiguousarray(c64.astype(np.uint8))
+
+
+def load_ply_colors(filename, as_float=False):
+    """ply with optional per-vertex colours -> (points int32 [N,3], colors uint8 [N,3] or None).  The colour columns are
+    the properties named red green blue (also r g b, diffuse_red ...), wherever the header puts them among x y z,
+    normals and alpha; a file that declares none gives None.  ASCII bodies are parsed by libpcgc_host.so
+    (pcgc_parse_ply_columns) on a few threads; binary files go through _load_binary_ply.  as_float=True keeps the
+    positions of an ASCII file as float64 instead of truncating them (a scale != 1 reconstruction holds fractions)."""
+    import mmap
+    with open(filename, "rb") as f:
+        if _ply_is_binary(f, filename):
+            pts, _, colors = _load_binary_ply(filename, with_colors=True)
+            return pts, colors
+        f.seek(0)
+        head = f.read(4096)
+        while head.startswith(b"ply") and b"end_header" not in head:
+            more = f.read(65536)
+            if not more:
+                break
+            head += more
+        end = head.find(b"end_header")
+        if end < 0:
+            return load_ply_data(filename), None             # no header: nothing names a colour column
+        nl = head.find(b"\n", end)
+        start = nl + 1 if nl >= 0 else len(head)
+        props, n_vertex, element = [], -1, None
+        for ln in head[:end].decode("ascii", "replace").splitlines():
+            t = ln.split()
+            if len(t) >= 3 and t[0] == "element":
+                element = t[1]
+                if element == "vertex":
+                    n_vertex = int(t[2])
+            elif len(t) >= 3 and t[0] == "property" and element == "vertex":
+                props.append(t[-1])
+        if not all(k in props for k in "xyz"):
+            raise ValueError("%s: ply header declares no x, y, z vertex properties" % filename)
+        names = _color_names(props)
+        cols = np.array([props.index(k) for k in ("x", "y", "z") + (names or ())], np.int32)
+        size = os.fstat(f.fileno()).st_size
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size > start else None
+    if mm is None:
+        return np.zeros((0, 3), np.int32), (np.zeros((0, 3), np.uint8) if names else None)
+    try:
+        buf = np.frombuffer(mm, np.uint8)[start:]
+        cap = n_vertex if n_vertex >= 0 else buf.size // (2 * len(props)) + 1      # a row is at least "0 " per property
+        out = np.empty((cap, len(cols)), np.float64)
+        n = np.zeros(1, np.int64)
+        _lib.check_host(_lib.host().pcgc_parse_ply_columns(_lib.nptr(buf), buf.size, _lib.nptr(cols), len(cols), n_vertex, _lib.nptr(out),
+                                                           cap, _lib.nptr(n), min(64, _lib.host_threads())), "pcgc_parse_ply_columns")
+        del buf
+    finally:
+        try:
+            mm.close()
+        except BufferError:
+            pass
+    out = out[:int(n[0])]
+    if n_vertex >= 0 and len(out) != n_vertex:
+        raise ValueError("%s: header declares %d vertices, the body holds %d" % (filename, n_vertex, len(out)))
+    pts = np.ascontiguousarray(out[:, :3]) if as_float else out[:, :3].astype(np.int32)
+    return pts, (_as_uint8_colors(out[:, 3:], filename) if names else None)
 
 
 def load_ply_normals(filename):
@@ -193,6 +279,41 @@ def write_ply_data(filename, points):
         f.write(head)
         f.write(body)
 
+
+
+def write_ply_colors(filename, points, colors):
+    """Coloured ASCII ply as the MPEG tools (pc_error, tmc3) write and read it: `property uchar red/green/blue` after
+    x y z, one `x y z r g b` line per point.  Positions are formatted as write_ply_data formats them (str(int) for integer
+    arrays, through pcgc_format_points_colors_int; str(float) otherwise)."""
+    points = np.asarray(points)
+    points = points.reshape(-1, points.shape[-1])[:, :3] if points.size else points.reshape(0, 3)
+    colors = np.asarray(colors)
+    if colors.shape != (points.shape[0], 3):
+        raise ValueError("write_ply_colors: %d points, colours of shape %s" % (points.shape[0], colors.shape))
+    if colors.dtype != np.uint8:
+        colors = _as_uint8_colors(colors, "write_ply_colors")
+    colors = np.ascontiguousarray(colors)
+    head = ("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % points.shape[0]).encode()
+    with open(filename, "wb") as f:
+        f.write(head)
+        if points.shape[0] == 0:
+            return
+        if np.issubdtype(points.dtype, np.integer):
+            pts = np.ascontiguousarray(points, np.int64)
+            n = np.zeros(1, np.int64)
+            host = _lib.host()
+            rc = host.pcgc_format_points_colors_int(_lib.nptr(pts), _lib.nptr(colors), pts.shape[0], None, 0, _lib.nptr(n))
+            buf = np.empty(int(n[0]), np.uint8)               # the first call only sizes the text (-2)
+            rc = host.pcgc_format_points_colors_int(_lib.nptr(pts), _lib.nptr(colors), pts.shape[0], _lib.nptr(buf), buf.size, _lib.nptr(n))
+            _lib.check_host(rc, "pcgc_format_points_colors_int")
+            f.write(memoryview(buf)[:int(n[0])])
+            return
+        s = np.array([[str(v) for v in row] for row in points]) if points.shape[0] < 64 else _float_str(points)
+        line = s[:, 0]
+        for c in [s[:, 1], s[:, 2]] + [_str_table(colors[:, k].astype(np.int64)) for k in range(3)]:
+            line = np.char.add(np.char.add(line, " "), c)
+        f.write(("\n".join(line.tolist()) + "\n").encode())
 
 
 def write_ply_normals(filename, points, normals):

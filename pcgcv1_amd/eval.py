@@ -20,6 +20,7 @@ from . import metrics
 from .dataprocess import inout_bitstream as bs
 from .dataprocess import inout_points as iop
 from .process import postprocess_points, preprocess_points
+from .recolor import recolored_metrics
 from .transform import compress_factorized, compress_hyper, compress_hyper_ahead, decompress_factorized, decompress_hyper
 
 
@@ -223,14 +224,17 @@ def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None,
 
 
 def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname="pcgcv1_amd.models.model_voxception",
-         fixed_thres=None, postfix="", estimate_normals=False, pointnums="count"):
+         fixed_thres=None, postfix="", estimate_normals=False, pointnums="count", color=False):
     """eval.py:160-215.  The config .ini has DEFAULT {cube_size, min_num} and one section per rate with
     {scale, ckpt_dir, rho_d1, rho_d2} (eval.py:170-183).  Returns the list of result rows (dicts).
     estimate_normals=True: an input ply without normals gets them from metrics.estimate_normals(points, 10, 20) (the
     radius / max_nn with which mesh2pc_open3d.py:75-78 wrote the reference's test sets), so D2 and the rho_d2 search run
     as for a ply that carries normals.  A ply with normals keeps its own either way.
     pointnums="d1": every rate point writes the encoder's D1-optimised counts (pointnums.py) instead of the true ones; the
-    rest of the row (rho search, the three reconstructions) is computed the same way on that container."""
+    rest of the row (rho search, the three reconstructions) is computed the same way on that container.
+    color=True (the input ply must carry colours): the rho = 1 and rho_d1 reconstructions are recoloured from the original
+    (recolor.py) and the row gains pc_error's c[i],PSNRF for rho = 1 and "optimal D1 c[0],PSNRF"; the rho search itself
+    stays on D1 / D2."""
     if mode not in ("hyper", "factorized"):
         raise ValueError("eval: mode must be 'hyper' or 'factorized' (got %r)" % (mode,))
     hyper = mode == "hyper"
@@ -238,6 +242,11 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
     points, normals = iop.load_ply_normals(input_file)
     if normals is None and estimate_normals:
         normals = metrics.estimate_normals(points, radius=10, max_nn=20)
+    colors = None
+    if color:
+        colors = iop.load_ply_colors(input_file)[1]
+        if colors is None:
+            raise ValueError("%s has no colour properties (red green blue): --color needs a coloured input" % input_file)
     filename = os.path.split(input_file)[-1][:-4]
     os.makedirs(rootdir, exist_ok=True)
     config = configparser.ConfigParser()
@@ -270,8 +279,11 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
             cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num,
                                                                           mode="factorized", pointnums=pointnums)
 
+        def reconstruct(rho):
+            return postprocess_points(cubes_d, points_numbers, cube_positions, scale, cube_size, rho, fixed_thres)
+
         def measure(rho):
-            rec = postprocess_points(cubes_d, points_numbers, cube_positions, scale, cube_size, rho, fixed_thres)
+            rec = reconstruct(rho)
             if metrics._off_grid(rec):                        # scale != 1: pc_error measures the float coordinates (process.py:76-77)
                 return metrics.pc_error(points, rec, normals, res - 1)
             rec = np.unique(np.rint(rec).astype(np.int32), axis=0)          # pc_error drops duplicate points (dropDuplicates 2)
@@ -293,6 +305,11 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
                     "bpp_strings_head": bpps[3], "bpp_pointsnums": bpps[4], "bpp_cubepos": bpps[5], "rho_d1": rho_d1,
                     "optimal D1 PSNR": r1["mseF,PSNR (p2point)"], "rho_d2": rho_d2,
                     "optimal D2 PSNR": r2.get("mseF,PSNR (p2plane)", float("nan")), "rate": rate})
+        if colors is not None:
+            c1 = recolored_metrics(points, colors, reconstruct(1.0))
+            cd1 = c1 if rho_d1 == 1.0 else recolored_metrics(points, colors, reconstruct(rho_d1))
+            row.update({"c[0],PSNRF": c1["c[0],PSNRF"], "c[1],PSNRF": c1["c[1],PSNRF"], "c[2],PSNRF": c1["c[2],PSNRF"],
+                        "optimal D1 c[0],PSNRF": cd1["c[0],PSNRF"]})
         rows.append(row)
         with open(os.path.join(rootdir, filename + postfix + ".csv"), "w", newline="") as f:
             wr = csv.DictWriter(f, fieldnames=list(rows[0]))
@@ -317,10 +334,12 @@ def main(argv=None):
                     help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
     ap.add_argument("--pointnums", choices=("count", "d1"), default="count",
                     help="what the container's .pointnums holds: the true counts, or the encoder's D1-optimised ones")
+    ap.add_argument("--color", action="store_true",
+                    help="recolour the rho = 1 and rho_d1 reconstructions from the (coloured) input and add pc_error's c[i],PSNRF")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
         for r in eval(input_file, a.rootdir, a.cfgdir, a.res, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix,
-                      a.estimate_normals, a.pointnums):
+                      a.estimate_normals, a.pointnums, a.color):
             print(r)
 
 

@@ -11,13 +11,13 @@ from . import eval as rd
 
 
 def eval(input_file, rootdir, resolution, mode, cube_size, modelname, fixed_thres, postfix, ckpt_root=None, estimate_normals=False,
-         pointnums="count"):
+         pointnums="count", color=False):
     csv_rootdir = os.path.join(rootdir, "csv")
     cfg_rootdir = os.path.join(rootdir, "cfg")
     os.makedirs(csv_rootdir, exist_ok=True)
     _, config_file = rd.set_default_config(input_file, cfg_rootdir, resolution, mode, cube_size, ckpt_root=ckpt_root, modelname=modelname)
     return rd.eval(input_file, csv_rootdir, config_file, resolution, mode=mode, cube_size=cube_size, modelname=modelname,
-                   fixed_thres=fixed_thres, postfix=postfix, estimate_normals=estimate_normals, pointnums=pointnums)
+                   fixed_thres=fixed_thres, postfix=postfix, estimate_normals=estimate_normals, pointnums=pointnums, color=color)
 
 
 def main(argv=None):
@@ -37,10 +37,12 @@ def main(argv=None):
                     help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
     ap.add_argument("--pointnums", choices=("count", "d1"), default="count",
                     help="what the container's .pointnums holds: the true counts, or the encoder's D1-optimised ones")
+    ap.add_argument("--color", action="store_true",
+                    help="recolour the rho = 1 and rho_d1 reconstructions from the (coloured) input and add pc_error's c[i],PSNRF")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
         for row in eval(input_file, a.rootdir, a.resolution, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix, a.ckpt_root,
-                        a.estimate_normals, a.pointnums):
+                        a.estimate_normals, a.pointnums, a.color):
             print(row)
 
 

@@ -6,6 +6,7 @@ voxelised clouds: mse1 = mean_{p in A} min_{q in B} |p-q|^2, mse2 the same B->A,
 pc_error_d binary cannot ship, its answers on seeded clouds are pinned in tests/golden/pc_error_d1.npz.
 `d2_metrics` adds the point-to-plane figures ("mseF,PSNR (p2plane)", eval.py's D2) with pc_error's tie handling
 and normal transfer (csrc/tail.hip), pinned in tests/golden/pc_error_d2.npz.
+`color_metrics` is the tool's `--color=1` table (csrc/color.hip), pinned in tests/golden/pc_error_color.npz.
 """
 import numpy as np
 import torch
@@ -83,6 +84,45 @@ def d2_metrics(points_a, normals_a, points_b, resolution):
             "mse1,PSNR (p2plane)": psnr(mse1), "mse2,PSNR (p2plane)": psnr(mse2), "mseF,PSNR (p2plane)": psnr(mse_f),
             "h.       1(p2plane)": h1, "h.       2(p2plane)": h2, "h.        (p2plane)": max(h1, h2)}
 
+
+def _colored_cloud(points, colors, res, what):
+    """device copies of a voxelised coloured cloud, checked for what the kernels assume: coordinates within [0, res), no
+    point twice (pc_error drops duplicates first; which colour it keeps is not part of the stated rule)"""
+    pts = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+    col = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    if len(pts) == 0 or len(pts) != len(col):
+        raise ValueError("%s: %d points, %d colours" % (what, len(pts), len(col)))
+    if int(pts.min()) < 0 or int(pts.max()) >= res:
+        raise ValueError("%s: coordinates outside [0, %d)" % (what, res))
+    dev = _lib.require_gpu()
+    p_d = torch.from_numpy(pts).to(dev)
+    _sorted_keys(p_d, res)                                    # raises on duplicate points
+    return p_d, torch.from_numpy(col).to(dev)
+
+
+def color_metrics(points_a, colors_a, points_b, colors_b):
+    """The colour figures `pc_error --color=1` (0.13.4) prints for two voxelised clouds with uint8 rgb per point, under its
+    own keys: "c[i],    1" = mean over A of (yuv_a[i] - yuv_m[i])^2 with m the rounded-half-up integer mean colour of ALL
+    nearest points of B and yuv = BT.709 of rgb / 255, "c[i],PSNR1" = -10 log10 of it, the 2 forms with A and B swapped,
+    the F forms the larger mse (smaller PSNR) per channel (include/pcgc.h, pcgc_color_mse; pinned against the pc_error
+    binary in tests/golden/pc_error_color.npz).  The tool's h.c[i] lines are not produced."""
+    lib = _lib.hip()
+    res = int(max(int(np.max(points_a)), int(np.max(points_b))) + 1)
+    pa, ca = _colored_cloud(points_a, colors_a, res, "color_metrics: cloud A")
+    pb, cb = _colored_cloud(points_b, colors_b, res, "color_metrics: cloud B")
+    out = torch.empty(6, dtype=torch.float64, device=pa.device)
+    ws = torch.empty(int(lib.pcgc_color_mse_workspace_bytes(res, max(len(pa), len(pb)))), dtype=torch.uint8, device=pa.device)
+    _lib.check(lib.pcgc_color_mse(_lib.dptr(pa), _lib.dptr(ca), len(pa), _lib.dptr(pb), _lib.dptr(cb), len(pb), res, _lib.dptr(out),
+                                  _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_color_mse A->B")
+    _lib.check(lib.pcgc_color_mse(_lib.dptr(pb), _lib.dptr(cb), len(pb), _lib.dptr(pa), _lib.dptr(ca), len(pa), res, _lib.dptr(out[3:]),
+                                  _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_color_mse B->A")
+    m = out.cpu().numpy()
+    res_ = {}
+    for d, mse in (("1", m[:3]), ("2", m[3:]), ("F", np.maximum(m[:3], m[3:]))):
+        for i in range(3):
+            res_["c[%d],    %s" % (i, d)] = float(mse[i])
+            res_["c[%d],PSNR%s" % (i, d)] = float("inf") if mse[i] == 0 else float(-10.0 * np.log10(mse[i]))
+    return res_
 
 
 def estimate_normals(points, radius=10, max_nn=20, return_cov=False):
@@ -178,14 +218,21 @@ def pc_error_off_grid(points_a, points_b, normals_a=None, resolution=1023):
     return out
 
 
-def pc_error(points_a, points_b, normals_a=None, resolution=1023):
+def pc_error(points_a, points_b, normals_a=None, resolution=1023, colors_a=None, colors_b=None):
     """All figures of myutils/pc_error_wrapper.pc_error (26-75) as one dict: D1 always, D2 when normals are given.
-    points_b with fractional coordinates (a rate point with scale != 1): pc_error_off_grid."""
+    points_b with fractional coordinates (a rate point with scale != 1): pc_error_off_grid.
+    colors_a and colors_b (uint8 [N,3], both): the colour keys of `--color=1` as well (color_metrics; voxelised clouds only)."""
+    if (colors_a is None) != (colors_b is None):
+        raise ValueError("pc_error: colours of both clouds are needed for the colour figures")
     if _off_grid(points_b):
+        if colors_a is not None:
+            raise ValueError("pc_error: the colour figures need a cloud on the integer grid")
         return pc_error_off_grid(points_a, points_b, normals_a, resolution)
     out = d1_metrics(points_a, points_b, resolution)
     if normals_a is not None:
         out.update(d2_metrics(points_a, normals_a, points_b, resolution))
+    if colors_a is not None:
+        out.update(color_metrics(points_a, colors_a, points_b, colors_b))
     return out
 
 

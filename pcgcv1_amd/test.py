@@ -27,6 +27,9 @@ _FLAGS = [
                                 "that give the decoder at rho = 1 the smallest cube-local D1 (pcgcv1_amd/pointnums.py)"),
     ("gpu", int, 1, "GPUs to use: 1 = this process; N > 1 = the cube list sharded over N ranks, one per GPU (started here "
                     "unless a launcher already set WORLD_SIZE); 0 is refused: there is no CPU path"),
+    ("colors_from", str, "", "decompress only: the ORIGINAL coloured ply; the written _rec.ply then carries its colours transferred "
+                             "onto the decoded points (pcgcv1_amd/recolor.py).  An encoder-side / evaluation tool: the bitstream "
+                             "holds no colours, a real decoder does not have this file"),
 ]
 
 
@@ -133,6 +136,10 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if (args.gpu > 1 or world > 1) and args.pointnums != "count":
         raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 runs on one GPU)")
+    if (args.gpu > 1 or world > 1) and args.colors_from:
+        raise SystemExit("multi-GPU runs write geometry only (--colors_from runs on one GPU)")
+    if args.colors_from and args.command != "decompress":
+        raise SystemExit("--colors_from belongs to decompress: compress reads geometry only, the bitstream holds no colours")
     if args.gpu > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(argv, args.gpu))
     if args.gpu > 1 and world != args.gpu:                 # e.g. --gpu=8 under `torchrun --nproc-per-node 1`: never silently one GPU
@@ -192,7 +199,7 @@ def main(argv=None):
             # the tail (top-k, points, text, file) follows the decoder slice by slice instead of waiting for the last cube;
             # PCGC_STREAM_TAIL=0 / --scale != 1 / PCGC_STAGE_TIMES=1: postprocess on the whole batch, as the reference does
             tail = None
-            if args.scale == 1 and not stage_times and os.environ.get("PCGC_STREAM_TAIL", "1") != "0":
+            if args.scale == 1 and not stage_times and os.environ.get("PCGC_STREAM_TAIL", "1") != "0" and not args.colors_from:
                 tail = StreamedPostprocess(args.output, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
             cubes = decompress_hyper(y_strings, y_min_vs, y_max_vs, y_shape, z_strings, z_min_v, z_max_v, z_shape, model,
                                      args.ckpt_dir, verbose=stage_times, on_slice=tail)
@@ -202,7 +209,24 @@ def main(argv=None):
                 _report(model, args.ckpt_dir, t0, " + post process")
                 return
             _report(model, args.ckpt_dir, t0)
+        if args.colors_from:
+            return _write_recolored(args, cubes, points_numbers, cube_positions)
         postprocess(args.output, cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
+
+
+def _write_recolored(args, cubes, points_numbers, cube_positions):
+    """--colors_from: the decoded points (the ones postprocess would write, in its order) with the original's colours"""
+    from .dataprocess.inout_points import write_ply_colors
+    from .process import postprocess_points
+    from .recolor import load_source, recolor
+    print('===== Post process =====')
+    t0 = time.time()
+    src_points, src_colors = load_source(args.colors_from)
+    pts = postprocess_points(cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
+    colors, counts = recolor(src_points, src_colors, pts, return_counts=True)
+    write_ply_colors(args.output, pts, colors)
+    print("Recolour from {} and write {}: {}s ({} of {} points coloured from their own nearest source points)".format(
+        args.colors_from, args.output, round(time.time() - t0, 4), int((counts == 0).sum()), len(pts)))
 
 
 if __name__ == "__main__":
