@@ -275,6 +275,52 @@ int pcgc_color_mse(const int32_t* points_a, const uint8_t* colors_a, int64_t n_a
                    const uint8_t* colors_b, int64_t n_b, int res, double* out3, void* workspace, size_t workspace_bytes,
                    pcgc_stream_t stream);
 
+/* ---- RAHT colour transform (pcgcv1_amd/colorcodec.py; tests/_raht_ref.py is the rule in numpy) ----------
+ * The region-adaptive hierarchical transform over the Morton order of M unique voxels with coordinates < 2^depth
+ * (depth <= 12).  key = 3 depth bits, bit triple b from the top = x_b y_b z_b (pcgc_raht_keys; sort them with any sort).
+ * Leaf j is the j-th key in ascending order.  The node that starts at leaf j > 0 is the right sibling of exactly one merge;
+ * pcgc_raht_structure gives per leaf (device arrays, int32 [M]):
+ *   subband[j] = the level l of that merge (the highest bit in which key[j] and key[j-1] differ); subband[0] = 3 depth (DC)
+ *   left[j]    = the leaf at which its left sibling starts (weight w1 = j - left[j]);  w_right[j] = its own weight w2
+ *   order[k]   = the leaves grouped by subband, ascending subband, ascending leaf within one (order[M-1] = 0)
+ * and level_counts (HOST, int64 [3 depth + 1]) = leaves per subband; the call synchronises the stream once to read them.
+ * It fails on keys that are not ascending, unique and below 2^(3 depth).
+ *   pcgc_raht_forward / _inverse run in place on attr float64 [M,3] (leaf order): the merge of leaf j replaces
+ *   (attr[left[j]], attr[j]) = (a1, a2) by (lo, hi) with lo = (sqrt(w1) a1 + sqrt(w2) a2) / sqrt(w1 + w2),
+ *   hi = (sqrt(w1) a2 - sqrt(w2) a1) / sqrt(w1 + w2), levels ascending; the inverse undoes them, levels descending, with
+ *   a1 = (sqrt(w1) lo - sqrt(w2) hi) / sqrt(w), a2 = (sqrt(w2) lo + sqrt(w1) hi) / sqrt(w).  After the forward pass attr[j]
+ *   is the coefficient of subband[j] and attr[0] the DC.  One launch per level with merges; fuse_top != 0: every level
+ *   from the first one above which at most 1024 leaves remain runs in ONE one-workgroup launch through LDS.  *launches
+ *   (may be NULL) = kernel launches made.  Bit-exact float64 (no contraction, correctly rounded sqrt and division).
+ *   pcgc_raht_load_colors: attr[j] = YCoCg-R (Co = R - B, t = B + (Co >> 1), Cg = G - t, Y = t + (Cg >> 1)) of the uint8 rgb of
+ *   point point_of_leaf[j];  pcgc_raht_store_colors: rint, clip (Y [0,255], Co / Cg [-255,255]), inverse YCoCg-R, clip to
+ *   [0,255], written to point point_of_leaf[j].
+ *   pcgc_raht_quantize: q[k][c] = rint(coef[order[k]][c] / step) as int32 [M,3], and level_maxabs (device int32 [37],
+ *   zeroed by the call) = max |q| per subband.  pcgc_raht_symbols: for k < n, symbol = q + amax[subband] where
+ *   |q| <= amax[subband], else the escape symbol 2 amax + 1 (int16 [n,3]; amax device int32 [37], < 16383).
+ *   pcgc_raht_dequantize: coef[order[k]][c] = (symbol - amax) * step for k < n (0 where escaped), then the patches
+ *   patch int32 [n_patch,2] = (k * 3 + c, q) -> q * step (escaped values and the raw positions k >= n; everything else 0).
+ * Workspace: max(37 int32 per 256 leaves + 512, 4 M) bytes, rounded up to 256 — about 4 M bytes; nothing per level. */
+size_t pcgc_raht_workspace_bytes(int64_t m);
+int pcgc_raht_keys(const int32_t* points, int64_t m, int64_t* keys, pcgc_stream_t stream);
+int pcgc_raht_structure(const int64_t* sorted_keys, int64_t m, int depth, int32_t* subband, int32_t* left, int32_t* w_right,
+                        int32_t* order, int64_t* level_counts, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_raht_forward(double* attr, int64_t m, int depth, const int32_t* left, const int32_t* w_right, const int32_t* subband,
+                      const int32_t* order, const int64_t* level_counts, int fuse_top, int* launches, void* workspace,
+                      size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_raht_inverse(double* attr, int64_t m, int depth, const int32_t* left, const int32_t* w_right, const int32_t* subband,
+                      const int32_t* order, const int64_t* level_counts, int fuse_top, int* launches, void* workspace,
+                      size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_raht_load_colors(const uint8_t* rgb, const int64_t* point_of_leaf, int64_t m, double* attr, pcgc_stream_t stream);
+int pcgc_raht_store_colors(const double* attr, const int64_t* point_of_leaf, int64_t m, uint8_t* rgb, pcgc_stream_t stream);
+int pcgc_raht_quantize(const double* coef, const int32_t* order, const int32_t* subband, int64_t m, double step, int32_t* q,
+                       int32_t* level_maxabs, pcgc_stream_t stream);
+int pcgc_raht_symbols(const int32_t* q, const int32_t* order, const int32_t* subband, int64_t n, const int32_t* amax,
+                      int16_t* symbols, pcgc_stream_t stream);
+int pcgc_raht_dequantize(const int16_t* symbols, int64_t n, const int32_t* patch, int64_t n_patch, const int32_t* order,
+                         const int32_t* subband, const int32_t* amax, int64_t m, double step, double* coef,
+                         pcgc_stream_t stream);
+
 /* points2voxels (dataprocess/inout_points.py:116-132) on device: scatter
  * n points (cube index, x, y, z as int32 x4) into zero-initialised float cubes. */
 int pcgc_voxelize(const int32_t* cube_xyz, int64_t n, int cube_size, float* cubes,

@@ -72,6 +72,16 @@ HIP_API = {
     "pcgc_recolor": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_color_mse_workspace_bytes": (c_sz, [c_int, c_i64]),
     "pcgc_color_mse": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_raht_workspace_bytes": (c_sz, [c_i64]),
+    "pcgc_raht_keys": (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    "pcgc_raht_structure": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_raht_forward": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_raht_inverse": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_raht_load_colors": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "pcgc_raht_store_colors": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "pcgc_raht_quantize": (c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "pcgc_raht_symbols": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pcgc_raht_dequantize": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp]),
     "pcgc_conv3d_bwd_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "pcgc_conv3d_bwd_data": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "pcgc_conv3d_bwd_data_fused": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),

@@ -38,6 +38,7 @@ HIP_SOURCES = {
     "mesh.hip": ["-ffp-contract=off"],
     "pointnums.hip": ["-ffp-contract=off"],
     "color.hip": ["-ffp-contract=off"],
+    "raht.hip": ["-ffp-contract=off"],
 }
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-fno-gpu-rdc"]

@@ -2,9 +2,9 @@
 
     python -m pcgcv1_amd.recolor --source ORIGINAL.ply --target X_rec.ply --output X_rec_color.ply
 
-The codec is a geometry codec: its bitstream holds no colours.  This is the encoder-side / evaluation step that usually
-follows it — the original's colours are transferred onto the reconstruction, which an attribute coder would then compress
-and `metrics.color_metrics` can measure.  The rule (DESIGN.md "Colours"; include/pcgc.h, pcgc_recolor), in integers:
+The geometry files hold no colours.  This is the encoder-side / evaluation step that follows the geometry codec — the
+original's colours are transferred onto the reconstruction, which the attribute coder (colorcodec.py, `test.py compress
+--colors raht`) then compresses and `metrics.color_metrics` can measure.  The rule (DESIGN.md "Colours"; include/pcgc.h, pcgc_recolor), in integers:
 
     N_T(s) = all target points at the minimal distance from the source point s (ties kept);  B(t) = { s : t in N_T(s) }
     colour(t) = (2 sum_{B(t)} c_s + |B(t)|) // (2 |B(t)|) per channel, the mean rounded half up,

@@ -4,7 +4,8 @@
     python -m pcgcv1_amd.test decompress compressed/X --ckpt_dir=checkpoints/hyper/a6.00b3.00
 
 compress writes ./compressed/<basename>.{strings,strings_head,strings_hyper,pointnums,cubepos};
-decompress writes <name>_rec.ply.  --ckpt_dir additionally accepts "synthetic[:seed[:profile]]"
+decompress writes <name>_rec.ply.  compress --colors=raht --color_qstep=Q (a coloured ply) adds <basename>.colors, the colours
+of the decoded points (pcgcv1_amd/colorcodec.py); decompress finds that file and writes a coloured ply.  --ckpt_dir additionally accepts "synthetic[:seed[:profile]]"
 (checkpoint.py).  --gpu=0 is rejected: this build has no CPU path; --gpu=N shards the cubes over N GPUs
 (one rank per GPU over RCCL, pcgcv1_amd/sharding.py; same files as one GPU).
 """
@@ -28,8 +29,12 @@ _FLAGS = [
     ("gpu", int, 1, "GPUs to use: 1 = this process; N > 1 = the cube list sharded over N ranks, one per GPU (started here "
                     "unless a launcher already set WORLD_SIZE); 0 is refused: there is no CPU path"),
     ("colors_from", str, "", "decompress only: the ORIGINAL coloured ply; the written _rec.ply then carries its colours transferred "
-                             "onto the decoded points (pcgcv1_amd/recolor.py).  An encoder-side / evaluation tool: the bitstream "
-                             "holds no colours, a real decoder does not have this file"),
+                             "onto the decoded points (pcgcv1_amd/recolor.py).  An encoder-side / evaluation tool: a real decoder "
+                             "does not have this file.  Colours that travel in the bitstream: compress --colors=raht"),
+    ("colors", str, "none", "compress only: 'raht' = code the colours of the decoded points (the input's, transferred onto the "
+                            "encoder's own reconstruction at rho = 1) into <name>.colors with the RAHT codec "
+                            "(pcgcv1_amd/colorcodec.py); decompress then writes a coloured ply.  'none' = geometry only"),
+    ("color_qstep", float, 4.0, "quantiser step of --colors=raht (all three YCoCg channels); larger = fewer bits"),
 ]
 
 
@@ -41,7 +46,7 @@ def parse_args(argv=None):
     ap.add_argument("output", nargs="?", help="output stem / .ply (derived from the input when omitted)")
     for name, typ, default, meaning in _FLAGS:
         ap.add_argument("--" + name, type=typ, default=default, help=meaning,
-                        **({"choices": ("count", "d1")} if name == "pointnums" else {}))
+                        **({"choices": ("count", "d1")} if name == "pointnums" else {"choices": ("none", "raht")} if name == "colors" else {}))
     args = ap.parse_args(argv)
     print(args)
     return args
@@ -140,6 +145,25 @@ def main(argv=None):
         raise SystemExit("multi-GPU runs write geometry only (--colors_from runs on one GPU)")
     if args.colors_from and args.command != "decompress":
         raise SystemExit("--colors_from belongs to decompress: compress reads geometry only, the bitstream holds no colours")
+    if args.colors != "none":
+        if args.command != "compress":
+            raise SystemExit("--colors belongs to compress: decompress decodes <name>.colors whenever the file is there")
+        if args.gpu > 1 or world > 1:
+            raise SystemExit("multi-GPU runs write geometry only (--colors=raht runs on one GPU)")
+        if args.scale != 1:
+            raise SystemExit("--colors=raht codes the colours of a voxelised reconstruction: --scale must be 1 (got %g)" % args.scale)
+        if not (args.color_qstep > 0):
+            raise SystemExit("--color_qstep must be positive (got %g)" % args.color_qstep)
+    if args.command == "decompress" and args.input and os.path.exists(args.input + ".colors"):
+        why = "%s.colors holds the colours of the rho = 1, scale = 1 reconstruction, decoded on one GPU" % args.input
+        if args.rho != 1:
+            raise SystemExit("--rho=%g: %s (decode with --rho=1, or remove the file for geometry only)" % (args.rho, why))
+        if args.scale != 1:
+            raise SystemExit("--scale=%g: %s" % (args.scale, why))
+        if args.colors_from:
+            raise SystemExit("--colors_from: %s; the stream's own colours are written, no original is needed" % why)
+        if args.gpu > 1 or world > 1:
+            raise SystemExit("--gpu=%d: %s" % (max(args.gpu, world), why))
     if args.gpu > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_launch(argv, args.gpu))
     if args.gpu > 1 and world != args.gpu:                 # e.g. --gpu=8 under `torchrun --nproc-per-node 1`: never silently one GPU
@@ -154,11 +178,17 @@ def main(argv=None):
     if args.command == "compress":
         if not args.output:
             args.output = os.path.split(args.input)[-1][:-4]
+        coded_colors = args.colors == "raht"
+        if coded_colors:                          # before any GPU work: a ply without colours is refused by name
+            from .recolor import load_source
+            src_points, src_colors = load_source(args.input)
         cubes, cube_positions, points_numbers = preprocess(args.input, args.scale, args.cube_size, args.min_num)
+        logits = None
         if args.mode == "factorized":
             strings, min_v, max_v, shape = compress_factorized(cubes, model, args.ckpt_dir, verbose=True)
-            if args.pointnums == "d1":           # the decoder's logits: decode the strings as decompress does
+            if args.pointnums == "d1" or coded_colors:           # the decoder's logits: decode the strings as decompress does
                 logits = decompress_factorized(strings, min_v, max_v, shape, model, args.ckpt_dir)
+            if args.pointnums == "d1":
                 points_numbers = _d1_counts(cubes, logits, points_numbers)
             bs.write_binary_files_factorized(args.output, strings, points_numbers, cube_positions, min_v, max_v, shape,
                                              rootdir='./compressed')
@@ -174,9 +204,11 @@ def main(argv=None):
                 time.sleep(0.003)
                 return bs.encode_cube_positions(cube_positions)
             cubepos = _lib.workers("job").submit(_cubepos)
-            if args.pointnums == "d1":           # the encoder-side reconstruction is what the decoder will compute
+            if args.pointnums == "d1" or coded_colors:           # the encoder-side reconstruction is what the decoder will compute
                 out = compress_hyper(cubes, model, args.ckpt_dir, decompress=True, verbose=stage_times)
-                points_numbers = _d1_counts(cubes, out[8], points_numbers)
+                logits = out[8]
+                if args.pointnums == "d1":
+                    points_numbers = _d1_counts(cubes, logits, points_numbers)
                 out = out[:8]
             else:
                 out = compress_hyper(cubes, model, args.ckpt_dir, verbose=stage_times)
@@ -185,10 +217,13 @@ def main(argv=None):
             bs.write_binary_files_hyper(args.output, y_strings, z_strings, points_numbers, cube_positions, y_min_vs,
                                         y_max_vs, y_shape, z_min_v, z_max_v, z_shape, rootdir='./compressed',
                                         cubepos=cubepos.result())
+        if coded_colors:
+            _write_colors(args, logits, points_numbers, cube_positions, src_points, src_colors)
     else:
         rootdir, filename = os.path.split(args.input)
         if not args.output:
             args.output = filename + "_rec.ply"
+        colors_file = args.input + ".colors" if os.path.exists(args.input + ".colors") else ""
         if args.mode == "factorized":
             strings, points_numbers, cube_positions, min_v, max_v, shape = bs.read_binary_files_factorized(filename, rootdir)
             cubes = decompress_factorized(strings, min_v, max_v, shape, model, args.ckpt_dir, verbose=True)
@@ -199,7 +234,7 @@ def main(argv=None):
             # the tail (top-k, points, text, file) follows the decoder slice by slice instead of waiting for the last cube;
             # PCGC_STREAM_TAIL=0 / --scale != 1 / PCGC_STAGE_TIMES=1: postprocess on the whole batch, as the reference does
             tail = None
-            if args.scale == 1 and not stage_times and os.environ.get("PCGC_STREAM_TAIL", "1") != "0" and not args.colors_from:
+            if args.scale == 1 and not stage_times and os.environ.get("PCGC_STREAM_TAIL", "1") != "0" and not args.colors_from and not colors_file:
                 tail = StreamedPostprocess(args.output, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
             cubes = decompress_hyper(y_strings, y_min_vs, y_max_vs, y_shape, z_strings, z_min_v, z_max_v, z_shape, model,
                                      args.ckpt_dir, verbose=stage_times, on_slice=tail)
@@ -211,6 +246,8 @@ def main(argv=None):
             _report(model, args.ckpt_dir, t0)
         if args.colors_from:
             return _write_recolored(args, cubes, points_numbers, cube_positions)
+        if colors_file:
+            return _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file)
         postprocess(args.output, cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
 
 
@@ -227,6 +264,36 @@ def _write_recolored(args, cubes, points_numbers, cube_positions):
     write_ply_colors(args.output, pts, colors)
     print("Recolour from {} and write {}: {}s ({} of {} points coloured from their own nearest source points)".format(
         args.colors_from, args.output, round(time.time() - t0, 4), int((counts == 0).sum()), len(pts)))
+
+
+def _write_colors(args, logits, points_numbers, cube_positions, src_points, src_colors):
+    """--colors=raht: the points the decoder will write at rho = 1 (from the encoder's own decode), the input's colours transferred
+    onto them, coded into compressed/<name>.colors"""
+    import numpy as np
+    from .colorcodec import encode_colors, write_colors_file
+    from .process import postprocess_points
+    from .recolor import recolor
+    t0 = time.time()
+    pts = np.asarray(postprocess_points(logits, points_numbers, cube_positions, 1, args.cube_size, 1)).astype(np.int32)
+    data = encode_colors(pts, recolor(src_points, src_colors, pts), args.color_qstep)
+    name = os.path.join("./compressed", args.output + ".colors")
+    write_colors_file(name, data)
+    print("colors raht: {} bytes ({:.4f} bits per input point, color_qstep {:g}) for {} decoded points -> {}: {}s".format(
+        len(data), 8.0 * len(data) / len(src_points), args.color_qstep, len(pts), name, round(time.time() - t0, 4)))
+
+
+def _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file):
+    """<name>.colors is there: the decoded points (postprocess's, in its order) with the colours the stream holds"""
+    import numpy as np
+    from .colorcodec import decode_colors, read_colors_file
+    from .dataprocess.inout_points import write_ply_colors
+    from .process import postprocess_points
+    print('===== Post process =====')
+    t0 = time.time()
+    pts = postprocess_points(cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
+    colors = decode_colors(np.asarray(pts).astype(np.int32), read_colors_file(colors_file))
+    write_ply_colors(args.output, pts, colors)
+    print("Decode {} and write {}: {}s ({} points)".format(colors_file, args.output, round(time.time() - t0, 4), len(pts)))
 
 
 if __name__ == "__main__":
