@@ -320,6 +320,35 @@ int pcgc_raht_symbols(const int32_t* q, const int32_t* order, const int32_t* sub
 int pcgc_raht_dequantize(const int16_t* symbols, int64_t n, const int32_t* patch, int64_t n_patch, const int32_t* order,
                          const int32_t* subband, const int32_t* amax, int64_t m, double step, double* coef,
                          pcgc_stream_t stream);
+/* sums (device int64 [37 * 3], zeroed by the call): sums[subband * 3 + c] = sum over the rows k < n of q of subband `subband` of
+ * min(|q[k][c]|, amax[subband] + 1) — the first moment colorcodec.choose_ratio fits a table to, so that the symbols need not
+ * leave the device for a histogram.  amax as pcgc_raht_symbols takes it (after the per-level maxima are known). */
+int pcgc_raht_abs_sums(const int32_t* q, const int32_t* order, const int32_t* subband, int64_t n, const int32_t* amax,
+                       int64_t* sums, pcgc_stream_t stream);
+
+/* ---- Chunked 64-way interleaved rANS, the entropy coder of colour stream version 2 (csrc/rans.hip; DESIGN.md 7d;
+ * tests/_rans_ref.py is the rule in numpy) ---------------------------------------------------------------------------------
+ * State uint32, lower bound 2^16, 16-bit words, 16-bit tables.  One wavefront per chunk; symbol j of a chunk belongs to lane
+ * j % 64 and step j / 64.  All arrays are device arrays:
+ *   symbols   int16 [n_symbols], as pcgc_raht_symbols writes them (flat [K,3]);
+ *   chunks    int64 [n_chunks,3] = (level, index of the chunk's first symbol in `symbols`, n) with 1 <= n <= 64 steps_per_chunk;
+ *             the table of symbol i is the level's table of channel i % 3;
+ *   cdfs      int32 [cdf_total]: per level three tables of (symbols + 1) entries each, 0 .. 65536, every frequency >= 1;
+ *             cdf_offsets int64 [n_levels + 1] = where each level's tables start; max_entries = the longest table (<= 4098).
+ * pcgc_rans_encode writes the chunks' bytes (min(n, 64) final states as uint32, lane ascending, then the words in the order
+ * the decoder takes them) back to back into out (2-byte aligned; 2 bytes per symbol of the chunks + 256 per chunk always suffice) and
+ * offsets int64 [n_chunks + 1] = where each chunk starts, the last entry the total.  A chunk whose descriptor does not fit
+ * the arrays is refused: it gets no bytes (offsets[c + 1] == offsets[c]).
+ * pcgc_rans_decode reads payload (2-byte aligned) with the same offsets, writes the symbols and status int32 [n_chunks]:
+ * 0 = ok, bit 0 = a final state differs from 2^16, bit 1 = words left over or missing, 4 = descriptor or byte range
+ * refused (nothing of that chunk was read).  Every read of the stream is clamped to the chunk's own bytes. */
+size_t pcgc_rans_workspace_bytes(int64_t n_chunks, int steps_per_chunk);
+int pcgc_rans_encode(const int16_t* symbols, int64_t n_symbols, const int64_t* chunks, int64_t n_chunks, const int32_t* cdfs,
+                     const int64_t* cdf_offsets, int n_levels, int64_t cdf_total, int max_entries, int steps_per_chunk, void* out,
+                     int64_t out_bytes, int64_t* offsets, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_rans_decode(const void* payload, int64_t payload_bytes, const int64_t* offsets, const int64_t* chunks, int64_t n_chunks,
+                     const int32_t* cdfs, const int64_t* cdf_offsets, int n_levels, int64_t cdf_total, int max_entries,
+                     int steps_per_chunk, int16_t* symbols, int64_t n_symbols, int32_t* status, pcgc_stream_t stream);
 
 /* points2voxels (dataprocess/inout_points.py:116-132) on device: scatter
  * n points (cube index, x, y, z as int32 x4) into zero-initialised float cubes. */

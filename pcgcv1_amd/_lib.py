@@ -82,6 +82,10 @@ HIP_API = {
     "pcgc_raht_quantize": (c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp, c_vp]),
     "pcgc_raht_symbols": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pcgc_raht_dequantize": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp]),
+    "pcgc_raht_abs_sums": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pcgc_rans_workspace_bytes": (c_sz, [c_i64, c_int]),
+    "pcgc_rans_encode": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_rans_decode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
     "pcgc_conv3d_bwd_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "pcgc_conv3d_bwd_data": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "pcgc_conv3d_bwd_data_fused": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),

@@ -39,6 +39,7 @@ HIP_SOURCES = {
     "pointnums.hip": ["-ffp-contract=off"],
     "color.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
+    "rans.hip": [],
 }
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-fno-gpu-rdc"]

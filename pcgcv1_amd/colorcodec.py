@@ -1,7 +1,8 @@
-"""Colour codec for decoded geometry: RAHT + uniform quantiser + static range coding -> <name>.colors.
+"""Colour codec for decoded geometry: RAHT + uniform quantiser + static entropy coding -> <name>.colors.
 
     data = encode_colors(points, colors, qstep)          # points int [M,3] unique voxels, colors uint8 [M,3]
-    colors = decode_colors(points, data)                 # uint8 [M,3] in the order of `points`
+    data = encode_colors(points, colors, qstep, coder="rans")            # stream version 2: the entropy coder runs on the GPU too
+    colors = decode_colors(points, data)                 # uint8 [M,3] in the order of `points`; either version
 
 The rule (tests/_raht_ref.py is its definition in numpy): YCoCg-R, the region-adaptive hierarchical transform
 over the Morton order of the voxels, q = rint(coef / qstep), range coding of q per subband (level, channel) with a two-sided
@@ -19,6 +20,19 @@ The file, little endian:
     (position delta as a varint, value as a zigzag varint, positions k * 3 + c ascending) and the raw tail: q of every leaf of
     the levels >= L and of the DC, zigzag varints.  L follows from the geometry: the lowest level above which (itself
     included) at most RAW_LEAVES leaves remain, where tables would cost more than they save.
+
+Version 2 (coder="rans"; tests/_rans_ref.py is its definition in numpy, csrc/rans.hip codes it): the same header with version = 2,
+the same q, tables, escapes and raw tail; only the entropy coder of the large levels differs.  A level of at least
+RANS_MIN_SYMBOLS symbols (3 x its leaves) is cut into chunks of 64 RANS_STEPS symbols (the last one shorter) and every chunk is
+coded on its own with 64 interleaved rANS lanes (state uint32, lower bound 2^16, 16-bit words; symbol j of a chunk belongs to
+lane j % 64 and step j / 64, its table is the level's table of channel (first + j) % 3).  A chunk's bytes are its min(n, 64) final
+states (uint32, lane ascending) and then its words in the order the decoder takes them (steps ascending, lanes ascending
+within a step).  A smaller level keeps version 1's range stream: a chunk carries up to 256 bytes of states, more than the top
+levels' whole payload.
+
+    36  14 L  per coded level: amax u16, ratio[Y, Co, Cg] u16 (Q16), coder u16 (0 = range, 1 = rANS), stream bytes u32
+    then, for the rANS levels in level order, one u32 per chunk: the chunk's bytes (ceil(3 leaves / (64 RANS_STEPS)) chunks per
+    level; they add up to the level's stream bytes), then the L streams, the escapes and the raw tail as in version 1.
 """
 import struct
 
@@ -30,6 +44,15 @@ MAGIC = b"PCRA"
 VERSION = 1
 HEADER_BYTES = 36
 LEVEL_BYTES = 12
+VERSION_RANS = 2           # the stream version coder="rans" writes
+LEVEL_BYTES_RANS = 14
+CODER_RANGE, CODER_RANS = 0, 1
+RANS_LANES = 64
+# format constants of version 2, confirmed from profiles/colorcodec_rans_rd.txt (bytes of the alternatives on both clouds) and
+# profiles/colorcodec_rans_bench.txt (times at S = 512 ... 4096); DESIGN.md 7d gives the reasoning
+RANS_STEPS = 2048          # S: a chunk holds up to 64 S symbols
+RANS_MIN_SYMBOLS = 16384   # T: a level with fewer symbols keeps the range coder
+RANS_LOW = 1 << 16         # L: the lower bound of a lane's state, and its value before the first and after the last symbol
 RAW_LEAVES = 48            # the top of the tree, at most this many leaves (DC included), is stored raw
 AMAX_CAP = 2047            # largest |q| with a symbol of its own; larger values take the escape symbol
 MAX_COORD = 4095           # 12-bit clouds, as recolor
@@ -81,8 +104,13 @@ def build_tables(amax, ratios):
 def choose_ratio(abs_hist):
     """Q16 ratio of the geometric table for a subband with abs_hist[k] values of magnitude k: the moment fit
     E|q| = 2 r / (1 - r^2).  The encoder's choice only: the decoder reads the 16 bits."""
-    n = float(abs_hist.sum())
-    mean = float((abs_hist * np.arange(len(abs_hist))).sum()) / n if n else 0.0
+    return ratio_of_sum(int((abs_hist * np.arange(len(abs_hist))).sum()), int(abs_hist.sum()))
+
+
+def ratio_of_sum(abs_sum, n):
+    """choose_ratio from the integer sum of the n magnitudes (pcgc_raht_abs_sums): the same double, the same ratio"""
+    n = float(n)
+    mean = float(abs_sum) / n if n else 0.0
     r = (np.sqrt(1.0 + mean * mean) - 1.0) / mean if mean > 0 else 0.0
     return int(min(65535, max(1, int(round(r * 65536)))))
 
@@ -172,18 +200,16 @@ def pack(d, m, qstep, level_counts, amax, symbols, tail, esc_pos=(), esc_val=())
     return head + payload
 
 
-def unpack(data, d, m, level_counts):
-    """-> (qstep, amax int32 [L], symbols int16 [K,3], patch int32 [P,2]): patch rows (k * 3 + c, q) hold the escaped values and
-    the raw tail.  d, m and level_counts are the decoded geometry's; every disagreement is a ValueError that says which."""
-    from . import coder_ops
+def _read_header(data, d, m, level_counts, want_version, level_bytes):
+    """the checks both versions share -> (counts, n_coded, qstep, n_esc, payload)"""
     data = bytes(data)
     if len(data) < HEADER_BYTES:
         raise ValueError(".colors: %d bytes, shorter than its %d-byte header (truncated file)" % (len(data), HEADER_BYTES))
     if data[:4] != MAGIC:
         raise ValueError(".colors: wrong magic %r (want %r): not a colour stream" % (data[:4], MAGIC))
     version, fd, n_coded, fm, qstep, crc, n_esc, gcrc = struct.unpack("<BBHQdIII", data[4:HEADER_BYTES])
-    if version != VERSION:
-        raise ValueError(".colors: version %d, this decoder reads version %d" % (version, VERSION))
+    if version != want_version:
+        raise ValueError(".colors: version %d, this decoder reads version %d" % (version, want_version))
     if fd != d or fm != m:
         raise ValueError(".colors was coded for other geometry: it holds d = %d, M = %d, the decoded points have d = %d, M = %d"
                          % (fd, fm, d, m))
@@ -195,10 +221,33 @@ def unpack(data, d, m, level_counts):
     if not (qstep > 0 and np.isfinite(qstep)):
         raise ValueError(".colors: color_qstep %r is not a positive number" % (qstep,))
     payload = data[HEADER_BYTES:]
-    if len(payload) < LEVEL_BYTES * n_coded:
+    if len(payload) < level_bytes * n_coded:
         raise ValueError(".colors: truncated in the level table")
     if _crc(payload) != crc:
         raise ValueError(".colors: checksum mismatch (truncated or corrupt payload)")
+    return counts, n_coded, qstep, n_esc, payload
+
+
+def _read_patch(payload, at, n_esc, k_raw, m):
+    """the escape list and the raw tail, from payload[at:] to its end -> patch int32 [P,2]"""
+    esc, at = _get_varints(payload, at, 2 * n_esc, "escape list")
+    esc = esc.reshape(-1, 2)
+    tail, at = _get_varints(payload, at, 3 * (m - k_raw), "raw tail")
+    if at != len(payload):
+        raise ValueError(".colors: %d bytes after the raw tail" % (len(payload) - at))
+    esc_pos = np.cumsum(esc[:, 0])
+    if len(esc_pos) and esc_pos[-1] >= 3 * k_raw:
+        raise ValueError(".colors: an escape position lies outside the coded levels")
+    patch = np.concatenate([np.stack([esc_pos, _unzigzag(esc[:, 1])], -1),
+                            np.stack([np.arange(3 * k_raw, 3 * m, dtype=np.int64), _unzigzag(tail)], -1)]).astype(np.int32)
+    return patch
+
+
+def unpack(data, d, m, level_counts):
+    """-> (qstep, amax int32 [L], symbols int16 [K,3], patch int32 [P,2]): patch rows (k * 3 + c, q) hold the escaped values and
+    the raw tail.  d, m and level_counts are the decoded geometry's; every disagreement is a ValueError that says which."""
+    from . import coder_ops
+    counts, n_coded, qstep, n_esc, payload = _read_header(data, d, m, level_counts, VERSION, LEVEL_BYTES)
     rows = [struct.unpack("<HHHHI", payload[LEVEL_BYTES * l:LEVEL_BYTES * (l + 1)]) for l in range(n_coded)]
     at = LEVEL_BYTES * n_coded
     k_raw = sum(counts[:n_coded])
@@ -211,22 +260,104 @@ def unpack(data, d, m, level_counts):
             symbols[k:k + counts[l]] = coder_ops.range_decode(payload[at:at + nbytes], (counts[l], 3), build_tables(a, [r0, r1, r2])[None])
         at += nbytes
         k += counts[l]
-    esc, at = _get_varints(payload, at, 2 * n_esc, "escape list")
-    esc = esc.reshape(-1, 2)
-    tail, at = _get_varints(payload, at, 3 * (m - k_raw), "raw tail")
-    if at != len(payload):
-        raise ValueError(".colors: %d bytes after the raw tail" % (len(payload) - at))
-    esc_pos = np.cumsum(esc[:, 0])
-    if len(esc_pos) and esc_pos[-1] >= 3 * k_raw:
-        raise ValueError(".colors: an escape position lies outside the coded levels")
-    patch = np.concatenate([np.stack([esc_pos, _unzigzag(esc[:, 1])], -1),
-                            np.stack([np.arange(3 * k_raw, 3 * m, dtype=np.int64), _unzigzag(tail)], -1)]).astype(np.int32)
+    patch = _read_patch(payload, at, n_esc, k_raw, m)
     return float(qstep), np.array([r[0] for r in rows], np.int32), symbols, patch
 
 
 def header_bytes(data):
-    """bytes of the header and the level table (what the rate test does not count as payload)"""
-    return HEADER_BYTES + LEVEL_BYTES * struct.unpack("<H", bytes(data[6:8]))[0]
+    """bytes of the header and the level table (what the rate test does not count as payload); version 2's chunk table is payload"""
+    per_level = LEVEL_BYTES_RANS if bytes(data[4:5]) == bytes([VERSION_RANS]) else LEVEL_BYTES
+    return HEADER_BYTES + per_level * struct.unpack("<H", bytes(data[6:8]))[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------- container, version 2
+def rans_chunk_count(n_symbols, steps=None):
+    """chunks of a level of n_symbols symbols"""
+    per = RANS_LANES * (RANS_STEPS if steps is None else steps)
+    return -(-int(n_symbols) // per)
+
+
+def level_coders(level_counts):
+    """the coder of every coded level: rANS from RANS_MIN_SYMBOLS symbols on"""
+    counts = [int(c) for c in level_counts]
+    return [CODER_RANS if 3 * c >= RANS_MIN_SYMBOLS else CODER_RANGE for c in counts[:coded_levels(counts)]]
+
+
+def assemble_v2(d, m, qstep, level_counts, amax, ratios, streams, chunk_sizes, tail, esc_pos=(), esc_val=()):
+    """The bytes of a version 2 file from coded streams: streams[l] = the bytes of level l (range or rANS, level_coders says
+    which), chunk_sizes[l] = the bytes of each of its chunks (rANS levels; anything empty otherwise)."""
+    counts = [int(c) for c in level_counts]
+    n_coded = coded_levels(counts)
+    kinds = level_coders(counts)
+    tail = np.asarray(tail, np.int64).reshape(-1, 3)
+    if len(counts) != 3 * d + 1 or sum(counts) != m or len(tail) != m - sum(counts[:n_coded]) or not (
+            len(amax) == len(ratios) == len(streams) == len(chunk_sizes) == n_coded):
+        raise ValueError("colour container: the streams do not fit the level counts")
+    table, chunk_table = [], []
+    for l in range(n_coded):
+        if kinds[l] == CODER_RANS:
+            sizes = np.asarray(chunk_sizes[l], np.int64).reshape(-1)
+            if len(sizes) != rans_chunk_count(3 * counts[l]) or int(sizes.sum()) != len(streams[l]):
+                raise ValueError("colour container: the chunks of level %d do not fit its stream" % l)
+            chunk_table.append(sizes.astype("<u4").tobytes())
+        table.append(struct.pack("<HHHHHI", int(amax[l]), int(ratios[l][0]), int(ratios[l][1]), int(ratios[l][2]), kinds[l], len(streams[l])))
+    esc_pos = np.asarray(esc_pos, np.int64).reshape(-1)
+    esc = np.stack([np.diff(esc_pos, prepend=0), _zigzag(esc_val)], -1) if len(esc_pos) else np.zeros((0, 2), np.int64)
+    payload = b"".join(table) + b"".join(chunk_table) + b"".join(bytes(x) for x in streams) + _put_varints(esc) + _put_varints(_zigzag(tail))
+    head = MAGIC + struct.pack("<BBHQdIII", VERSION_RANS, d, n_coded, m, float(qstep), _crc(payload), len(esc_pos), _geometry_crc(counts))
+    return head + payload
+
+
+def unpack_v2(data, d, m, level_counts):
+    """The host's half of reading a version 2 file: every check that needs no symbol, and the range-coded levels.
+    -> (qstep, amax int32 [L], ratios int32 [L,3], kinds [L], streams [L] (bytes; b"" for a range level), chunk_sizes [L] (int64
+    arrays), symbols int16 [K,3] with the rows of the range-coded levels filled in and the others 0, patch int32 [P,2]).
+    d, m and level_counts are the decoded geometry's; every disagreement is a ValueError that says which."""
+    from . import coder_ops
+    counts, n_coded, qstep, n_esc, payload = _read_header(data, d, m, level_counts, VERSION_RANS, LEVEL_BYTES_RANS)
+    rows = [struct.unpack("<HHHHHI", payload[LEVEL_BYTES_RANS * l:LEVEL_BYTES_RANS * (l + 1)]) for l in range(n_coded)]
+    kinds = level_coders(counts)
+    at = LEVEL_BYTES_RANS * n_coded
+    chunk_sizes = []
+    for l, (a, r0, r1, r2, kind, nbytes) in enumerate(rows):
+        if kind != kinds[l]:
+            raise ValueError(".colors: level %d (%d symbols) names coder %d, the format gives it coder %d" % (l, 3 * counts[l], kind, kinds[l]))
+        if a > AMAX_CAP or min(r0, r1, r2) < 1:
+            raise ValueError(".colors: the table of level %d (amax %d, ratios %d %d %d) is outside the format" % (l, a, r0, r1, r2))
+        n_chunks = rans_chunk_count(3 * counts[l]) if kind == CODER_RANS else 0
+        if at + 4 * n_chunks > len(payload):
+            raise ValueError(".colors: truncated in the chunk table of level %d" % l)
+        sizes = np.frombuffer(payload, "<u4", n_chunks, at).astype(np.int64)
+        at += 4 * n_chunks
+        if kind == CODER_RANS:
+            per = RANS_LANES * RANS_STEPS
+            n_of = np.minimum(per, 3 * counts[l] - per * np.arange(n_chunks, dtype=np.int64))
+            states = 4 * np.minimum(n_of, RANS_LANES)
+            if (sizes & 1).any():
+                raise ValueError(".colors: a chunk of level %d has an odd number of word bytes" % l)
+            if (sizes < states).any() or (sizes > states + 2 * n_of).any():
+                raise ValueError(".colors: a chunk of level %d cannot hold its states and at most one word per symbol" % l)
+            if int(sizes.sum()) != nbytes:
+                raise ValueError(".colors: the chunks of level %d hold %d bytes, its stream %d" % (l, int(sizes.sum()), nbytes))
+        chunk_sizes.append(sizes)
+    k_raw = sum(counts[:n_coded])
+    symbols = np.zeros((k_raw, 3), np.int16)
+    streams = []
+    k = 0
+    for l, (a, r0, r1, r2, kind, nbytes) in enumerate(rows):
+        if at + nbytes > len(payload) or (counts[l] == 0) != (nbytes == 0):
+            raise ValueError(".colors: the stream of level %d does not fit the file (byte counts overrun the payload)" % l)
+        if kind == CODER_RANS:
+            streams.append(payload[at:at + nbytes])
+        else:
+            streams.append(b"")
+            if counts[l]:
+                symbols[k:k + counts[l]] = coder_ops.range_decode(payload[at:at + nbytes], (counts[l], 3), build_tables(a, [r0, r1, r2])[None])
+        at += nbytes
+        k += counts[l]
+    patch = _read_patch(payload, at, n_esc, k_raw, m)
+    return (float(qstep), np.array([r[0] for r in rows], np.int32), np.array([r[1:4] for r in rows], np.int32).reshape(-1, 3), kinds, streams,
+            chunk_sizes, symbols, patch)
 
 
 def write_colors_file(filename, data):
@@ -335,6 +466,129 @@ def raht_inverse(points, coef, fuse_top=True):
     return out.cpu().numpy()
 
 
+# ---------------------------------------------------------------------------------------------------------------- rANS on the device
+class _RansJob:
+    """The chunks of some runs of symbols (run i: counts[i] symbols from index bases[i] of one flat int16 array, tables cdfs[i] int32
+    [3, symbols + 1]) and their tables on the device, for pcgc_rans_encode / pcgc_rans_decode."""
+
+    def __init__(self, bases, counts, cdfs, steps, dev):
+        import torch
+        per = RANS_LANES * int(steps)
+        if steps < 1 or steps > 1 << 20:
+            raise ValueError("rANS: steps_per_chunk %r outside [1, 2^20]" % (steps,))
+        self.steps, self.dev = int(steps), dev
+        self.per_run = [-(-int(n) // per) for n in counts]
+        rows = []
+        for i, (b, n) in enumerate(zip(bases, counts)):
+            first = np.arange(self.per_run[i], dtype=np.int64) * per
+            rows.append(np.stack([np.full_like(first, i), int(b) + first, np.minimum(per, int(n) - first)], -1))
+        self.chunks = np.concatenate(rows) if rows else np.zeros((0, 3), np.int64)
+        self.n_chunks = len(self.chunks)
+        cdfs = [np.ascontiguousarray(c, np.int32) for c in cdfs]
+        for c in cdfs:
+            if c.ndim != 2 or c.shape[0] != 3 or not (3 <= c.shape[1] <= 2 * AMAX_CAP + 3) or (c[:, 0] != 0).any() or (
+                    c[:, -1] != 65536).any() or (np.diff(c, axis=1) < 1).any():
+                raise ValueError("rANS: a table is not three 16-bit CDFs of 2 .. %d symbols with every frequency >= 1" % (2 * AMAX_CAP + 2))
+        self.n_runs = len(cdfs)
+        if self.n_chunks:
+            self.max_entries = max(c.shape[1] for c in cdfs)
+            off = np.cumsum([0] + [c.size for c in cdfs]).astype(np.int64)
+            self.cdf_total = int(off[-1])
+            self.cdfs_d = torch.from_numpy(np.concatenate([c.reshape(-1) for c in cdfs])).to(dev)
+            self.off_d = torch.from_numpy(off).to(dev)
+            self.chunks_d = torch.from_numpy(np.ascontiguousarray(self.chunks)).to(dev)
+
+    def split(self, per_chunk):
+        """per-chunk values -> one array per run"""
+        return np.split(np.asarray(per_chunk), np.cumsum(self.per_run)[:-1]) if self.per_run else []
+
+    def encode(self, sym_d, timings=None):
+        """sym_d int16 device tensor (flat) -> (the chunks' bytes back to back, int64 [n_chunks] bytes of each).  Two copies come
+        back: the chunk offsets (8 bytes per chunk), which tell how many bytes there are, and then those bytes."""
+        import torch
+        if not self.n_chunks:
+            return b"", np.zeros(0, np.int64)
+        lib = _lib.hip()
+        n = sym_d.numel()
+        coded = int(self.chunks[:, 2].sum())                             # the worst case: every symbol a word, every chunk 64 states
+        out = torch.empty(2 * coded + 4 * RANS_LANES * self.n_chunks, dtype=torch.uint8, device=self.dev)
+        t = _start(timings)
+        offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=self.dev)
+        ws = torch.empty(int(lib.pcgc_rans_workspace_bytes(self.n_chunks, self.steps)), dtype=torch.uint8, device=self.dev)
+        _lib.check(lib.pcgc_rans_encode(_lib.dptr(sym_d), n, _lib.dptr(self.chunks_d), self.n_chunks, _lib.dptr(self.cdfs_d), _lib.dptr(self.off_d),
+                                        self.n_runs, self.cdf_total, self.max_entries, self.steps, _lib.dptr(out), out.numel(), _lib.dptr(offsets),
+                                        _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_rans_encode")
+        t = _clock(timings, "v2: rANS encode kernels", t)
+        off = offsets.cpu().numpy()
+        sizes = np.diff(off)
+        if (sizes < 4).any():
+            raise _lib.PcgcError("pcgc_rans_encode refused chunk %d" % int(np.flatnonzero(sizes < 4)[0]))
+        payload = out[:int(off[-1])].cpu().numpy().tobytes()
+        _clock(timings, "v2: read-back of offsets and bytes", t)
+        return payload, sizes
+
+    def decode(self, payload, sizes, sym_d, timings=None):
+        """writes the symbols into sym_d (int16 device tensor, flat) -> status int32 [n_chunks]"""
+        import torch
+        if not self.n_chunks:
+            return np.zeros(0, np.int32)
+        lib = _lib.hip()
+        off = np.concatenate([[0], np.cumsum(np.asarray(sizes, np.int64))]).astype(np.int64)
+        if len(off) != self.n_chunks + 1 or int(off[-1]) != len(payload) or len(payload) == 0:
+            raise ValueError("rANS: %d chunk sizes adding up to %d bytes for %d chunks in %d bytes" % (len(off) - 1, int(off[-1]), self.n_chunks, len(payload)))
+        t = _start(timings)
+        pay_d = torch.from_numpy(np.frombuffer(bytearray(payload), np.uint8)).to(self.dev)
+        off_d = torch.from_numpy(off).to(self.dev)
+        status = torch.empty(self.n_chunks, dtype=torch.int32, device=self.dev)
+        t = _clock(timings, "v2: upload of the rANS bytes", t)
+        _lib.check(lib.pcgc_rans_decode(_lib.dptr(pay_d), pay_d.numel(), _lib.dptr(off_d), _lib.dptr(self.chunks_d), self.n_chunks,
+                                        _lib.dptr(self.cdfs_d), _lib.dptr(self.off_d), self.n_runs, self.cdf_total, self.max_entries, self.steps,
+                                        _lib.dptr(sym_d), sym_d.numel(), _lib.dptr(status), _lib.stream()), "pcgc_rans_decode")
+        _clock(timings, "v2: rANS decode kernel", t)
+        return status.cpu().numpy()
+
+
+def _rans_runs(level_counts):
+    counts = [int(c) for c in level_counts]
+    if any(c < 0 for c in counts) or any(c % 3 for c in counts[:-1]):
+        raise ValueError("rANS: level_counts are symbols per level, every level but the last a multiple of 3 (whole [count, 3] rows)")
+    return np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if counts else np.zeros(0, np.int64), counts
+
+
+def rans_encode(symbols, level_counts, cdfs, steps_per_chunk=None):
+    """The rANS kernels on their own.  symbols: int16, flat, sum(level_counts) of them, level after level; level_counts[l] symbols
+    belong to level l and are coded with cdfs[l] (int32 [3, A_l + 1], as build_tables gives; symbol i takes the table of channel
+    (index within its level) % 3); every level is cut into chunks of 64 steps_per_chunk symbols.
+    -> (bytes of all chunks back to back, int64 [chunks] bytes of each chunk)"""
+    import torch
+    dev = _lib.require_gpu()
+    bases, counts = _rans_runs(level_counts)
+    sym = np.ascontiguousarray(symbols, np.int16).reshape(-1)
+    if len(sym) != sum(counts) or len(cdfs) != len(counts):
+        raise ValueError("rANS: %d symbols and %d tables for level counts %r" % (len(sym), len(cdfs), counts))
+    for b, n, c in zip(bases, counts, cdfs):
+        if n and (int(sym[b:b + n].min()) < 0 or int(sym[b:b + n].max()) > np.shape(c)[1] - 2):
+            raise ValueError("rANS: a symbol outside its level's alphabet of %d" % (np.shape(c)[1] - 1))
+    job = _RansJob(bases, counts, cdfs, RANS_STEPS if steps_per_chunk is None else steps_per_chunk, dev)
+    return job.encode(torch.from_numpy(sym).to(dev))
+
+
+def rans_decode(payload, chunk_sizes, level_counts, cdfs, steps_per_chunk=None):
+    """the inverse of rans_encode -> (symbols int16 [sum(level_counts)], status int32 [chunks]: 0 = the chunk ended with every
+    state at 2^16 and every word taken).  The sizes are checked against the level counts here, before the kernel runs."""
+    import torch
+    dev = _lib.require_gpu()
+    bases, counts = _rans_runs(level_counts)
+    job = _RansJob(bases, counts, cdfs, RANS_STEPS if steps_per_chunk is None else steps_per_chunk, dev)
+    sizes = np.asarray(chunk_sizes, np.int64).reshape(-1)
+    states = 4 * np.minimum(job.chunks[:, 2], RANS_LANES)
+    if len(sizes) != job.n_chunks or (sizes & 1).any() or (sizes < states).any() or (sizes > states + 2 * job.chunks[:, 2]).any():
+        raise ValueError("rANS: the chunk sizes do not fit the level counts")
+    sym_d = torch.zeros(sum(counts), dtype=torch.int16, device=dev)
+    status = job.decode(bytes(payload), sizes, sym_d)
+    return sym_d.cpu().numpy(), status
+
+
 def _check_step(qstep):
     q = float(qstep)
     if not (q > 0 and np.isfinite(q)):
@@ -342,11 +596,100 @@ def _check_step(qstep):
     return q
 
 
-def encode_colors(points, colors, qstep, fuse_top=True, timings=None):
-    """points int [M,3] unique voxels in [0, 4095], colors uint8 [M,3], qstep > 0 -> the bytes of <name>.colors"""
+def _encode_rans(plan, q, sym, maxabs, amax, amax_d, n_coded, k_raw, qstep, timings, t):
+    """the version 2 tail of encode_colors: nothing per symbol leaves the device except the small levels' symbols, the escapes
+    (rare) and the raw tail; the tables come from per-subband sums, the large levels' bytes from the rANS kernels"""
+    import torch
+    from . import coder_ops
+    lib, dev, s = _lib.hip(), plan.dev, _lib.stream()
+    counts = [int(c) for c in plan.level_counts]
+    ts = _start(timings)
+    sums_d = torch.empty(37 * 3, dtype=torch.int64, device=dev)      # one per (subband, channel), as pcgc.h says
+    _lib.check(lib.pcgc_raht_abs_sums(_lib.dptr(q), _lib.dptr(plan.order), _lib.dptr(plan.subband), k_raw, _lib.dptr(amax_d), _lib.dptr(sums_d), s),
+               "pcgc_raht_abs_sums")
+    _clock(timings, "v2: abs sums kernel", ts)
+    tail = q[k_raw:].cpu().numpy()
+    esc_pos, esc_val = np.zeros(0, np.int64), np.zeros(0, np.int64)
+    if (maxabs[:n_coded] > AMAX_CAP).any():              # rare: an escape is a |q| above AMAX_CAP in a level whose amax is the cap
+        flat = q[:k_raw].reshape(-1)
+        pos_d = torch.nonzero(flat.abs() > AMAX_CAP).reshape(-1)
+        esc_pos, esc_val = pos_d.cpu().numpy(), flat[pos_d].cpu().numpy()
+    t = _clock(timings, "quantise + symbols", t)
+    ts = _start(timings)
+    sums = sums_d.cpu().numpy().reshape(-1, 3)
+    kinds = level_coders(counts)
+    base = np.concatenate([[0], np.cumsum(counts[:n_coded])]).astype(np.int64)
+    ratios = [[ratio_of_sum(int(sums[l, c]), counts[l]) for c in range(3)] for l in range(n_coded)]
+    cdfs = [build_tables(int(amax[l]), ratios[l]) for l in range(n_coded)]
+    on_gpu = [l for l in range(n_coded) if kinds[l] == CODER_RANS]
+    on_host = [l for l in range(n_coded) if kinds[l] == CODER_RANGE and counts[l]]
+    streams, chunk_sizes = [b""] * n_coded, [np.zeros(0, np.int64)] * n_coded
+    job = _RansJob([3 * base[l] for l in on_gpu], [3 * counts[l] for l in on_gpu], [cdfs[l] for l in on_gpu], RANS_STEPS, dev)
+    ts = _clock(timings, "v2: tables (host) and their upload", ts)
+    payload, sizes = job.encode(sym.reshape(-1), timings)
+    ts = _start(timings)
+    at = 0
+    for l, sz in zip(on_gpu, job.split(sizes)):
+        chunk_sizes[l] = sz
+        streams[l] = payload[at:at + int(sz.sum())]
+        at += int(sz.sum())
+    if on_host:
+        small = torch.cat([sym[base[l]:base[l + 1]] for l in on_host]).cpu().numpy()
+        at = 0
+        for l in on_host:
+            streams[l] = coder_ops.range_encode(small[at:at + counts[l]], cdfs[l][None])
+            at += counts[l]
+    data = assemble_v2(plan.d, plan.m, qstep, counts, amax, ratios, streams, chunk_sizes, tail, esc_pos, esc_val)
+    _clock(timings, "v2: small levels (host range coder), varints, crc", ts)
+    _clock(timings, "host coding", t)
+    return data
+
+
+def _decode_rans(plan, data, timings=None):
+    """the version 2 head of decode_colors -> (qstep, amax, symbols on the device, patch); everything about the file is checked on
+    the host before the kernel is launched"""
+    import torch
+    dev = plan.dev
+    counts = [int(c) for c in plan.level_counts]
+    ts = _start(timings)
+    qstep, amax, ratios, kinds, streams, chunk_sizes, symbols, patch = unpack_v2(data, plan.d, plan.m, counts)
+    ts = _clock(timings, "v2: host checks, small levels (host range coder), varints, crc", ts)
+    n_coded = len(amax)
+    base = np.concatenate([[0], np.cumsum(counts[:n_coded])]).astype(np.int64)
+    sym = torch.empty((int(base[-1]), 3), dtype=torch.int16, device=dev)
+    l = 0
+    while l < n_coded:                                   # one upload per run of neighbouring range-coded levels (usually one: the top)
+        if kinds[l] != CODER_RANGE:
+            l += 1
+            continue
+        e = l
+        while e < n_coded and kinds[e] == CODER_RANGE:
+            e += 1
+        if base[e] > base[l]:
+            sym[base[l]:base[e]] = torch.from_numpy(symbols[base[l]:base[e]]).to(dev)
+        l = e
+    on_gpu = [l for l in range(n_coded) if kinds[l] == CODER_RANS]
+    job = _RansJob([3 * base[l] for l in on_gpu], [3 * counts[l] for l in on_gpu],
+                   [build_tables(int(amax[l]), ratios[l]) for l in on_gpu], RANS_STEPS, dev)
+    _clock(timings, "v2: tables (host) and their upload", ts)
+    if job.n_chunks:
+        status = job.decode(b"".join(streams[l] for l in on_gpu), np.concatenate([chunk_sizes[l] for l in on_gpu]), sym.reshape(-1), timings)
+        if status.any():
+            c = int(np.flatnonzero(status)[0])
+            raise ValueError(".colors: corrupt rANS chunk %d of level %d (status %d: %s)" % (
+                c, on_gpu[int(job.chunks[c, 0])], int(status[c]),
+                "its states do not return to 2^16" if status[c] & 1 else "words left over or missing" if status[c] & 2 else "refused"))
+    return qstep, amax, sym, patch
+
+
+def encode_colors(points, colors, qstep, fuse_top=True, timings=None, coder="range"):
+    """points int [M,3] unique voxels in [0, 4095], colors uint8 [M,3], qstep > 0 -> the bytes of <name>.colors.  coder: "range" =
+    stream version 1 (the host's range coder), "rans" = version 2 (the large levels coded by csrc/rans.hip)"""
     import torch
     lib = _lib.hip()
     qstep = _check_step(qstep)
+    if coder not in ("range", "rans"):
+        raise ValueError("colour codec: coder must be 'range' or 'rans' (got %r)" % (coder,))
     col = np.asarray(colors)
     n = len(np.asarray(points))
     if col.shape != (n, 3) or col.dtype != np.uint8:
@@ -373,6 +716,11 @@ def encode_colors(points, colors, qstep, fuse_top=True, timings=None):
     sym = torch.empty((k_raw, 3), dtype=torch.int16, device=dev)
     _lib.check(lib.pcgc_raht_symbols(_lib.dptr(q), _lib.dptr(plan.order), _lib.dptr(plan.subband), k_raw, _lib.dptr(amax_d), _lib.dptr(sym), s),
                "pcgc_raht_symbols")
+    if coder == "rans":
+        data = _encode_rans(plan, q, sym, maxabs, amax, amax_d, n_coded, k_raw, qstep, timings, t)
+        if timings is not None:
+            timings["launches"] = plan.launches
+        return data
     symbols = sym.cpu().numpy()
     tail = q[k_raw:].cpu().numpy()
     esc_pos, esc_val = np.zeros(0, np.int64), np.zeros(0, np.int64)
@@ -397,11 +745,15 @@ def decode_colors(points, data, fuse_top=True, timings=None):
     plan = Plan(points)
     t = _clock(timings, "sort + structure", t)
     m, dev, s = plan.m, plan.dev, _lib.stream()
-    qstep, amax, symbols, patch = unpack(data, plan.d, m, plan.level_counts)
+    head = bytes(data[:HEADER_BYTES])
+    if len(head) == HEADER_BYTES and head[:4] == MAGIC and head[4] == VERSION_RANS:
+        qstep, amax, symbols, patch = _decode_rans(plan, data, timings)
+    else:                                                # version 1, and every refusal in version 1's words
+        qstep, amax, symbols, patch = unpack(data, plan.d, m, plan.level_counts)
     t = _clock(timings, "host coding", t)
     amax_d = torch.zeros(64, dtype=torch.int32, device=dev)
     amax_d[:len(amax)] = torch.from_numpy(amax).to(dev)
-    sym = torch.from_numpy(symbols).to(dev)
+    sym = symbols if torch.is_tensor(symbols) else torch.from_numpy(symbols).to(dev)
     patch_d = torch.from_numpy(np.ascontiguousarray(patch)).to(dev)
     attr = torch.empty((m, 3), dtype=torch.float64, device=dev)
     _lib.check(lib.pcgc_raht_dequantize(_lib.dptr(sym) if len(symbols) else None, len(symbols), _lib.dptr(patch_d), len(patch),

@@ -274,6 +274,48 @@ __global__ void __launch_bounds__(kThreads) symbols_kernel(const int32_t* q, con
   }
 }
 
+// sums[subband][c] += min(|q|, amax[subband] + 1) over the rows k < n: the first moment the colour tables are fitted to, in integers.
+// The rows come in subband order, so a wave almost always holds one subband: it then adds its 64 values up with lane shuffles
+// and makes one LDS atomic per channel; a wave that straddles two subbands falls back to one atomic per lane.
+__global__ void __launch_bounds__(kThreads) abs_sums_kernel(const int32_t* q, const int32_t* order, const int32_t* subband, int64_t n,
+                                                            const int32_t* amax, unsigned long long* sums) {
+  __shared__ unsigned int part[kBins * 3];                              // at most 256 x (AMAX_CAP + 1) per entry
+  if (threadIdx.x < kBins * 3) part[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool valid = k < n;
+  int l = -1;
+  unsigned int a[3] = {0u, 0u, 0u};
+  if (valid) {
+    l = min(max(subband[order[k]], 0), kBins - 1);
+    const unsigned int cap = (unsigned int)min(max(amax[l], 0), 2047) + 1u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int v = q[k * 3 + c];
+      a[c] = min(v < 0 ? 0u - (unsigned int)v : (unsigned int)v, cap);
+    }
+  }
+  const unsigned long long live = __ballot(valid);
+  if (live) {                                                           // wave-uniform
+    const int lref = __shfl(l, __ffsll((long long)live) - 1);
+    if (__all(!valid || l == lref)) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        unsigned int v = a[c];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if (lane == 0 && v) atomicAdd(&part[lref * 3 + c], v);
+      }
+    } else if (valid) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (a[c]) atomicAdd(&part[l * 3 + c], a[c]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kBins * 3 && part[threadIdx.x]) atomicAdd(&sums[threadIdx.x], (unsigned long long)part[threadIdx.x]);
+}
+
 __global__ void __launch_bounds__(kThreads) dequantize_kernel(const int16_t* sym, const int32_t* order, const int32_t* subband, int64_t n,
                                                               const int32_t* amax, double step, double* coef) {
   const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -440,6 +482,18 @@ int pcgc_raht_symbols(const int32_t* q, const int32_t* order, const int32_t* sub
   if (n == 0) return 0;
   hipLaunchKernelGGL(symbols_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, (hipStream_t)stream, q, order, subband, n, amax, symbols);
   return launch_ok("raht symbols kernel");
+}
+
+int pcgc_raht_abs_sums(const int32_t* q, const int32_t* order, const int32_t* subband, int64_t n, const int32_t* amax, int64_t* sums,
+                       pcgc_stream_t stream) {
+  PCGC_REQUIRE(sums && n >= 0 && (n == 0 || (q && order && subband && amax)), "pcgc_raht_abs_sums: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  static_assert(kBins * 3 <= kThreads, "one thread per (subband, channel) sum");
+  PCGC_CHECK_HIP(hipMemsetAsync(sums, 0, kBins * 3 * sizeof(int64_t), s));
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(abs_sums_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, s, q, order, subband, n, amax,
+                     reinterpret_cast<unsigned long long*>(sums));
+  return launch_ok("raht abs sums kernel");
 }
 
 int pcgc_raht_dequantize(const int16_t* symbols, int64_t n, const int32_t* patch, int64_t n_patch, const int32_t* order,

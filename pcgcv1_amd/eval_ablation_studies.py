@@ -11,13 +11,14 @@ from . import eval as rd
 
 
 def eval(input_file, rootdir, resolution, mode, cube_size, modelname, fixed_thres, postfix, ckpt_root=None, estimate_normals=False,
-         pointnums="count", color=False):
+         pointnums="count", color=False, color_qstep=None, color_coder="range"):
     csv_rootdir = os.path.join(rootdir, "csv")
     cfg_rootdir = os.path.join(rootdir, "cfg")
     os.makedirs(csv_rootdir, exist_ok=True)
     _, config_file = rd.set_default_config(input_file, cfg_rootdir, resolution, mode, cube_size, ckpt_root=ckpt_root, modelname=modelname)
     return rd.eval(input_file, csv_rootdir, config_file, resolution, mode=mode, cube_size=cube_size, modelname=modelname,
-                   fixed_thres=fixed_thres, postfix=postfix, estimate_normals=estimate_normals, pointnums=pointnums, color=color)
+                   fixed_thres=fixed_thres, postfix=postfix, estimate_normals=estimate_normals, pointnums=pointnums, color=color,
+                   color_qstep=color_qstep, color_coder=color_coder)
 
 
 def main(argv=None):
@@ -39,10 +40,14 @@ def main(argv=None):
                     help="what the container's .pointnums holds: the true counts, or the encoder's D1-optimised ones")
     ap.add_argument("--color", action="store_true",
                     help="recolour the rho = 1 and rho_d1 reconstructions from the (coloured) input and add pc_error's c[i],PSNRF")
+    ap.add_argument("--color_qstep", type=float, default=None,
+                    help="with --color: also code the recoloured rho = 1 reconstruction with the RAHT colour codec at this step")
+    ap.add_argument("--color_coder", choices=("range", "rans"), default="range",
+                    help="with --color_qstep: the entropy coder of the colour stream (range = version 1, rans = version 2, on the GPU)")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
         for row in eval(input_file, a.rootdir, a.resolution, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix, a.ckpt_root,
-                        a.estimate_normals, a.pointnums, a.color):
+                        a.estimate_normals, a.pointnums, a.color, a.color_qstep, a.color_coder):
             print(row)
 
 

@@ -35,6 +35,8 @@ _FLAGS = [
                             "encoder's own reconstruction at rho = 1) into <name>.colors with the RAHT codec "
                             "(pcgcv1_amd/colorcodec.py); decompress then writes a coloured ply.  'none' = geometry only"),
     ("color_qstep", float, 4.0, "quantiser step of --colors=raht (all three YCoCg channels); larger = fewer bits"),
+    ("color_coder", str, "range", "entropy coder of --colors=raht: 'range' = stream version 1 (the host's range coder); 'rans' = version "
+                                  "2, chunked interleaved rANS coded and decoded on the GPU.  decompress reads either"),
 ]
 
 
@@ -46,7 +48,8 @@ def parse_args(argv=None):
     ap.add_argument("output", nargs="?", help="output stem / .ply (derived from the input when omitted)")
     for name, typ, default, meaning in _FLAGS:
         ap.add_argument("--" + name, type=typ, default=default, help=meaning,
-                        **({"choices": ("count", "d1")} if name == "pointnums" else {"choices": ("none", "raht")} if name == "colors" else {}))
+                        **({"choices": ("count", "d1")} if name == "pointnums" else {"choices": ("none", "raht")} if name == "colors" else
+                           {"choices": ("range", "rans")} if name == "color_coder" else {}))
     args = ap.parse_args(argv)
     print(args)
     return args
@@ -145,6 +148,9 @@ def main(argv=None):
         raise SystemExit("multi-GPU runs write geometry only (--colors_from runs on one GPU)")
     if args.colors_from and args.command != "decompress":
         raise SystemExit("--colors_from belongs to decompress: compress reads geometry only, the bitstream holds no colours")
+    if args.color_coder != "range" and args.colors != "raht":
+        raise SystemExit("--color_coder=%s chooses the entropy coder of --colors=raht: give both (decompress reads the coder from the file)"
+                         % args.color_coder)
     if args.colors != "none":
         if args.command != "compress":
             raise SystemExit("--colors belongs to compress: decompress decodes <name>.colors whenever the file is there")
@@ -275,11 +281,12 @@ def _write_colors(args, logits, points_numbers, cube_positions, src_points, src_
     from .recolor import recolor
     t0 = time.time()
     pts = np.asarray(postprocess_points(logits, points_numbers, cube_positions, 1, args.cube_size, 1)).astype(np.int32)
-    data = encode_colors(pts, recolor(src_points, src_colors, pts), args.color_qstep)
+    data = encode_colors(pts, recolor(src_points, src_colors, pts), args.color_qstep, coder=args.color_coder)
     name = os.path.join("./compressed", args.output + ".colors")
     write_colors_file(name, data)
-    print("colors raht: {} bytes ({:.4f} bits per input point, color_qstep {:g}) for {} decoded points -> {}: {}s".format(
-        len(data), 8.0 * len(data) / len(src_points), args.color_qstep, len(pts), name, round(time.time() - t0, 4)))
+    print("colors raht: {} bytes ({:.4f} bits per input point, color_qstep {:g}{}) for {} decoded points -> {}: {}s".format(
+        len(data), 8.0 * len(data) / len(src_points), args.color_qstep, ", rANS" if args.color_coder == "rans" else "", len(pts), name,
+        round(time.time() - t0, 4)))
 
 
 def _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file):

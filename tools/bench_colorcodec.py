@@ -2,11 +2,15 @@
 bench cloud (828 225 points, 205 cubes, a6 checkpoint) with a textured colour field, and measure the entropy layer against the
 numpy reference's empirical entropy on the rate test's cloud.
 
-    python tools/bench_colorcodec.py [--reps 20] [--warmup 3] [--out-dir profiles]
+    python tools/bench_colorcodec.py [--reps 20] [--warmup 3] [--out-dir profiles] [--coder range|rans|both]
 
 Writes <out-dir>/colorcodec_bench.txt (encode / decode split into stages, median of --reps after warm-up, every stage ended by a
 device synchronise; launches per direction with and without the fused tree top; tests/_raht_ref.py on the host as baseline) and
 <out-dir>/colorcodec_rd.txt (bits per point, bits / H and c[i],PSNRF coded and recoloured-uncoded at the six steps).
+--coder rans / both (stream version 2, the entropy coder on the GPU: csrc/rans.hip) writes <out-dir>/colorcodec_rans_bench.txt
+(the same stages for the chosen coders, interleaved in one loop of one process, and the format constants' alternatives) and
+<out-dir>/colorcodec_rans_rd.txt (bytes of both versions at the six steps on both clouds, version 2's overhead split into
+states, chunk table and range-coded levels, bits / H on the test cloud) and leaves the two version 1 files alone.
 Needs an MI355X: there is no host path to time."""
 import argparse
 import os
@@ -30,12 +34,117 @@ def textured(points, res, sigma, seed):
     return np.clip(np.rint(col + np.random.default_rng(seed).normal(0, sigma, col.shape)), 0, 255).astype(np.uint8)
 
 
+def overhead(cc, data, points):
+    """(states, chunk table, range-coded levels, rANS words) bytes of a version 2 file"""
+    import struct
+    plan = cc.Plan(points)
+    counts = [int(c) for c in plan.level_counts]
+    _, _, _, kinds, streams, chunk_sizes, _, _ = cc.unpack_v2(data, plan.d, plan.m, counts)
+    per = cc.RANS_LANES * cc.RANS_STEPS
+    states = sum(4 * min(cc.RANS_LANES, 3 * counts[l] - per * i) for l in range(len(kinds)) for i in range(len(chunk_sizes[l])))
+    table = 4 * sum(len(c) for c in chunk_sizes)
+    rows = [struct.unpack("<HHHHHI", data[36 + 14 * l:50 + 14 * l]) for l in range(len(kinds))]
+    ranged = sum(r[5] for r in rows if r[4] == cc.CODER_RANGE)
+    return states, table, ranged, sum(len(x) for x in streams) - states
+
+
+def rans_report(a, ref, cc, rc, synthetic, model, postprocess_points, preprocess_points, compress_hyper):
+    coders = ("range", "rans") if a.coder == "both" else ("rans",)
+    s0, t0_ = cc.RANS_STEPS, cc.RANS_MIN_SYMBOLS
+    pts = synthetic.make_cloud(seed=5, res=128, n_shells=3, rmin=0.2, rmax=0.4).astype(np.int32)
+    col = textured(pts, 128, 10, 5)
+    src = synthetic.make_cloud(1300).astype(np.int32)
+    src_col = textured(src, 1024, 10, 1300)
+    cubes, pos, nums = preprocess_points(src, 1.0, 64, 64)
+    logits = compress_hyper(cubes, model, a.ckpt, decompress=True)[8]
+    rec = np.unique(np.rint(postprocess_points(logits, nums, pos, 1.0, 64, 1.0, None)).astype(np.int32), axis=0)
+    rec_col = rc.recolor(src, src_col, rec)
+    clouds = (("test cloud (tests/test_gpu_colorcodec.py::_coloured_cloud, %d points)" % len(pts), pts, col, True),
+              ("bench cloud (synthetic.make_cloud(1300) decoded with the a6 checkpoint, %d points), textured colours (sigma 10)" % len(rec), rec, rec_col, False))
+    rd = ["RAHT colour codec, stream version 2 (chunked 64-way interleaved rANS): bytes against version 1 (tools/bench_colorcodec.py --coder %s)" % a.coder,
+          "format constants: S = RANS_STEPS = %d steps per chunk, T = RANS_MIN_SYMBOLS = %d symbols" % (s0, t0_), ""]
+    for title, p, c, with_h in clouds:
+        rd.append(title)
+        rd.append("step  v1 bytes  v2 bytes  v2/v1   states  chunk table  range levels  rANS words" + ("  v1 bits/H  v2 bits/H" if with_h else ""))
+        worst = 0.0
+        for step in STEPS:
+            v1 = cc.encode_colors(p, c, step)
+            v2 = cc.encode_colors(p, c, step, coder="rans")
+            assert np.array_equal(cc.decode_colors(p, v2), cc.decode_colors(p, v1))
+            st, tb, rg, wd = overhead(cc, v2, p)
+            line = "%4d  %8d  %8d  %6.4f  %6d  %11d  %12d  %10d" % (step, len(v1), len(v2), len(v2) / len(v1), st, tb, rg, wd)
+            if with_h:
+                _, q, sub, _ = ref.codec(p, c, step)
+                h = ref.empirical_bits(q, sub)
+                worst = max(worst, 8 * len(v2) / h)
+                line += "  %9.4f  %9.4f" % (8 * len(v1) / h, 8 * len(v2) / h)
+            rd.append(line)
+        if with_h:
+            rd.append("largest version 2 bits / H = %.4f  ->  the version 2 rate test's margin m2 = %.4f" % (worst, worst - 1 + 0.05))
+        rd.append("")
+    rd.append("alternatives: v2 / v1 bytes at steps 1, 4, 32 (test cloud | bench cloud)")
+    for s_alt, t_alt in ((2048, 4096), (2048, 16384), (2048, 65536), (1024, 16384), (512, 16384), (256, 16384)):
+        cc.RANS_STEPS, cc.RANS_MIN_SYMBOLS = s_alt, t_alt
+        cells = []
+        for _, p, c, _ in clouds:
+            cells.append("  ".join("%.4f" % (len(cc.encode_colors(p, c, step, coder="rans")) / len(cc.encode_colors(p, c, step))) for step in (1, 4, 32)))
+        rd.append("S %4d  T %5d:  %s" % (s_alt, t_alt, "  |  ".join(cells)))
+    cc.RANS_STEPS, cc.RANS_MIN_SYMBOLS = s0, t0_
+    with open(os.path.join(a.out_dir, "colorcodec_rans_rd.txt"), "w") as f:
+        f.write("\n".join(rd) + "\n")
+    print("\n".join(rd), flush=True)
+
+    step = 4.0
+    out = ["RAHT colour codec, both entropy coders: times on the decoded geometry of the bench cloud (%d points, d = %d), color_qstep %g" % (len(rec), cc.Plan(rec).d, step),
+           "median of %d runs after %d warm-up runs, ms; every stage ends with a device synchronise; the coders take turns inside one loop of one process" % (a.reps, a.warmup),
+           "(tools/bench_colorcodec.py --coder %s).  'host coding': the host range coder (range); the table work, the rANS kernels and the copies (rans)" % a.coder, ""]
+    for s_alt in (s0,) + tuple(x for x in (512, 1024, 2048, 4096) if x != s0):
+        cc.RANS_STEPS = s_alt
+        runs = {(k, w): [] for k in coders for w in ("encode", "decode")}
+        size = {}
+        for i in range(a.warmup + a.reps):
+            for k in coders:
+                te, td = {}, {}
+                t0 = time.perf_counter()
+                data = cc.encode_colors(rec, rec_col, step, timings=te, coder=k)
+                te["total"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                cc.decode_colors(rec, data, timings=td)
+                td["total"] = time.perf_counter() - t0
+                size[k] = len(data)
+                if i >= a.warmup:
+                    runs[(k, "encode")].append(te)
+                    runs[(k, "decode")].append(td)
+        out.append("S = %d steps per chunk%s" % (s_alt, " (the format's)" if s_alt == s0 else " (alternative)"))
+        med = {}
+        for (k, w), r in runs.items():
+            med[(k, w)] = {key: 1e3 * float(np.median([x[key] for x in r])) for key in STAGES + ("total",)}
+        for w in ("encode", "decode"):
+            for k in coders:
+                out.append("  %-5s %s: %s | total %.3f | .colors %d bytes" % (k, w, "  ".join("%s %.3f" % (key, med[(k, w)][key]) for key in STAGES),
+                                                                             med[(k, w)]["total"], size[k]))
+            if "rans" in coders:
+                sub = sorted(key for key in runs[("rans", w)][0] if key.startswith("v2: "))
+                out.append("        rans %s, inside the stages above (each ended by its own synchronise): %s" % (
+                    w, "; ".join("%s %.3f" % (key[4:], 1e3 * float(np.median([x[key] for x in runs[("rans", w)]]))) for key in sub)))
+            if len(coders) == 2:
+                out.append("        %s: range / rans  host coding %.2fx  total %.2fx" % (w, med[("range", w)]["host coding"] / med[("rans", w)]["host coding"],
+                                                                                       med[("range", w)]["total"] / med[("rans", w)]["total"]))
+        out.append("")
+    cc.RANS_STEPS = s0
+    with open(os.path.join(a.out_dir, "colorcodec_rans_bench.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+    print("\n".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--ckpt", default=os.path.join(ROOT, "checkpoints", "hyper", "a6.00b3.00"))
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--coder", choices=("range", "rans", "both"), default="range",
+                    help="entropy coder(s) of the colour stream to measure: range = version 1, rans = version 2, both = side by side")
     a = ap.parse_args()
     import _raht_ref as ref
     from pcgcv1_amd import _lib, metrics, synthetic
@@ -46,6 +155,8 @@ def main():
     from pcgcv1_amd.transform import compress_hyper
     _lib.require_gpu()
     os.makedirs(a.out_dir, exist_ok=True)
+    if a.coder != "range":
+        return rans_report(a, ref, cc, rc, synthetic, model, postprocess_points, preprocess_points, compress_hyper)
 
     # ---- the rate test's cloud: bits / H at the six steps
     rd = ["RAHT colour codec: rate and distortion (tools/bench_colorcodec.py)", ""]
