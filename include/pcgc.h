@@ -396,6 +396,33 @@ int pcgc_pointnums_sweep(const int32_t* m, const int64_t* A, const int64_t* Bc, 
                          const int32_t* fixed_k, int L, int32_t* k_out, int64_t* sums, void* workspace,
                          size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- the same for the smallest cube-local D2 (point-to-plane) ----
+ * Stands in for eval's rho_d2 search (eval_ablation_studies.py:152-205 with the RHOS_D2 ladder of line 196; the figure is
+ * pc_error's "mseF,PSNR (p2plane)", myutils/pc_error_wrapper.py:46-51), which picks one rho per cloud at the decoder's side.
+ *
+ * pcgc_pointnums_normals: point_key int64 [n_points] = cube * cs^3 + voxel index of every input point under the mapping of
+ * pcgc_voxelize_points (< 0: a point of a dropped cube), normals float32 [n_points, 3], vox_key int64 [n_vox] the distinct
+ * keys >= 0 in ascending order (= the occupied voxels, cube by cube, in ascending voxel index: the P order of
+ * pcgc_pointnums_curves) -> vox_normals int16 [n_vox, 4] = (nx, ny, nz, 0), the normal of the voxel's lowest-index point as
+ * rint(1024 n / |n|) (float64, half to even); a zero or non-finite normal gives (0, 0, 0).  All on the device.
+ *
+ * pcgc_pointnums_curves_d2: pcgc_pointnums_curves with vox_normals int16 [total_pts, 4] of the call's cubes (8-byte
+ * aligned).  m as there; with v*(p, k) the voxel of S(k) nearest to p (ties: the lowest rank under logit descending, index
+ * ascending) and p*(v) the occupied voxel nearest to v (ties: the smallest voxel index),
+ *   A2 = sum over occupied p of ((v* - p) . n_q(p))^2,   B2 = sum over v in S(k) of ((p* - v) . n_q(p*))^2
+ * in the same flat layout, so pcgc_pointnums_sweep serves as it is.  One term is at most 3 (cs - 1)^2 1026^2: the caller
+ * cuts chunks so that (total_pts + total_seg) times that stays below 2^62. */
+size_t pcgc_pointnums_normals_workspace_bytes(int64_t n_vox);
+int pcgc_pointnums_normals(const int64_t* point_key, const float* normals, int64_t n_points, const int64_t* vox_key,
+                           int64_t n_vox, int16_t* vox_normals, void* workspace, size_t workspace_bytes,
+                           pcgc_stream_t stream);
+size_t pcgc_pointnums_curves_d2_workspace_bytes(int64_t total_seg, int64_t total_pts);
+int pcgc_pointnums_curves_d2(const float* x, const float* logits, const float* thresholds, const int16_t* vox_normals, int B,
+                             int cube_size, const int64_t* pts_off, const int64_t* seg_off, const int64_t* curve_off,
+                             int64_t total_seg, int64_t total_pts, const int32_t* seg_blocks, int n_seg_blocks,
+                             const int32_t* pts_blocks, int n_pts_blocks, int32_t* m, int64_t* A2, int64_t* B2,
+                             void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- mesh -> point cloud with normals (dataprocess/mesh2pc_open3d.py:55-85) ---- */
 /* sample_points_uniformly + np.dot(points, get_rotate_matrix()) (mesh2pc_open3d.py:57-66).  vertices double [V,3],
  * triangles int32 [T,3], area_cdf double [T] = inclusive running sum of the triangle areas (pcgc_mesh_area_cdf), all on

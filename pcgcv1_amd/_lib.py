@@ -55,6 +55,11 @@ HIP_API = {
     "pcgc_pointnums_curves_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcgc_pointnums_curves": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_vp, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_pointnums_normals_workspace_bytes": (c_sz, [c_i64]),
+    "pcgc_pointnums_normals": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_pointnums_curves_d2_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcgc_pointnums_curves_d2": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_vp,
+                                         c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_pointnums_sweep_workspace_bytes": (c_sz, [c_int, c_int]),
     "pcgc_pointnums_sweep": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_mesh_sample": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.c_uint64, c_vp, c_vp, c_vp]),

@@ -18,6 +18,14 @@
 //   pn_sweep_kernel     per (cube, assignment): argmin over k of j A + (J - j) B (ties: smallest k), or a given k
 //   pn_sum_kernel       per assignment: sum A, sum B, sum m over the cubes
 // Everything is integer arithmetic: the curves and the sums are exact and deterministic.
+//
+// The point-to-plane (D2) curves (--pointnums d2) run the same two searches and measure each winner along a normal:
+//   pn_owner_kernel / pn_nquant_kernel   the normal of every occupied voxel: that of its lowest-index input point (integer
+//                       atomic min, then a gather), quantised to rint(1024 n / |n|), int16 x 4 in P's order
+//   pn_bplane_kernel    pn_bdist_kernel's search carrying (distance, position in P); emits ((p* - v) . n_q(p*))^2
+//   pn_aplane_kernel    pn_adist_kernel's running strict minimum; each change of the nearest voxel adds (new - old) plane error,
+//                       of either sign, to the difference array
+// compact, rank, scan, gather and the sweep serve both.
 #include <climits>
 #include "common.h"
 
@@ -309,6 +317,114 @@ __global__ void __launch_bounds__(kTile) pn_sum_kernel(const int64_t* picks, int
   }
 }
 
+// ---- point-to-plane (D2) curves: the same two searches, each winner measured along the occupied voxel's normal ----
+// A voxel's normal is int16 x 4 (nx, ny, nz, 0), |component| <= 1024, read as one int2: x = nx | ny << 16, y = nz.
+__device__ __forceinline__ int64_t pn_plane(uint32_t a, uint32_t b, int2 n) {
+  const int dx = (int)(a & 255u) - (int)(b & 255u);
+  const int dy = (int)((a >> 8) & 255u) - (int)((b >> 8) & 255u);
+  const int dz = (int)(a >> 16) - (int)(b >> 16);
+  const int dot = dx * (int)(int16_t)(n.x & 0xffff) + dy * (n.x >> 16) + dz * (int)(int16_t)(n.y & 0xffff);   // <= 3 255 1024
+  return (int64_t)dot * (int64_t)dot;
+}
+
+// per ranked voxel: the nearest occupied voxel (ties: the smallest voxel index = the first in P's order, kept by the strict
+// <), then the squared distance to that voxel's plane
+__global__ void __launch_bounds__(kTile) pn_bplane_kernel(const int32_t* blocks, const int64_t* seg_off, const int64_t* pts_off,
+                                                          const int32_t* sorted_idx, const int32_t* pts, const int2* vn, int cs,
+                                                          int64_t* dB) {
+  __shared__ uint32_t tp[kTile];
+  const int b = blocks[2 * blockIdx.x], start = blocks[2 * blockIdx.x + 1];
+  const int64_t s0 = seg_off[b], p0 = pts_off[b];
+  const int M = (int)(seg_off[b + 1] - s0), N = (int)(pts_off[b + 1] - p0);
+  const int r = start + threadIdx.x;
+  const bool mine = r < M;
+  const uint32_t cv = pn_pack(mine ? sorted_idx[s0 + r] : 0, cs);
+  int best = INT_MAX, bi = 0;
+  for (int t0 = 0; t0 < N; t0 += kTile) {
+    const int u = t0 + threadIdx.x;
+    if (u < N) tp[threadIdx.x] = pn_pack(pts[p0 + u], cs);
+    __syncthreads();
+    const int n = min(kTile, N - t0);
+    for (int q = 0; q < n; ++q) {
+      const int d = pn_d2(cv, tp[q]);
+      if (d < best) { best = d; bi = t0 + q; }
+    }
+    __syncthreads();
+  }
+  if (mine) dB[s0 + r] = N > 0 ? pn_plane(pn_pack(pts[p0 + bi], cs), cv, vn[p0 + bi]) : 0;
+}
+
+// per occupied voxel: its nearest voxel over the ranked list changes only on a strict drop of the distance (ties: the lowest
+// rank); every change adds (new - old) plane error, of either sign, to the difference array at that rank
+__global__ void __launch_bounds__(kTile) pn_aplane_kernel(const int32_t* blocks, const int64_t* seg_off, const int64_t* pts_off,
+                                                          const int32_t* sorted_idx, const int32_t* pts, const int2* vn, int cs,
+                                                          int64_t* dA) {
+  __shared__ uint32_t tv[kTile];
+  const int b = blocks[2 * blockIdx.x], start = blocks[2 * blockIdx.x + 1];
+  const int64_t s0 = seg_off[b], p0 = pts_off[b];
+  const int M = (int)(seg_off[b + 1] - s0), N = (int)(pts_off[b + 1] - p0);
+  const int p = start + threadIdx.x;
+  const bool mine = p < N;
+  const uint32_t cp = pn_pack(mine ? pts[p0 + p] : 0, cs);
+  const int2 nq = mine ? vn[p0 + p] : make_int2(0, 0);
+  int cur = INT_MAX;
+  int64_t cur_e = 0;
+  unsigned long long* da = reinterpret_cast<unsigned long long*>(dA + s0);
+  for (int t0 = 0; t0 < M; t0 += kTile) {
+    const int u = t0 + threadIdx.x;
+    if (u < M) tv[threadIdx.x] = pn_pack(sorted_idx[s0 + u], cs);
+    __syncthreads();
+    if (mine) {
+      const int n = min(kTile, M - t0);
+      for (int q = 0; q < n; ++q) {
+        const int d = pn_d2(cp, tv[q]);
+        if (d < cur) {
+          const int64_t e = pn_plane(tv[q], cp, nq);
+          if (e != cur_e) atomicAdd(da + t0 + q, (unsigned long long)(e - cur_e));   // two's complement: exact in any order
+          cur = d;
+          cur_e = e;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// voxel normals: point i (key = cube * cs^3 + voxel, < 0: a point of a dropped cube) finds its voxel in the sorted distinct keys
+// and leaves the smallest i there
+__global__ void __launch_bounds__(kTile) pn_owner_kernel(const int64_t* point_key, int64_t n_points, const int64_t* vox_key,
+                                                         int64_t n_vox, int32_t* owner) {
+  const int64_t i = (int64_t)blockIdx.x * kTile + threadIdx.x;
+  if (i >= n_points) return;
+  const int64_t key = point_key[i];
+  if (key < 0) return;
+  int64_t lo = 0, hi = n_vox;                                    // first slot with vox_key >= key
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (vox_key[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  if (lo < n_vox && vox_key[lo] == key) atomicMin(&owner[lo], (int32_t)i);
+}
+
+// n_q = rint(1024 n / |n|) in float64, half to even; a zero or non-finite normal (or a voxel no point claimed) -> (0, 0, 0)
+__global__ void __launch_bounds__(kTile) pn_nquant_kernel(const int32_t* owner, const float* normals, int64_t n_points,
+                                                          int64_t n_vox, int16_t* out) {
+  const int64_t s = (int64_t)blockIdx.x * kTile + threadIdx.x;
+  if (s >= n_vox) return;
+  const int64_t i = owner[s];
+  int q[3] = {0, 0, 0};
+  if (i >= 0 && i < n_points) {
+    const double x = (double)normals[3 * i], y = (double)normals[3 * i + 1], z = (double)normals[3 * i + 2];
+    const double len = sqrt(x * x + y * y + z * z);
+    if (isfinite(x) && isfinite(y) && isfinite(z) && len > 0.0) {
+      q[0] = (int)rint(1024.0 * x / len);
+      q[1] = (int)rint(1024.0 * y / len);
+      q[2] = (int)rint(1024.0 * z / len);
+    }
+  }
+  out[4 * s] = (int16_t)q[0]; out[4 * s + 1] = (int16_t)q[1]; out[4 * s + 2] = (int16_t)q[2]; out[4 * s + 3] = 0;
+}
+
 struct CurvesWs {
   uint32_t* seg_key;
   int32_t* seg_idx;
@@ -398,6 +514,72 @@ int pcgc_pointnums_curves(const float* x, const float* logits, const float* thre
   hipLaunchKernelGGL(pn_scan_kernel, dim3(B), dim3(1024), 0, s, seg_off, w.dA, w.dB);
   if (int rc = launch_ok("pn_scan_kernel")) return rc;
   hipLaunchKernelGGL(pn_gather_kernel, dim3(B), dim3(kTile), 0, s, seg_off, curve_off, w.gend, w.dA, w.dB, m, A, Bc);
+  return launch_ok("pn_gather_kernel");
+}
+
+size_t pcgc_pointnums_normals_workspace_bytes(int64_t n_vox) { return align_up(4 * (size_t)(n_vox > 0 ? n_vox : 1)); }
+
+int pcgc_pointnums_normals(const int64_t* point_key, const float* normals, int64_t n_points, const int64_t* vox_key,
+                           int64_t n_vox, int16_t* vox_normals, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  if (n_vox == 0) return 0;
+  PCGC_REQUIRE(point_key && normals && vox_key && vox_normals && n_points > 0 && n_points < 0x7f7f7f7f && n_vox > 0 &&
+                   n_vox <= n_points,
+               "pcgc_pointnums_normals: bad arguments");
+  PCGC_REQUIRE(workspace && workspace_bytes >= pcgc_pointnums_normals_workspace_bytes(n_vox),
+               "pcgc_pointnums_normals: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* owner = (int32_t*)workspace;
+  PCGC_CHECK_HIP(hipMemsetAsync(owner, 0x7f, 4 * (size_t)n_vox, s));           // 0x7f7f7f7f: above every point index
+  hipLaunchKernelGGL(pn_owner_kernel, dim3((unsigned)((n_points + kTile - 1) / kTile)), dim3(kTile), 0, s, point_key, n_points,
+                     vox_key, n_vox, owner);
+  if (int rc = launch_ok("pn_owner_kernel")) return rc;
+  hipLaunchKernelGGL(pn_nquant_kernel, dim3((unsigned)((n_vox + kTile - 1) / kTile)), dim3(kTile), 0, s, (const int32_t*)owner,
+                     normals, n_points, n_vox, vox_normals);
+  return launch_ok("pn_nquant_kernel");
+}
+
+size_t pcgc_pointnums_curves_d2_workspace_bytes(int64_t total_seg, int64_t total_pts) {
+  return curves_layout(total_seg, total_pts, nullptr, nullptr);
+}
+
+int pcgc_pointnums_curves_d2(const float* x, const float* logits, const float* thresholds, const int16_t* vox_normals, int B,
+                             int cube_size, const int64_t* pts_off, const int64_t* seg_off, const int64_t* curve_off,
+                             int64_t total_seg, int64_t total_pts, const int32_t* seg_blocks, int n_seg_blocks,
+                             const int32_t* pts_blocks, int n_pts_blocks, int32_t* m, int64_t* A2, int64_t* B2, void* workspace,
+                             size_t workspace_bytes, pcgc_stream_t stream) {
+  if (B == 0) return 0;
+  PCGC_REQUIRE(x && logits && thresholds && pts_off && seg_off && curve_off && m && A2 && B2 && B > 0 && cube_size >= 1 &&
+                   cube_size <= 256 && total_seg >= 0 && total_seg < ((int64_t)1 << 31) && total_pts >= 0 &&
+                   n_seg_blocks >= 0 && n_pts_blocks >= 0 && (n_seg_blocks == 0 || seg_blocks) &&
+                   (n_pts_blocks == 0 || pts_blocks) && (total_pts == 0 || vox_normals) && ((uintptr_t)vox_normals & 7) == 0,
+               "pcgc_pointnums_curves_d2: bad arguments");
+  PCGC_REQUIRE(workspace && workspace_bytes >= pcgc_pointnums_curves_d2_workspace_bytes(total_seg, total_pts),
+               "pcgc_pointnums_curves_d2: workspace too small");
+  CurvesWs w;
+  curves_layout(total_seg, total_pts, (char*)workspace, &w);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t vox = (int64_t)cube_size * cube_size * cube_size;
+  const int2* vn = reinterpret_cast<const int2*>(vox_normals);
+  PCGC_CHECK_HIP(hipMemsetAsync(w.dA, 0, 8 * (size_t)total_seg, s));
+  hipLaunchKernelGGL(pn_compact_kernel, dim3(B), dim3(1024), 0, s, x, logits, thresholds, vox, pts_off, seg_off, w.pts,
+                     w.seg_key, w.seg_idx);
+  if (int rc = launch_ok("pn_compact_kernel")) return rc;
+  if (n_seg_blocks) {
+    hipLaunchKernelGGL(pn_rank_kernel, dim3(n_seg_blocks), dim3(kTile), 0, s, seg_blocks, seg_off, w.seg_key, w.seg_idx,
+                       w.sorted_idx, w.gend);
+    if (int rc = launch_ok("pn_rank_kernel")) return rc;
+    hipLaunchKernelGGL(pn_bplane_kernel, dim3(n_seg_blocks), dim3(kTile), 0, s, seg_blocks, seg_off, pts_off, w.sorted_idx,
+                       w.pts, vn, cube_size, w.dB);
+    if (int rc = launch_ok("pn_bplane_kernel")) return rc;
+  }
+  if (n_pts_blocks) {
+    hipLaunchKernelGGL(pn_aplane_kernel, dim3(n_pts_blocks), dim3(kTile), 0, s, pts_blocks, seg_off, pts_off, w.sorted_idx,
+                       w.pts, vn, cube_size, w.dA);
+    if (int rc = launch_ok("pn_aplane_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(pn_scan_kernel, dim3(B), dim3(1024), 0, s, seg_off, w.dA, w.dB);
+  if (int rc = launch_ok("pn_scan_kernel")) return rc;
+  hipLaunchKernelGGL(pn_gather_kernel, dim3(B), dim3(kTile), 0, s, seg_off, curve_off, w.gend, w.dA, w.dB, m, A2, B2);
   return launch_ok("pn_gather_kernel");
 }
 

@@ -165,13 +165,24 @@ def _d1_counts(cubes, logits, points_numbers):
     return optimize_points_numbers(cubes, logits, points_numbers)[0]
 
 
-def _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, pointnums="count"):
+def _d2_counts(points, normals, cubes, logits, points_numbers, cube_positions, scale, cube_size):
+    from .pointnums import optimize_points_numbers, voxel_normals
+    if normals is None:
+        raise ValueError("pointnums='d2' needs normals: a ply with nx ny nz, or estimate_normals=True (--estimate_normals)")
+    vn = voxel_normals(points, normals, cube_positions, scale, cube_size)
+    return optimize_points_numbers(cubes, logits, points_numbers, metric="d2", normals=vn)[0]
+
+
+def _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, pointnums="count", normals=None):
     """eval.py:45-75 without the metrics: compress_factorized, the three-file container written and read back,
     decompress_factorized.  bpps like rate_point's, the hyper and head terms 0 (eval.py:69-71)."""
     cubes, cube_positions, points_numbers = preprocess_points(points, scale, cube_size, min_num)
     strings, min_v, max_v, shape = compress_factorized(cubes, model, ckpt_dir)
     if pointnums == "d1":
         points_numbers = _d1_counts(cubes, decompress_factorized(strings, min_v, max_v, shape, model, ckpt_dir), points_numbers)
+    elif pointnums == "d2":
+        points_numbers = _d2_counts(points, normals, cubes, decompress_factorized(strings, min_v, max_v, shape, model, ckpt_dir),
+                                    points_numbers, cube_positions, scale, cube_size)
     own_tmp = rootdir is None
     rootdir = rootdir or tempfile.mkdtemp(prefix="pcgc_eval_")
     sizes = bs.write_binary_files_factorized("x", strings, points_numbers, cube_positions, min_v, max_v, shape, rootdir=rootdir,
@@ -188,17 +199,22 @@ def _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, r
     return cubes_d, pos_d, nums_d, int(n), bpps
 
 
-def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, started=None, mode="hyper", pointnums="count"):
+def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None, started=None, mode="hyper", pointnums="count",
+               normals=None):
     """eval.py:77-113 (hyper) / 45-75 (factorized) without the metrics: returns (decoded cubes, cube_positions,
     points_numbers, N, bpps) with bpps = [total, strings, strings_hyper, strings_head, pointnums, cubepos] rounded to
     4 decimals like the reference.  pointnums="d1": the container holds pointnums.optimize_points_numbers' counts (the
-    encoder-side reconstruction's; `started` is not used then)."""
+    encoder-side reconstruction's; `started` is not used then).  pointnums="d2": its D2-optimised counts, from `normals`
+    (float [N,3], one per point)."""
     if mode == "factorized":
-        return _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir, pointnums)
-    if pointnums == "d1":
+        return _rate_point_factorized(points, model, ckpt_dir, scale, cube_size, min_num, rootdir, pointnums, normals)
+    if pointnums in ("d1", "d2"):
         cubes, cube_positions, points_numbers = preprocess_points(points, scale, cube_size, min_num)
         out = compress_hyper(cubes, model, ckpt_dir, decompress=True)
-        points_numbers = _d1_counts(cubes, out[8], points_numbers)
+        if pointnums == "d1":
+            points_numbers = _d1_counts(cubes, out[8], points_numbers)
+        else:
+            points_numbers = _d2_counts(points, normals, cubes, out[8], points_numbers, cube_positions, scale, cube_size)
         stream = out[:8]
     elif started is not None:
         cube_positions, points_numbers, ahead = started
@@ -231,7 +247,8 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
     radius / max_nn with which mesh2pc_open3d.py:75-78 wrote the reference's test sets), so D2 and the rho_d2 search run
     as for a ply that carries normals.  A ply with normals keeps its own either way.
     pointnums="d1": every rate point writes the encoder's D1-optimised counts (pointnums.py) instead of the true ones; the
-    rest of the row (rho search, the three reconstructions) is computed the same way on that container.
+    rest of the row (rho search, the three reconstructions) is computed the same way on that container.  pointnums="d2": the
+    D2-optimised counts, from the normals this function already has (the ply's, or the estimated ones; neither: an error).
     color=True (the input ply must carry colours): the rho = 1 and rho_d1 reconstructions are recoloured from the original
     (recolor.py) and the row gains pc_error's c[i],PSNRF for rho = 1 and "optimal D1 c[0],PSNRF"; the rho search itself
     stays on D1 / D2.
@@ -246,6 +263,8 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
     points, normals = iop.load_ply_normals(input_file)
     if normals is None and estimate_normals:
         normals = metrics.estimate_normals(points, radius=10, max_nn=20)
+    if pointnums == "d2" and normals is None:
+        raise ValueError("%s has no normals (nx ny nz): pointnums='d2' needs them, or estimate_normals=True (--estimate_normals)" % input_file)
     colors = None
     if color:
         colors = iop.load_ply_colors(input_file)[1]
@@ -272,7 +291,7 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
         ckpt_dir = str(config.get(rate, "ckpt_dir"))
         if hyper and not ahead:
             cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num,
-                                                                          pointnums=pointnums)
+                                                                          pointnums=pointnums, normals=normals)
         elif hyper:
             cur, started = started, None
             cur[2].result()                                   # this rate's strings exist (rate_point picks them up below)
@@ -281,7 +300,7 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
             cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num, started=cur)
         else:                                                 # eval.py:188-189: test_factorized (one stream per cloud, nothing to overlap)
             cubes_d, cube_positions, points_numbers, n, bpps = rate_point(points, model, ckpt_dir, scale, cube_size, min_num,
-                                                                          mode="factorized", pointnums=pointnums)
+                                                                          mode="factorized", pointnums=pointnums, normals=normals)
 
         def reconstruct(rho):
             return postprocess_points(cubes_d, points_numbers, cube_positions, scale, cube_size, rho, fixed_thres)
@@ -352,8 +371,9 @@ def main(argv=None):
     ap.add_argument("--postfix", type=str, default="")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
-    ap.add_argument("--pointnums", choices=("count", "d1"), default="count",
-                    help="what the container's .pointnums holds: the true counts, or the encoder's D1-optimised ones")
+    ap.add_argument("--pointnums", choices=("count", "d1", "d2"), default="count",
+                    help="what the container's .pointnums holds: the true counts, the encoder's D1-optimised ones, or (d2) its "
+                         "D2-optimised ones, from the normals of the ply or of --estimate_normals")
     ap.add_argument("--color", action="store_true",
                     help="recolour the rho = 1 and rho_d1 reconstructions from the (coloured) input and add pc_error's c[i],PSNRF")
     ap.add_argument("--color_qstep", type=float, default=None,

@@ -36,8 +36,9 @@ def main(argv=None):
                                                                 "(default ./checkpoints/<mode>)")
     ap.add_argument("--estimate_normals", action="store_true",
                     help="estimate normals (radius 10, 20 neighbours) for an input ply without them, for D2 and rho_d2")
-    ap.add_argument("--pointnums", choices=("count", "d1"), default="count",
-                    help="what the container's .pointnums holds: the true counts, or the encoder's D1-optimised ones")
+    ap.add_argument("--pointnums", choices=("count", "d1", "d2"), default="count",
+                    help="what the container's .pointnums holds: the true counts, the encoder's D1-optimised ones, or (d2) its "
+                         "D2-optimised ones, from the normals of the ply or of --estimate_normals")
     ap.add_argument("--color", action="store_true",
                     help="recolour the rho = 1 and rho_d1 reconstructions from the (coloured) input and add pc_error's c[i],PSNRF")
     ap.add_argument("--color_qstep", type=float, default=None,

@@ -23,6 +23,22 @@ seen), and with --scale != 1 it is measured on the coded grid.  pc_error's whole
 therefore rank two assignments differently; DESIGN.md §"Encoder-side point counts" has the measured table.
 
 The curves and the sweep run on the device (csrc/pointnums.hip); the selection is a handful of Python integers.
+
+metric="d2" (`--pointnums d2`) does the same for the point-to-plane error.  Every occupied voxel carries the normal of the
+lowest-index input point that maps to it (the mapping of preprocess / pcgc_voxelize_points), quantised to
+n_q = rint(1024 n / |n|) (float64, half to even, int32 components; a zero or non-finite normal gives (0, 0, 0)), so all that
+follows is integer arithmetic again.  With v*(p, k) the voxel of S_b(k) nearest to p (ties: the lowest rank under logit
+descending, voxel index ascending) and p*(v) the occupied voxel nearest to v (ties: the smallest voxel index),
+
+    A2_b(k) = sum_{p in P_b} ((v*(p, k) - p) . n_q(p))^2          B2_b(k) = sum_{v in S_b(k)} ((p*(v) - v) . n_q(p*(v)))^2
+
+replace A and B: F2 = max(sum A2 / sum N, sum B2 / sum m), the sweep argmin_k j A2 + (J - j) B2, the ladder eval.RHOS_D2
+(which holds 1.0), the same tie rules, hence F2(chosen) <= F2(true counts) and <= F2(any ladder rho).  F2 carries the factor
+1024^2 of the quantised normals; the report divides it out.  Like F, F2 is cube-local (a nearest neighbour or a plane across
+a cube face is not seen) and is measured on the coded grid; pc_error's whole-cloud D2 (metrics.d2_metrics) also averages the
+normals of all points that chose a decoded point, which F2 does not, so the two can rank assignments differently.  One term
+is at most 3 (cs - 1)^2 1026^2: chunks are cut so that (points + segment voxels) times that stays below 2^62, and the
+cross-chunk totals are Python integers.
 """
 from fractions import Fraction
 
@@ -31,6 +47,8 @@ import numpy as np
 from . import _lib
 
 RHOS_D1 = [0.8, 0.9, 1.0, 1.02, 1.05, 1.10, 1.15, 1.2, 1.25, 1.30, 1.40, 1.50, 1.75, 2.0, 2.5, 3.0]   # eval.RHOS_D1
+RHOS_D2 = [1.0, 0.98, 0.95, 0.92, 0.90, 0.88, 0.85, 0.82, 0.80, 0.75, 0.70, 0.65, 0.50, 0.40, 0.30]          # eval.RHOS_D2
+NORMAL_ONE = 1024             # length of a quantised normal
 K_CAP = 65535
 _CHUNK_SEG = 1 << 23          # segment voxels per pcgc_pointnums_curves call (32 bytes each): bounds the workspace
 _TILE = 256                   # elements per workgroup of the per-element kernels (csrc/pointnums.hip kTile)
@@ -102,10 +120,34 @@ def _offsets(counts):
     return np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))]).astype(np.int64)
 
 
+def plane_term_bound(cube_size):
+    """Upper bound of one plane-error term: |d|^2 |n_q|^2 <= 3 (cs - 1)^2 1026^2 (|n_q| <= 1024 + sqrt(3) / 2)."""
+    return 3 * (int(cube_size) - 1) ** 2 * 1026 ** 2
+
+
+def chunk_plan(n_seg, n_pts=None, chunk_seg=None, term_bound=None, limit=1 << 62):
+    """[(lo, hi)]: greedy runs of cubes whose segment voxels fit chunk_seg (one cube at least).  With term_bound (the d2
+    curves): a run also keeps (points + segment voxels) * term_bound below `limit`, so no int64 sum of a chunk can wrap."""
+    chunk_seg = _CHUNK_SEG if chunk_seg is None else chunk_seg
+    B = len(n_seg)
+    elems = [int(n_seg[b]) + (int(n_pts[b]) if term_bound else 0) for b in range(B)]
+    cap = (limit - 1) // term_bound if term_bound else None          # elements a chunk may hold
+    chunks, lo = [], 0
+    while lo < B:
+        hi, tot, el = lo + 1, int(n_seg[lo]), elems[lo]
+        while hi < B and tot + int(n_seg[hi]) <= chunk_seg and (cap is None or el + elems[hi] <= cap):
+            tot += int(n_seg[hi])
+            el += elems[hi]
+            hi += 1
+        chunks.append((lo, hi))
+        lo = hi
+    return chunks
+
+
 class _Prepared(object):
     """Thresholds, counts and the chunk plan of one cube batch."""
 
-    def __init__(self, cubes, logits, points_numbers):
+    def __init__(self, cubes, logits, points_numbers, vox_normals=None):
         import torch
         self.dev = _lib.require_gpu()
         self.x, B = _flat(cubes, self.dev)
@@ -133,14 +175,17 @@ class _Prepared(object):
         self.n_pts = n_pts.cpu().numpy().astype(np.int64)
         self.n_seg = n_seg.cpu().numpy().astype(np.int64)
         self.curve_off = _offsets(self.k_max)
-        self.chunks, lo = [], 0
-        while lo < B:                                 # greedy: cubes while the chunk's segment fits (one cube at least)
-            hi, tot = lo + 1, int(self.n_seg[lo])
-            while hi < B and tot + int(self.n_seg[hi]) <= _CHUNK_SEG:
-                tot += int(self.n_seg[hi])
-                hi += 1
-            self.chunks.append((lo, hi))
-            lo = hi
+        self.vn = None
+        if vox_normals is not None:                   # the d2 curves: int16 [sum N_b, 4] in P's order (voxel_normals)
+            vn = vox_normals if torch.is_tensor(vox_normals) else torch.from_numpy(np.ascontiguousarray(vox_normals, np.int16))
+            vn = vn.to(self.dev, torch.int16).contiguous()
+            if vn.dim() != 2 or vn.shape[1] != 4 or int(vn.shape[0]) != int(self.n_pts.sum()):
+                raise ValueError("voxel normals %s for %d occupied voxels (expected int16 [%d, 4], pointnums.voxel_normals)"
+                                 % (tuple(vn.shape), int(self.n_pts.sum()), int(self.n_pts.sum())))
+            self.vn = vn
+            self.pts_off = _offsets(self.n_pts)
+        # greedy: cubes while the chunk's segment fits (one cube at least)
+        self.chunks = chunk_plan(self.n_seg, self.n_pts, _CHUNK_SEG, plane_term_bound(cs) if self.vn is not None else None)
 
     def curves(self, lo, hi, m, A, Bc):
         """curves of cubes lo..hi into m / A / Bc (device views of the chunk's curve entries)"""
@@ -153,6 +198,15 @@ class _Prepared(object):
         lib = _lib.hip()
         ws = torch.empty(int(lib.pcgc_pointnums_curves_workspace_bytes(int(seg_off[-1]), int(pts_off[-1]))), dtype=torch.uint8,
                          device=dev)
+        if self.vn is not None:
+            vn = self.vn[int(self.pts_off[lo]):int(self.pts_off[hi])]
+            _lib.check(lib.pcgc_pointnums_curves_d2(_lib.dptr(self.x[lo:hi]), _lib.dptr(self.l[lo:hi]), _lib.dptr(self.thr[lo:hi]),
+                                                    _lib.dptr(vn) if vn.numel() else None, hi - lo, self.cs, _lib.dptr(d["p"]),
+                                                    _lib.dptr(d["s"]), _lib.dptr(d["c"]), int(seg_off[-1]), int(pts_off[-1]),
+                                                    _lib.dptr(d["sb"]), len(sb) // 2, _lib.dptr(d["pb"]), len(pb) // 2,
+                                                    _lib.dptr(m), _lib.dptr(A), _lib.dptr(Bc), _lib.dptr(ws), ws.numel(),
+                                                    _lib.stream()), "pcgc_pointnums_curves_d2")
+            return d["c"]
         _lib.check(lib.pcgc_pointnums_curves(_lib.dptr(self.x[lo:hi]), _lib.dptr(self.l[lo:hi]), _lib.dptr(self.thr[lo:hi]),
                                              hi - lo, self.cs, _lib.dptr(d["p"]), _lib.dptr(d["s"]), _lib.dptr(d["c"]),
                                              int(seg_off[-1]), int(pts_off[-1]), _lib.dptr(d["sb"]), len(sb) // 2,
@@ -164,8 +218,11 @@ class _Prepared(object):
 def distortion_curves(cubes, logits, points_numbers):
     """-> (m int32, A int64, B int64, offsets int64 [B+1]): the curves of every cube, flat; cube b's k = 1 .. K_b are the
     entries offsets[b] .. offsets[b+1]-1.  m / A / B are device tensors, offsets a numpy array."""
+    return _all_curves(_Prepared(cubes, logits, points_numbers))
+
+
+def _all_curves(p):
     import torch
-    p = _Prepared(cubes, logits, points_numbers)
     tot = int(p.curve_off[-1])
     m = torch.empty(tot, dtype=torch.int32, device=p.dev)
     A = torch.empty(tot, dtype=torch.int64, device=p.dev)
@@ -174,6 +231,69 @@ def distortion_curves(cubes, logits, points_numbers):
         a, b = int(p.curve_off[lo]), int(p.curve_off[hi])
         p.curves(lo, hi, m[a:b], A[a:b], Bc[a:b])
     return m, A, Bc, p.curve_off
+
+
+def point_keys(points, cube_positions, scale, cube_size):
+    """int64 [n]: cube * cs^3 + voxel index of every input point, cubes in stored order (ordered_positions), or -1 for a point
+    of a cube that was dropped — the mapping of process.preprocess_points (round(float32(p) * scale) when scale != 1, floor
+    division by the cube size, row-major voxel index) for the points as given, duplicates included."""
+    from .dataprocess.inout_points import ordered_positions
+    points = np.asarray(points)
+    if scale != 1:
+        points = np.round(points.astype("float32") * scale)
+    c = np.ascontiguousarray(points, np.int32).reshape(-1, 3).astype(np.int64)
+    cs = int(cube_size)
+    cube = np.floor_divide(c, cs)
+    loc = c - cube * cs
+    spos = np.asarray(ordered_positions(cube_positions), np.int64).reshape(-1, 3)
+    if len(c) == 0 or len(spos) == 0:
+        return np.full(len(c), -1, np.int64)
+    lo = np.minimum(cube.min(0), spos.min(0))
+    ext = np.maximum(cube.max(0), spos.max(0)) - lo + 1
+
+    def flat(v):
+        v = v - lo
+        return (v[:, 0] * ext[1] + v[:, 1]) * ext[2] + v[:, 2]
+    ck, pk = flat(spos), flat(cube)
+    order = np.argsort(ck, kind="stable")
+    at = np.minimum(np.searchsorted(ck[order], pk), len(ck) - 1)
+    b = order[at]
+    found = ck[b] == pk
+    key = b.astype(np.int64) * cs ** 3 + (loc[:, 0] * cs + loc[:, 1]) * cs + loc[:, 2]
+    return np.where(found, key, -1)
+
+
+def voxel_normals(points, normals, cube_positions, scale, cube_size):
+    """The quantised normal of every occupied voxel of the cubes preprocess makes of `points` -> int16 device tensor
+    [sum N_b, 4] = (nx, ny, nz, 0), cubes in stored order, a cube's voxels in ascending voxel index (the P order of the
+    curves).  A voxel takes the normal of the lowest-index input point that maps to it (point_keys), as
+    rint(1024 n / |n|); a zero or non-finite normal gives (0, 0, 0).  No dense volume is built: the distinct keys are
+    sorted, every point finds its voxel by bisection and leaves its index by an atomic min, a gather quantises."""
+    import torch
+    dev = _lib.require_gpu()
+    keys = point_keys(points, cube_positions, scale, cube_size)
+    nrm = np.ascontiguousarray(np.asarray(normals), np.float32).reshape(-1, 3)
+    if len(nrm) != len(keys):
+        raise ValueError("%d normals for %d points" % (len(nrm), len(keys)))
+    keys_d = torch.from_numpy(keys).to(dev)
+    nrm_d = torch.from_numpy(nrm).to(dev)
+    vox_key = torch.unique(keys_d[keys_d >= 0], sorted=True).contiguous()
+    n_vox = int(vox_key.numel())
+    out = torch.zeros((n_vox, 4), dtype=torch.int16, device=dev)
+    if n_vox:
+        lib = _lib.hip()
+        ws = torch.empty(int(lib.pcgc_pointnums_normals_workspace_bytes(n_vox)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.pcgc_pointnums_normals(_lib.dptr(keys_d), _lib.dptr(nrm_d), len(keys), _lib.dptr(vox_key), n_vox,
+                                              _lib.dptr(out), _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_pointnums_normals")
+    return out
+
+
+def distortion_curves_d2(cubes, logits, points_numbers, voxel_normals):
+    """-> (m int32, A2 int64, B2 int64, offsets int64 [B+1]) in distortion_curves' layout: the point-to-plane curves, with
+    voxel_normals the int16 [sum N_b, 4] tensor pointnums.voxel_normals returns for these cubes."""
+    if voxel_normals is None:
+        raise ValueError("distortion_curves_d2 needs the voxel normals (pointnums.voxel_normals)")
+    return _all_curves(_Prepared(cubes, logits, points_numbers, voxel_normals))
 
 
 def sweep_curves(m, A, Bc, offsets, sweep=64, fixed_k=None):
@@ -200,14 +320,24 @@ def sweep_curves(m, A, Bc, offsets, sweep=64, fixed_k=None):
     return k_out.cpu().numpy().astype(np.int64), sums.cpu().numpy()
 
 
-def optimize_points_numbers(cubes, logits, points_numbers, sweep=64, rhos=RHOS_D1, resolution=1023):
-    """-> (counts uint16 [B], report).  Chunk by chunk: curves, then the sweep and the ladder on the device; the per-
+def optimize_points_numbers(cubes, logits, points_numbers, sweep=64, rhos=None, resolution=1023, metric="d1", normals=None):
+    """-> (counts uint16 [B], report).  metric="d1" (rhos: RHOS_D1 unless given) minimises F; metric="d2" (rhos: RHOS_D2)
+    minimises F2 over the point-to-plane curves and needs normals = pointnums.voxel_normals(...) of these cubes; its report
+    has the same keys with F2 / 1024^2 (voxel units) as F and the sums of A2, B2 (with the 1024^2 factor) and m.
+      Chunk by chunk: curves, then the sweep and the ladder on the device; the per-
     assignment sums are added up as Python integers and the selection (select_assignment) runs on the host.  report:
     {"choice": ("ladder", rho) or ("sweep", j), "F_count", "F_chosen" (floats), "psnr_count", "psnr_chosen" (local PSNR
     at `resolution`), "sum_n", "sums": {assignment: (sum A, sum B, sum m)}, "ks": every assignment's counts [n_assign, B]}."""
     import torch
-    rhos = list(rhos)
-    p = _Prepared(cubes, logits, points_numbers)
+    if metric not in ("d1", "d2"):
+        raise ValueError("optimize_points_numbers: metric must be 'd1' or 'd2' (got %r)" % (metric,))
+    if metric == "d2" and normals is None:
+        raise ValueError("optimize_points_numbers: metric='d2' needs normals=pointnums.voxel_normals(...)")
+    if metric == "d1" and normals is not None:
+        raise ValueError("optimize_points_numbers: normals belong to metric='d2'")
+    rhos = list((RHOS_D1 if metric == "d1" else RHOS_D2) if rhos is None else rhos)
+    p = _Prepared(cubes, logits, points_numbers, normals)
+    unit = 1 if metric == "d1" else NORMAL_ONE ** 2
     ladder = ladder_counts(p.nums, p.k_max, rhos)
     n_assign = sweep + 1 + len(rhos)
     totals = [[0, 0, 0] for _ in range(n_assign)]
@@ -232,6 +362,7 @@ def optimize_points_numbers(cubes, logits, points_numbers, sweep=64, rhos=RHOS_D
     f_count = cloud_f(ladder_sums[i1][0], sum_n, ladder_sums[i1][1], ladder_sums[i1][2]) if i1 is not None else None
     sums = {("sweep", j): tuple(sweep_sums[j]) for j in range(sweep + 1)}
     sums.update({("ladder", rhos[i]): tuple(ladder_sums[i]) for i in range(len(rhos))})
+    f, f_count = f / unit, None if f_count is None else f_count / unit
     report = {"choice": (kind, idx if kind == "sweep" else rhos[idx]), "F_chosen": float(f), "psnr_chosen": local_psnr(f, resolution),
               "F_count": None if f_count is None else float(f_count),
               "psnr_count": None if f_count is None else local_psnr(f_count, resolution), "sum_n": sum_n, "sums": sums,

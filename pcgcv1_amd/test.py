@@ -25,7 +25,9 @@ _FLAGS = [
     ("min_num", int, 64, "cubes with fewer points are dropped"),
     ("rho", float, 1.0, "output points per cube = rho x the stored point count"),
     ("pointnums", str, "count", "what .pointnums holds: 'count' = each cube's point count (the reference's); 'd1' = the counts "
-                                "that give the decoder at rho = 1 the smallest cube-local D1 (pcgcv1_amd/pointnums.py)"),
+                                "that give the decoder at rho = 1 the smallest cube-local D1 (pcgcv1_amd/pointnums.py); 'd2' = "
+                                "the same for the point-to-plane error D2, with the normals of the ply (nx ny nz) or of "
+                                "--estimate_normals"),
     ("gpu", int, 1, "GPUs to use: 1 = this process; N > 1 = the cube list sharded over N ranks, one per GPU (started here "
                     "unless a launcher already set WORLD_SIZE); 0 is refused: there is no CPU path"),
     ("colors_from", str, "", "decompress only: the ORIGINAL coloured ply; the written _rec.ply then carries its colours transferred "
@@ -48,11 +50,31 @@ def parse_args(argv=None):
     ap.add_argument("output", nargs="?", help="output stem / .ply (derived from the input when omitted)")
     for name, typ, default, meaning in _FLAGS:
         ap.add_argument("--" + name, type=typ, default=default, help=meaning,
-                        **({"choices": ("count", "d1")} if name == "pointnums" else {"choices": ("none", "raht")} if name == "colors" else
+                        **({"choices": ("count", "d1", "d2")} if name == "pointnums" else {"choices": ("none", "raht")} if name == "colors" else
                            {"choices": ("range", "rans")} if name == "color_coder" else {}))
+    ap.add_argument("--estimate_normals", action="store_true",
+                    help="compress --pointnums=d2 with a ply that has no normals: estimate them (radius 10, 20 neighbours, as eval does)")
     args = ap.parse_args(argv)
+    if args.command == "compress" and args.pointnums == "d2" and not args.estimate_normals and not _ply_has_normals(args.input):
+        # with the other argument errors, before anything is loaded: d2 has nothing to measure against without normals
+        ap.error("--pointnums=d2 needs normals: %s has no nx ny nz properties (or cannot be read); write them into the ply, or "
+                 "pass --estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
     print(args)
     return args
+
+
+def _ply_has_normals(filename):
+    """whether the ply's header declares nx, ny and nz (False for a file that is missing or has no header)"""
+    try:
+        with open(filename, "rb") as f:
+            head = f.read(1 << 16)
+    except (OSError, TypeError):
+        return False
+    end = head.find(b"end_header")
+    if end < 0:
+        return False
+    props = {ln.split()[-1] for ln in head[:end].split(b"\n") if ln.strip().startswith(b"property")}
+    return {b"nx", b"ny", b"nz"} <= props
 
 
 def _import_model(name):
@@ -79,6 +101,29 @@ def _d1_counts(cubes, logits, points_numbers):
     return counts
 
 
+def _load_normals(args):
+    """--pointnums=d2: (points, normals) of the input, before any other work: the ply's own nx ny nz, or estimated ones"""
+    from .dataprocess.inout_points import load_ply_normals
+    points, normals = load_ply_normals(args.input)
+    if normals is None:
+        if not args.estimate_normals:
+            raise SystemExit("--pointnums=d2 needs normals: %s has no nx ny nz properties; write them into the ply, or pass "
+                             "--estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
+        from .metrics import estimate_normals
+        normals = estimate_normals(points, 10, 20)
+    return points, normals
+
+
+def _d2_counts(args, cubes, logits, points_numbers, cube_positions, source):
+    """--pointnums=d2: the normals go to the cubes' occupied voxels, then the optimiser runs on the point-to-plane curves"""
+    from .pointnums import optimize_points_numbers, voxel_normals
+    vn = voxel_normals(source[0], source[1], cube_positions, args.scale, args.cube_size)
+    counts, rep = optimize_points_numbers(cubes, logits, points_numbers, metric="d2", normals=vn)
+    print("pointnums d2: chose {} {}; cube-local D2 mse {:.6g} -> {:.6g} (PSNR {:.4f} -> {:.4f} dB at peak 1023)".format(
+        rep["choice"][0], rep["choice"][1], rep["F_count"], rep["F_chosen"], rep["psnr_count"], rep["psnr_chosen"]))
+    return counts
+
+
 def _main_sharded(args, world):
     """One process per GPU (`python -m torch.distributed.run --nproc-per-node N -m pcgcv1_amd.test ...`): the cube
     list is split over the ranks (pcgcv1_amd/sharding.py), rank 0 reads and writes the files.  Same files as one GPU."""
@@ -90,7 +135,7 @@ def _main_sharded(args, world):
     if args.mode != "hyper":
         raise SystemExit("multi-GPU runs are implemented for --mode=hyper")
     if args.pointnums != "count":
-        raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 runs on one GPU)")
+        raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 and d2 run on one GPU)")
     rank = int(os.environ.get("RANK", "0"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     if not dist.is_initialized():
@@ -143,7 +188,9 @@ def main(argv=None):
         raise SystemExit("--gpu=0: this build runs the hot path on an MI355X only (no CPU fallback)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if (args.gpu > 1 or world > 1) and args.pointnums != "count":
-        raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 runs on one GPU)")
+        raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 and d2 run on one GPU)")
+    if args.estimate_normals and (args.command != "compress" or args.pointnums != "d2"):
+        raise SystemExit("--estimate_normals belongs to compress --pointnums=d2")
     if (args.gpu > 1 or world > 1) and args.colors_from:
         raise SystemExit("multi-GPU runs write geometry only (--colors_from runs on one GPU)")
     if args.colors_from and args.command != "decompress":
@@ -188,14 +235,19 @@ def main(argv=None):
         if coded_colors:                          # before any GPU work: a ply without colours is refused by name
             from .recolor import load_source
             src_points, src_colors = load_source(args.input)
+        optimised = args.pointnums != "count"
+        if args.pointnums == "d2":                # likewise: a ply without normals is refused before any GPU work
+            source = _load_normals(args)
         cubes, cube_positions, points_numbers = preprocess(args.input, args.scale, args.cube_size, args.min_num)
         logits = None
         if args.mode == "factorized":
             strings, min_v, max_v, shape = compress_factorized(cubes, model, args.ckpt_dir, verbose=True)
-            if args.pointnums == "d1" or coded_colors:           # the decoder's logits: decode the strings as decompress does
+            if optimised or coded_colors:                        # the decoder's logits: decode the strings as decompress does
                 logits = decompress_factorized(strings, min_v, max_v, shape, model, args.ckpt_dir)
             if args.pointnums == "d1":
                 points_numbers = _d1_counts(cubes, logits, points_numbers)
+            elif args.pointnums == "d2":
+                points_numbers = _d2_counts(args, cubes, logits, points_numbers, cube_positions, source)
             bs.write_binary_files_factorized(args.output, strings, points_numbers, cube_positions, min_v, max_v, shape,
                                              rootdir='./compressed')
         else:
@@ -210,11 +262,13 @@ def main(argv=None):
                 time.sleep(0.003)
                 return bs.encode_cube_positions(cube_positions)
             cubepos = _lib.workers("job").submit(_cubepos)
-            if args.pointnums == "d1" or coded_colors:           # the encoder-side reconstruction is what the decoder will compute
+            if optimised or coded_colors:                        # the encoder-side reconstruction is what the decoder will compute
                 out = compress_hyper(cubes, model, args.ckpt_dir, decompress=True, verbose=stage_times)
                 logits = out[8]
                 if args.pointnums == "d1":
                     points_numbers = _d1_counts(cubes, logits, points_numbers)
+                elif args.pointnums == "d2":
+                    points_numbers = _d2_counts(args, cubes, logits, points_numbers, cube_positions, source)
                 out = out[:8]
             else:
                 out = compress_hyper(cubes, model, args.ckpt_dir, verbose=stage_times)

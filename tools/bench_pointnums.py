@@ -1,6 +1,8 @@
 """Time the encoder-side point-count search (csrc/pointnums.hip) on the synthetic cloud's 205 cubes under the a6 checkpoint:
 the curves (pointnums.distortion_curves), the sweep + ladder (pointnums.sweep_curves) and the whole
-optimize_points_numbers, host clock after a synchronise, after warm-up, median and min of --reps runs.
+optimize_points_numbers, host clock after a synchronise, after warm-up, median and min of --reps runs; then the same for the
+point-to-plane curves (--pointnums d2: voxel_normals, distortion_curves_d2, optimize_points_numbers(metric="d2")) with the
+normals of metrics.estimate_normals(points, 10, 20), in the same run.
 
     python tools/bench_pointnums.py [--reps 10] [--warmup 2] [--out FILE]
 
@@ -25,7 +27,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from pcgcv1_amd import pointnums as pn, synthetic
+    from pcgcv1_amd import metrics, pointnums as pn, synthetic
     from pcgcv1_amd.models import model_voxception as model
     from pcgcv1_amd.process import preprocess_points
     from pcgcv1_amd.transform import compress_hyper
@@ -63,6 +65,20 @@ def main():
     res["choice"] = list(rep["choice"])
     res["local_psnr_count_db"] = round(rep["psnr_count"], 4)
     res["local_psnr_chosen_db"] = round(rep["psnr_chosen"], 4)
+    normals = metrics.estimate_normals(pts, 10, 20)
+    vn = pn.voxel_normals(pts, normals, pos, 1.0, 64)
+    torch.cuda.synchronize()
+    d2 = {"voxel_normals": timed(lambda: pn.voxel_normals(pts, normals, pos, 1.0, 64)),
+          "curves": timed(lambda: pn.distortion_curves_d2(cubes, logits, nums, vn)),
+          "optimize_points_numbers": timed(lambda: pn.optimize_points_numbers(cubes, logits, nums, metric="d2", normals=vn)),
+          # the same two searches as d1; a dot product and a square per ranked voxel, and per change of an occupied voxel's nearest
+          "distance_evals": res["distance_evals"], "plane_terms_B": int(p.n_seg.sum())}
+    counts2, rep2 = pn.optimize_points_numbers(cubes, logits, nums, metric="d2", normals=vn)
+    d2["choice"] = list(rep2["choice"])
+    d2["local_psnr_count_db"] = round(rep2["psnr_count"], 4)
+    d2["local_psnr_chosen_db"] = round(rep2["psnr_chosen"], 4)
+    d2["counts_sum"] = int(counts2.astype(np.int64).sum())
+    res["d2"] = d2
     line = json.dumps(res)
     print(line)
     if a.out:
