@@ -326,6 +326,22 @@ int pcgc_raht_dequantize(const int16_t* symbols, int64_t n, const int32_t* patch
 int pcgc_raht_abs_sums(const int32_t* q, const int32_t* order, const int32_t* subband, int64_t n, const int32_t* amax,
                        int64_t* sums, pcgc_stream_t stream);
 
+/* ---- Colour rate control (csrc/color_rc.hip; colorcodec.encode_colors_target; tests/_color_rc_ref.py) ------
+ * pcgc_raht_rate_sweep prices n_steps candidate steps (HOST double [n_steps], 1 <= n_steps <= 32, each positive and finite,
+ * else -1 and nothing is launched) in one pass over coef (float64 [M,3] as pcgc_raht_forward leaves it): for the rows
+ * k < k_raw of the subband order (the coded leaves) and q = rint(coef[order[k]][c] / steps[i]), pcgc_raht_quantize's expression,
+ *   abs_sums (device int64 [n_steps][37][3]) [i][subband][c] = sum of min(|q|, 2048)  — what pcgc_raht_abs_sums gives after
+ *   pcgc_raht_quantize at that step, since amax = min(max |q|, 2047);   max_abs (device int32 [n_steps][37]) [i][subband] =
+ *   max |q|.  Both are zeroed by the call.  Integers only: exact, the same on every run.
+ * pcgc_raht_requantize: out[j][c] = rint(coef[j][c] / step) * step for every row (quantise, then dequantise: escapes and the
+ * raw tail carry q exactly); out must not overlap coef.
+ * pcgc_color_sse6: two uint8 [M,3] colourings of the same points -> out (device int64 [6], zeroed by the call) = the sums of
+ * dr^2, dg^2, db^2, dr dg, dr db, dg db with d = a - b: the squared error of any linear colour transform follows from them. */
+int pcgc_raht_rate_sweep(const double* coef, const int32_t* order, const int32_t* subband, int64_t m, int64_t k_raw,
+                         const double* steps, int n_steps, int64_t* abs_sums, int32_t* max_abs, pcgc_stream_t stream);
+int pcgc_raht_requantize(const double* coef, int64_t m, double step, double* out, pcgc_stream_t stream);
+int pcgc_color_sse6(const uint8_t* rgb_a, const uint8_t* rgb_b, int64_t m, int64_t* out, pcgc_stream_t stream);
+
 /* ---- Chunked 64-way interleaved rANS, the entropy coder of colour stream version 2 (csrc/rans.hip; DESIGN.md 7d;
  * tests/_rans_ref.py is the rule in numpy) ---------------------------------------------------------------------------------
  * State uint32, lower bound 2^16, 16-bit words, 16-bit tables.  One wavefront per chunk; symbol j of a chunk belongs to lane

@@ -88,6 +88,9 @@ HIP_API = {
     "pcgc_raht_symbols": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pcgc_raht_dequantize": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp]),
     "pcgc_raht_abs_sums": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pcgc_raht_rate_sweep": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "pcgc_raht_requantize": (c_int, [c_vp, c_i64, ctypes.c_double, c_vp, c_vp]),
+    "pcgc_color_sse6": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "pcgc_rans_workspace_bytes": (c_sz, [c_i64, c_int]),
     "pcgc_rans_encode": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_rans_decode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),

@@ -40,6 +40,7 @@ HIP_SOURCES = {
     "color.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
+    "color_rc.hip": ["-ffp-contract=off"],
 }
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
              "-fno-gpu-rdc"]

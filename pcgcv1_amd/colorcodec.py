@@ -3,6 +3,8 @@
     data = encode_colors(points, colors, qstep)          # points int [M,3] unique voxels, colors uint8 [M,3]
     data = encode_colors(points, colors, qstep, coder="rans")            # stream version 2: the entropy coder runs on the GPU too
     colors = decode_colors(points, data)                 # uint8 [M,3] in the order of `points`; either version
+    data, report = encode_colors_target(points, colors, psnr=38)         # the step chosen on the grid 2^(j/8): at least 38 dB luma
+    data, report = encode_colors_target(points, colors, bpp=0.6)         # ... or at most 0.6 bits per point; an ordinary file either way
 
 The rule (tests/_raht_ref.py is its definition in numpy): YCoCg-R, the region-adaptive hierarchical transform
 over the Morton order of the voxels, q = rint(coef / qstep), range coding of q per subband (level, channel) with a two-sided
@@ -254,7 +256,7 @@ def unpack(data, d, m, level_counts):
     symbols = np.empty((k_raw, 3), np.int16)
     k = 0
     for l, (a, r0, r1, r2, nbytes) in enumerate(rows):
-        if at + nbytes > len(payload) or (counts[l] == 0) != (nbytes == 0):
+        if at + nbytes > len(payload) or (counts[l] == 0 and nbytes != 0):   # a level of zeros alone may take no bytes
             raise ValueError(".colors: the stream of level %d does not fit the file" % l)
         if counts[l]:
             symbols[k:k + counts[l]] = coder_ops.range_decode(payload[at:at + nbytes], (counts[l], 3), build_tables(a, [r0, r1, r2])[None])
@@ -345,7 +347,7 @@ def unpack_v2(data, d, m, level_counts):
     streams = []
     k = 0
     for l, (a, r0, r1, r2, kind, nbytes) in enumerate(rows):
-        if at + nbytes > len(payload) or (counts[l] == 0) != (nbytes == 0):
+        if at + nbytes > len(payload) or (counts[l] == 0 and nbytes != 0):   # a level of zeros alone may take no bytes
             raise ValueError(".colors: the stream of level %d does not fit the file (byte counts overrun the payload)" % l)
         if kind == CODER_RANS:
             streams.append(payload[at:at + nbytes])
@@ -703,6 +705,15 @@ def encode_colors(points, colors, qstep, fuse_top=True, timings=None, coder="ran
     _lib.check(lib.pcgc_raht_load_colors(_lib.dptr(rgb), _lib.dptr(plan.point_of_leaf), m, _lib.dptr(attr), s), "pcgc_raht_load_colors")
     plan.transform(attr, fuse_top=fuse_top)
     t = _clock(timings, "transform", t)
+    return _encode_coef(plan, attr, qstep, coder, timings, t)
+
+
+def _encode_coef(plan, attr, qstep, coder, timings, t):
+    """encode_colors from the coefficients on: quantiser, symbols, entropy coding, container (attr is left as it is, so the
+    rate control codes the same coefficients at one step after another)"""
+    import torch
+    lib = _lib.hip()
+    m, dev, s = plan.m, plan.dev, _lib.stream()
     q = torch.empty((m, 3), dtype=torch.int32, device=dev)
     maxabs_d = torch.empty(64, dtype=torch.int32, device=dev)
     _lib.check(lib.pcgc_raht_quantize(_lib.dptr(attr), _lib.dptr(plan.order), _lib.dptr(plan.subband), m, qstep, _lib.dptr(q),
@@ -768,3 +779,265 @@ def decode_colors(points, data, fuse_top=True, timings=None):
     if timings is not None:
         timings["launches"] = plan.launches
     return colors
+
+
+# ---------------------------------------------------------------------------------------------------------------- rate control
+# Targets are searched over a fixed grid of steps, so that the result is a discrete, reproducible choice: notch j stands for the
+# step 2^(j / 8), 0.25 .. 128 in 73 notches of about 9 %.  The chosen step goes into the header as every step does.
+QSTEP_GRID_MIN = -16
+QSTEP_GRID_MAX = 56
+SWEEP_MAX_STEPS = 32       # candidate steps one pcgc_raht_rate_sweep launch prices
+RAW_VALUE_BYTES = 3        # the estimate's price of one value of the raw tail (a zigzag varint of the top of the tree)
+# BT.709 of rgb (include/pcgc.h, pcgc_color_mse): the rows give Y, U, V
+_BT709 = np.array([[0.2126, 0.7152, 0.0722], [-0.1146, -0.3854, 0.5], [0.5, -0.4542, -0.0458]], np.float64)
+
+
+def grid_step(j):
+    """the quantiser step of notch j"""
+    return 2.0 ** (j / 8.0)
+
+
+def parse_target(text):
+    """'psnr:38' / 'bpp:0.6' -> ("psnr", 38.0) / ("bpp", 0.6); anything else is a ValueError that says what is wanted"""
+    kind, sep, number = str(text).partition(":")
+    try:
+        value = float(number)
+    except ValueError:
+        value = float("nan")
+    if not sep or kind not in ("psnr", "bpp") or not np.isfinite(value) or (kind == "bpp" and value <= 0):
+        raise ValueError("--color_target=%s: want psnr:<dB> (luma PSNR of the decoded colours, at least) or bpp:<bits per point> "
+                         "(size of the colour file, at most; positive)" % (text,))
+    return kind, value
+
+
+def yuv_mse(sums6, m):
+    """sse6's six sums over m points -> the mean squared errors of BT.709 Y, U and V of rgb / 255 (float64 [3]): with d the rgb
+    difference and w a row of the matrix, (w . d)^2 = sum_i w_i^2 d_i^2 + 2 sum_{i<k} w_i w_k d_i d_k"""
+    s = np.asarray(sums6, np.int64).astype(np.float64)
+    w = _BT709
+    sq = w[:, 0] ** 2 * s[0] + w[:, 1] ** 2 * s[1] + w[:, 2] ** 2 * s[2]
+    mixed = w[:, 0] * w[:, 1] * s[3] + w[:, 0] * w[:, 2] * s[4] + w[:, 1] * w[:, 2] * s[5]
+    return (sq + 2.0 * mixed) / (255.0 * 255.0 * float(m))
+
+
+def psnr_ceiling(m):
+    """The highest finite luma PSNR that m uint8 points can have, in dB: the BT.709 weights of Y are whole multiples of 0.0002
+    (1063, 3576 and 361 of them, with no common factor), so a luma error that is not 0 is at least 0.0002 of a level, and the
+    smallest squared error that is not 0 is that of one such point.  Above it there is only the infinite PSNR of no luma error at all."""
+    return float(10.0 * np.log10(255.0 * 255.0 * float(m) / (0.0002 * 0.0002)))
+
+
+def psnr_of_mse(mse):
+    """dB at peak 1 (the mse is of values / 255); an mse that is not positive (rounding of an exact 0 included) is infinite"""
+    return float("inf") if not mse > 0 else float(-10.0 * np.log10(mse))
+
+
+def ratios_of_sums(abs_sums, n):
+    """ratio_of_sum for arrays: abs_sums int [...], n the subband's size (broadcast) -> Q16 ratios int64 [...]"""
+    a = np.asarray(abs_sums, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(np.asarray(n) > 0, a / np.asarray(n, np.float64), 0.0)
+        r = np.where(mean > 0, (np.sqrt(1.0 + mean * mean) - 1.0) / mean, 0.0)
+    return np.clip(np.rint(r * 65536), 1, 65535).astype(np.int64)
+
+
+def estimate_bits(abs_sums, n):
+    """Bits of a subband of n values whose magnitudes add up to abs_sums, under the two-sided geometric table the encoder would
+    choose for it (ratio r): a value q costs -log2((1 - r) / (1 + r)) - |q| log2(r), linear in |q|, so the sum suffices.  The
+    table's 16-bit quantisation and the escapes are not priced.  Arrays broadcast; an empty subband costs nothing."""
+    a = np.asarray(abs_sums, np.float64)
+    n = np.asarray(n, np.float64)
+    r = ratios_of_sums(abs_sums, n) / 65536.0
+    return np.where(n > 0, n * -np.log2((1.0 - r) / (1.0 + r)) + a * -np.log2(r), 0.0)
+
+
+def estimate_bytes(level_counts, abs_sums, coder="range"):
+    """The size of the file encode_colors would write, from a sweep's sums: abs_sums int64 [K, 37, 3] -> float64 [K].  Header,
+    level rows, per coded level the bytes of estimate_bits over its three channels (rounded up), RAW_VALUE_BYTES per value of
+    the raw tail and, for coder="rans", a rANS level's chunk table entries and final states."""
+    counts = np.asarray(level_counts, np.int64)
+    n_coded = coded_levels(counts)
+    sums = np.asarray(abs_sums, np.int64).reshape(-1, 37, 3)[:, :n_coded]
+    bits = estimate_bits(sums, counts[None, :n_coded, None]).sum(-1)                      # [K, L]
+    fixed = HEADER_BYTES + (LEVEL_BYTES_RANS if coder == "rans" else LEVEL_BYTES) * n_coded
+    fixed += RAW_VALUE_BYTES * 3 * int(counts.sum() - counts[:n_coded].sum())
+    if coder == "rans":
+        per = RANS_LANES * RANS_STEPS
+        for l, kind in enumerate(level_coders(counts)):
+            if kind == CODER_RANS:
+                n = 3 * int(counts[l])
+                chunks = rans_chunk_count(n)
+                fixed += 4 * chunks + 4 * (RANS_LANES * (chunks - 1) + min(RANS_LANES, n - per * (chunks - 1)))
+    return fixed + np.ceil(bits / 8.0).sum(-1)
+
+
+class _Search:
+    """What both targets share: the tree, the colours and their coefficients on the device, and the three device-side tools —
+    the sweep, the closed-loop probe and the real encode from the same coefficients."""
+
+    def __init__(self, points, colors, timings=None):
+        import torch
+        lib = _lib.hip()
+        col = np.asarray(colors)
+        n = len(np.asarray(points))
+        if col.shape != (n, 3) or col.dtype != np.uint8:
+            raise ValueError("colour codec: colors must be uint8 [%d, 3] (got %s %s)" % (n, col.dtype, col.shape))
+        t = _start(timings)
+        self.plan = plan = Plan(points)
+        t = _clock(timings, "sort + structure", t)
+        m, dev, s = plan.m, plan.dev, _lib.stream()
+        self.rgb = torch.from_numpy(np.ascontiguousarray(col)).to(dev)
+        self.coef = torch.empty((m, 3), dtype=torch.float64, device=dev)
+        _lib.check(lib.pcgc_raht_load_colors(_lib.dptr(self.rgb), _lib.dptr(plan.point_of_leaf), m, _lib.dptr(self.coef), s), "pcgc_raht_load_colors")
+        plan.transform(self.coef)
+        _clock(timings, "transform", t)
+        self.n_coded = coded_levels(plan.level_counts)
+        self.k_raw = int(plan.level_counts[:self.n_coded].sum())
+        self.work = torch.empty_like(self.coef)
+        self.out = torch.empty((m, 3), dtype=torch.uint8, device=dev)
+        self.sums6 = torch.empty(6, dtype=torch.int64, device=dev)
+        self.timings = timings
+        self.probes = self.real_encodes = 0
+
+    def sweep(self, steps):
+        """-> (abs_sums int64 [K, 37, 3], max_abs int32 [K, 37]) of the K steps, SWEEP_MAX_STEPS per launch"""
+        import torch
+        lib, plan = _lib.hip(), self.plan
+        steps = np.ascontiguousarray(steps, np.float64).reshape(-1)
+        if len(steps) == 0 or not (np.isfinite(steps) & (steps > 0)).all():
+            raise ValueError("colour codec: the sweep wants at least one step, all positive numbers (got %r)" % (steps,))
+        t = _start(self.timings)
+        sums = torch.empty((len(steps), 37, 3), dtype=torch.int64, device=plan.dev)
+        tops = torch.empty((len(steps), 37), dtype=torch.int32, device=plan.dev)
+        for k0 in range(0, len(steps), SWEEP_MAX_STEPS):
+            part = np.ascontiguousarray(steps[k0:k0 + SWEEP_MAX_STEPS])
+            _lib.check(lib.pcgc_raht_rate_sweep(_lib.dptr(self.coef), _lib.dptr(plan.order), _lib.dptr(plan.subband), plan.m, self.k_raw,
+                                                _lib.nptr(part), len(part), _lib.dptr(sums[k0:k0 + len(part)]), _lib.dptr(tops[k0:k0 + len(part)]),
+                                                _lib.stream()), "pcgc_raht_rate_sweep")
+        res = sums.cpu().numpy(), tops.cpu().numpy()
+        _clock(self.timings, "rate control: sweep", t)
+        return res
+
+    def probe(self, qstep):
+        """the closed loop at one step, on the device: the colours a decoder would write -> uint8 [M,3] device tensor (reused by
+        the next probe), in the order of the points"""
+        lib, plan, s = _lib.hip(), self.plan, _lib.stream()
+        _lib.check(lib.pcgc_raht_requantize(_lib.dptr(self.coef), plan.m, _check_step(qstep), _lib.dptr(self.work), s), "pcgc_raht_requantize")
+        plan.transform(self.work, inverse=True)
+        _lib.check(lib.pcgc_raht_store_colors(_lib.dptr(self.work), _lib.dptr(plan.point_of_leaf), plan.m, _lib.dptr(self.out), s),
+                   "pcgc_raht_store_colors")
+        return self.out
+
+    def psnr_y(self, qstep):
+        """luma PSNR of the closed loop at one step: 48 bytes come back"""
+        t = _start(self.timings)
+        out = self.probe(qstep)
+        _lib.check(_lib.hip().pcgc_color_sse6(_lib.dptr(out), _lib.dptr(self.rgb), self.plan.m, _lib.dptr(self.sums6), _lib.stream()), "pcgc_color_sse6")
+        y = psnr_of_mse(yuv_mse(self.sums6.cpu().numpy(), self.plan.m)[0])
+        self.probes += 1
+        _clock(self.timings, "rate control: probes", t)
+        return y
+
+    def encode(self, qstep, coder):
+        t = _start(self.timings)
+        data = _encode_coef(self.plan, self.coef, _check_step(qstep), coder, None, 0.0)
+        self.real_encodes += 1
+        _clock(self.timings, "rate control: real encodes", t)
+        return data
+
+
+def rate_sweep(points, colors, steps):
+    """pcgc_raht_rate_sweep on its own: for every step, what a real encode at that step would hand its tables — abs_sums int64
+    [K, 37, 3] (per subband and channel, the sum of min(|q|, 2048) over the coded levels) and max_abs int32 [K, 37]"""
+    return _Search(points, colors).sweep(steps)
+
+
+def probe_colors(points, colors, qstep):
+    """the closed loop of the PSNR search on its own: uint8 [M,3], what decode_colors gives for encode_colors at that step"""
+    return _Search(points, colors).probe(qstep).cpu().numpy()
+
+
+def sse6(rgb_a, rgb_b):
+    """two uint8 [M,3] colourings of the same points -> int64 [6]: the sums of dr^2, dg^2, db^2, dr dg, dr db, dg db (yuv_mse turns
+    them into the squared error of Y, U and V)"""
+    import torch
+    dev = _lib.require_gpu()
+    a, b = np.asarray(rgb_a), np.asarray(rgb_b)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape or a.dtype != np.uint8 or b.dtype != np.uint8 or len(a) == 0:
+        raise ValueError("sse6: two uint8 arrays [M, 3] of one shape, M > 0 (got %s %s and %s %s)" % (a.dtype, a.shape, b.dtype, b.shape))
+    a_d, b_d = torch.from_numpy(np.ascontiguousarray(a)).to(dev), torch.from_numpy(np.ascontiguousarray(b)).to(dev)
+    out = torch.empty(6, dtype=torch.int64, device=dev)
+    _lib.check(_lib.hip().pcgc_color_sse6(_lib.dptr(a_d), _lib.dptr(b_d), len(a), _lib.dptr(out), _lib.stream()), "pcgc_color_sse6")
+    return out.cpu().numpy()
+
+
+def encode_colors_target(points, colors, psnr=None, bpp=None, coder="range", timings=None):
+    """encode_colors with the step chosen on the grid 2^(j / 8), QSTEP_GRID_MIN <= j <= QSTEP_GRID_MAX -> (data, report).
+    psnr: the luma (BT.709 Y, peak 255) PSNR in dB of the decoded colours against `colors`, at least: the result has
+    psnr_y(j) >= psnr and j == QSTEP_GRID_MAX or psnr_y(j + 1) < psnr.  bpp: 8 len(data) / len(points), the whole file, at most:
+    len(data(j)) <= budget and j == QSTEP_GRID_MIN or len(data(j - 1)) > budget.  A target the grid cannot reach is a ValueError
+    that names what it can; so is a psnr above psnr_ceiling(M), which no file of M points with any luma error at all can have
+    (on uint8 colours the finest step decodes without error, so it never falls short: the ceiling is what is out of reach).
+    report: j, qstep, psnr_y, bytes, bpp, probes, real_encodes (and est_bytes, j_est with bpp)."""
+    if (psnr is None) == (bpp is None):
+        raise ValueError("colour codec: give exactly one target, psnr (dB) or bpp (bits per point)")
+    if coder not in ("range", "rans"):
+        raise ValueError("colour codec: coder must be 'range' or 'rans' (got %r)" % (coder,))
+    target = float(psnr if bpp is None else bpp)
+    if np.isnan(target) or (bpp is not None and not (target > 0)):
+        raise ValueError("colour codec: the target must be a number, a bpp positive (got %r)" % (target,))
+    search = _Search(points, colors, timings)
+    report = {}
+    if bpp is None:
+        seen = {}
+
+        def reached(j):
+            if j not in seen:
+                seen[j] = search.psnr_y(grid_step(j))
+            return seen[j] >= target
+
+        lo, hi = QSTEP_GRID_MIN, QSTEP_GRID_MAX
+        if not reached(lo):
+            raise ValueError("colour codec: a luma PSNR of %g dB is out of reach: the finest step, %g, gives %.4f dB" % (target, grid_step(lo), seen[lo]))
+        if target > psnr_ceiling(search.plan.m):         # met by a file without luma error alone: not a PSNR to search for
+            raise ValueError("colour codec: a luma PSNR of %g dB is out of reach: no decoded file of %d points has a finite PSNR above %.4f dB "
+                             "(the finest step, %g, gives %s dB)" % (target, search.plan.m, psnr_ceiling(search.plan.m), grid_step(lo),
+                                                                     "%.4f" % seen[lo] if np.isfinite(seen[lo]) else "no luma error at all, inf"))
+        if reached(hi):
+            lo = hi
+        while hi - lo > 1:                               # reached(lo) and not reached(hi)
+            mid = (lo + hi) // 2
+            if reached(mid):
+                lo = mid
+            else:
+                hi = mid
+        j = lo
+        data = search.encode(grid_step(j), coder)
+        y = seen[j]
+    else:
+        budget = int(np.floor(target * search.plan.m / 8.0 + 1e-6))
+        steps = [grid_step(j) for j in range(QSTEP_GRID_MIN, QSTEP_GRID_MAX + 1)]
+        est = estimate_bytes(search.plan.level_counts, search.sweep(steps)[0], coder)
+        fits = np.flatnonzero(est <= budget)
+        j = j_est = QSTEP_GRID_MIN + int(fits[0]) if len(fits) else QSTEP_GRID_MAX
+        data = search.encode(grid_step(j), coder)
+        if len(data) <= budget:
+            while j > QSTEP_GRID_MIN:
+                finer = search.encode(grid_step(j - 1), coder)
+                if len(finer) > budget:
+                    break
+                j, data = j - 1, finer
+        else:
+            while len(data) > budget:
+                if j == QSTEP_GRID_MAX:
+                    raise ValueError("colour codec: %g bits per point (%d bytes) is out of reach: the coarsest step, %g, takes %d bytes"
+                                     % (target, budget, grid_step(j), len(data)))
+                j += 1
+                data = search.encode(grid_step(j), coder)
+        y = search.psnr_y(grid_step(j))
+        report.update(est_bytes=float(est[j - QSTEP_GRID_MIN]), j_est=j_est)
+    report.update(j=j, qstep=grid_step(j), psnr_y=y, bytes=len(data), bpp=8.0 * len(data) / search.plan.m, probes=search.probes,
+                  real_encodes=search.real_encodes)
+    if timings is not None:
+        timings["launches"] = search.plan.launches
+    return data, report

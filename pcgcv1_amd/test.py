@@ -5,7 +5,8 @@
 
 compress writes ./compressed/<basename>.{strings,strings_head,strings_hyper,pointnums,cubepos};
 decompress writes <name>_rec.ply.  compress --colors=raht --color_qstep=Q (a coloured ply) adds <basename>.colors, the colours
-of the decoded points (pcgcv1_amd/colorcodec.py); decompress finds that file and writes a coloured ply.  --ckpt_dir additionally accepts "synthetic[:seed[:profile]]"
+of the decoded points (pcgcv1_amd/colorcodec.py); decompress finds that file and writes a coloured ply;
+--color_target=psnr:38 or bpp:0.6 instead of --color_qstep lets the encoder choose the step for a luma PSNR or a size.  --ckpt_dir additionally accepts "synthetic[:seed[:profile]]"
 (checkpoint.py).  --gpu=0 is rejected: this build has no CPU path; --gpu=N shards the cubes over N GPUs
 (one rank per GPU over RCCL, pcgcv1_amd/sharding.py; same files as one GPU).
 """
@@ -39,6 +40,9 @@ _FLAGS = [
     ("color_qstep", float, 4.0, "quantiser step of --colors=raht (all three YCoCg channels); larger = fewer bits"),
     ("color_coder", str, "range", "entropy coder of --colors=raht: 'range' = stream version 1 (the host's range coder); 'rans' = version "
                                   "2, chunked interleaved rANS coded and decoded on the GPU.  decompress reads either"),
+    ("color_target", str, "", "rate control of --colors=raht instead of --color_qstep: 'psnr:38' = the largest step of the grid "
+                              "2^(j/8) whose decoded luma (BT.709 Y) PSNR is at least 38 dB; 'bpp:0.6' = the smallest step whose "
+                              "<name>.colors holds at most 0.6 bits per input point.  Empty: --color_qstep as given"),
 ]
 
 
@@ -55,6 +59,16 @@ def parse_args(argv=None):
     ap.add_argument("--estimate_normals", action="store_true",
                     help="compress --pointnums=d2 with a ply that has no normals: estimate them (radius 10, 20 neighbours, as eval does)")
     args = ap.parse_args(argv)
+    if args.color_target:                                  # with the other argument errors, before anything is loaded
+        from .colorcodec import parse_target
+        try:
+            parse_target(args.color_target)
+        except ValueError as e:
+            ap.error(str(e))
+        if args.colors != "raht":
+            ap.error("--color_target=%s steers the quantiser of --colors=raht: give both" % args.color_target)
+        if args.color_qstep != ap.get_default("color_qstep"):
+            ap.error("--color_target=%s chooses the step itself: leave --color_qstep=%g out" % (args.color_target, args.color_qstep))
     if args.command == "compress" and args.pointnums == "d2" and not args.estimate_normals and not _ply_has_normals(args.input):
         # with the other argument errors, before anything is loaded: d2 has nothing to measure against without normals
         ap.error("--pointnums=d2 needs normals: %s has no nx ny nz properties (or cannot be read); write them into the ply, or "
@@ -335,8 +349,20 @@ def _write_colors(args, logits, points_numbers, cube_positions, src_points, src_
     from .recolor import recolor
     t0 = time.time()
     pts = np.asarray(postprocess_points(logits, points_numbers, cube_positions, 1, args.cube_size, 1)).astype(np.int32)
-    data = encode_colors(pts, recolor(src_points, src_colors, pts), args.color_qstep, coder=args.color_coder)
     name = os.path.join("./compressed", args.output + ".colors")
+    if args.color_target:
+        from .colorcodec import encode_colors_target, parse_target
+        kind, value = parse_target(args.color_target)
+        if kind == "bpp":                         # per INPUT point here, as the geometry's bpp; the codec counts the points it codes
+            value = value * len(src_points) / len(pts)
+        data, rep = encode_colors_target(pts, recolor(src_points, src_colors, pts), coder=args.color_coder, **{kind: value})
+        write_colors_file(name, data)
+        print("colors raht, target {}: color_qstep {:g} (grid notch {}), luma PSNR {:.4f} dB, {} bytes ({:.4f} bits per input point{}), "
+              "{} probes, {} real encodes, for {} decoded points -> {}: {}s".format(
+                  args.color_target, rep["qstep"], rep["j"], rep["psnr_y"], len(data), 8.0 * len(data) / len(src_points),
+                  ", rANS" if args.color_coder == "rans" else "", rep["probes"], rep["real_encodes"], len(pts), name, round(time.time() - t0, 4)))
+        return
+    data = encode_colors(pts, recolor(src_points, src_colors, pts), args.color_qstep, coder=args.color_coder)
     write_colors_file(name, data)
     print("colors raht: {} bytes ({:.4f} bits per input point, color_qstep {:g}{}) for {} decoded points -> {}: {}s".format(
         len(data), 8.0 * len(data) / len(src_points), args.color_qstep, ", rANS" if args.color_coder == "rans" else "", len(pts), name,

@@ -2,7 +2,7 @@
 bench cloud (828 225 points, 205 cubes, a6 checkpoint) with a textured colour field, and measure the entropy layer against the
 numpy reference's empirical entropy on the rate test's cloud.
 
-    python tools/bench_colorcodec.py [--reps 20] [--warmup 3] [--out-dir profiles] [--coder range|rans|both]
+    python tools/bench_colorcodec.py [--reps 20] [--warmup 3] [--out-dir profiles] [--coder range|rans|both] [--target]
 
 Writes <out-dir>/colorcodec_bench.txt (encode / decode split into stages, median of --reps after warm-up, every stage ended by a
 device synchronise; launches per direction with and without the fused tree top; tests/_raht_ref.py on the host as baseline) and
@@ -11,6 +11,9 @@ device synchronise; launches per direction with and without the fused tree top; 
 (the same stages for the chosen coders, interleaved in one loop of one process, and the format constants' alternatives) and
 <out-dir>/colorcodec_rans_rd.txt (bytes of both versions at the six steps on both clouds, version 2's overhead split into
 states, chunk table and range-coded levels, bits / H on the test cloud) and leaves the two version 1 files alone.
+--target (the rate control: csrc/color_rc.hip, colorcodec.encode_colors_target) writes <out-dir>/colorcodec_rc.txt alone: the time of
+one sweep launch of 32 steps and of one PSNR probe, encode_colors_target in both modes against a plain encode_colors at the step it
+chose (taking turns inside one loop of one process), and the size estimate against real files on both clouds.
 Needs an MI355X: there is no host path to time."""
 import argparse
 import os
@@ -137,6 +140,105 @@ def rans_report(a, ref, cc, rc, synthetic, model, postprocess_points, preprocess
     print("\n".join(out))
 
 
+def target_report(a, cc, rc, synthetic, model, postprocess_points, preprocess_points, compress_hyper):
+    import torch
+    from pcgcv1_amd import _lib
+    pts = synthetic.make_cloud(seed=5, res=128, n_shells=3, rmin=0.2, rmax=0.4).astype(np.int32)
+    col = textured(pts, 128, 10, 5)
+    src = synthetic.make_cloud(1300).astype(np.int32)
+    src_col = textured(src, 1024, 10, 1300)
+    cubes, pos, nums = preprocess_points(src, 1.0, 64, 64)
+    logits = compress_hyper(cubes, model, a.ckpt, decompress=True)[8]
+    rec = np.unique(np.rint(postprocess_points(logits, nums, pos, 1.0, 64, 1.0, None)).astype(np.int32), axis=0)
+    rec_col = rc.recolor(src, src_col, rec)
+    clouds = (("test cloud (tests/test_gpu_colorcodec.py::_coloured_cloud, %d points)" % len(pts), pts, col),
+              ("bench cloud (synthetic.make_cloud(1300) decoded with the a6 checkpoint, %d points), textured colours (sigma 10)" % len(rec), rec, rec_col))
+    med = lambda x: 1e3 * float(np.median(x))                             # noqa: E731
+    out = ["RAHT colour codec, rate control (tools/bench_colorcodec.py --target): times on the bench cloud's decoded geometry (%d points), ms," % len(rec),
+           "median of %d runs after %d warm-up runs in one process" % (a.reps, a.warmup), ""]
+
+    # ---- the kernels: one sweep launch of 32 steps (device events around the call), the sweep with its read-back, one probe
+    search = cc._Search(rec, rec_col)
+    lib, plan = _lib.hip(), search.plan
+    steps = np.array([cc.grid_step(j) for j in range(cc.QSTEP_GRID_MIN, cc.QSTEP_GRID_MIN + 32)])
+    sums = torch.empty((32, 37, 3), dtype=torch.int64, device=plan.dev)
+    tops = torch.empty((32, 37), dtype=torch.int32, device=plan.dev)
+    t_launch, t_sweep, t_grid, t_probe = [], [], [], []
+    grid = [cc.grid_step(j) for j in range(cc.QSTEP_GRID_MIN, cc.QSTEP_GRID_MAX + 1)]
+    for i in range(a.warmup + a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _lib.check(lib.pcgc_raht_rate_sweep(_lib.dptr(search.coef), _lib.dptr(plan.order), _lib.dptr(plan.subband), plan.m, search.k_raw,
+                                            _lib.nptr(steps), 32, _lib.dptr(sums), _lib.dptr(tops), _lib.stream()), "pcgc_raht_rate_sweep")
+        e1.record()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        search.sweep(steps)
+        t1 = time.perf_counter()
+        search.sweep(grid)
+        t2 = time.perf_counter()
+        search.psnr_y(4.0)
+        t3 = time.perf_counter()
+        if i >= a.warmup:
+            t_launch.append(e0.elapsed_time(e1) / 1e3)
+            t_sweep.append(t1 - t0)
+            t_grid.append(t2 - t1)
+            t_probe.append(t3 - t2)
+    out.append("pcgc_raht_rate_sweep, 32 steps, one launch with its two memsets (device events): %.3f" % med(t_launch))
+    out.append("the same with the read-back of the sums (host clock): %.3f;  all 73 steps, three launches and the read-back: %.3f" % (med(t_sweep), med(t_grid)))
+    out.append("one PSNR probe (requantise, inverse transform, store colours, six sums, 48 bytes back; host clock): %.3f" % med(t_probe))
+    out.append("")
+
+    # ---- the whole search against a plain encode at the step it chose, taking turns
+    for coder in ("range", "rans"):
+        for kw in ({"psnr": 38.0}, {"bpp": 0.6}):
+            rep = cc.encode_colors_target(rec, rec_col, coder=coder, **kw)[1]
+            t_target, t_plain, stages = [], [], []
+            for i in range(a.warmup + a.reps):
+                tm = {}
+                t0 = time.perf_counter()
+                cc.encode_colors_target(rec, rec_col, coder=coder, timings=tm, **kw)
+                t1 = time.perf_counter()
+                cc.encode_colors(rec, rec_col, rep["qstep"], coder=coder)
+                t2 = time.perf_counter()
+                if i >= a.warmup:
+                    t_target.append(t1 - t0)
+                    t_plain.append(t2 - t1)
+                    stages.append(tm)
+            name = "psnr:%g" % kw["psnr"] if "psnr" in kw else "bpp:%g" % kw["bpp"]
+            out.append("%-5s %-8s encode_colors_target %.3f | plain encode_colors at its step %.3f | ratio %.2f | notch %d, step %.4f, luma PSNR %.4f dB, %d bytes, "
+                       "%d probes, %d real encodes%s" % (coder, name, med(t_target), med(t_plain), med(t_target) / med(t_plain), rep["j"], rep["qstep"],
+                                                          rep["psnr_y"], rep["bytes"], rep["probes"], rep["real_encodes"],
+                                                          ", estimate %.0f bytes at notch %d" % (rep["est_bytes"], rep["j_est"]) if "j_est" in rep else ""))
+            out.append("        inside (each stage ended by its own synchronise, so the parts add up to more than the untimed call): %s" % "; ".join(
+                "%s %.3f" % (k, med([x[k] for x in stages])) for k in sorted(stages[0]) if k != "launches"))
+    out.append("")
+
+    # ---- the estimate against real files
+    for title, p, c in clouds:
+        out.append(title)
+        search = cc._Search(p, c)
+        counts = search.plan.level_counts
+        fixed = (1.0, 4.0, 16.0, 64.0)
+        sw = search.sweep(fixed)[0]
+        for coder in ("range", "rans"):
+            est = cc.estimate_bytes(counts, sw, coder)
+            real = [len(cc.encode_colors(p, c, s, coder=coder)) for s in fixed]
+            out.append("  %-5s est / real bytes at steps 1, 4, 16, 64: %s" % (coder, "  ".join("%.4f (%d / %d)" % (e / r, e, r) for e, r in zip(est, real))))
+            cells = []
+            for bpp in (0.25, 0.5, 1.0, 2.0):
+                try:
+                    rep = cc.encode_colors_target(p, c, bpp=bpp, coder=coder)[1]
+                    cells.append("%g bpp: |%d - %d| = %d, %d real encodes" % (bpp, rep["j_est"], rep["j"], abs(rep["j_est"] - rep["j"]), rep["real_encodes"]))
+                except ValueError as e:
+                    cells.append("%g bpp: %s" % (bpp, e))
+            out.append("        |j_est - j|: %s" % ";  ".join(cells))
+        out.append("")
+    with open(os.path.join(a.out_dir, "colorcodec_rc.txt"), "w") as f:
+        f.write("\n".join(out) + "\n")
+    print("\n".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -145,6 +247,7 @@ def main():
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--coder", choices=("range", "rans", "both"), default="range",
                     help="entropy coder(s) of the colour stream to measure: range = version 1, rans = version 2, both = side by side")
+    ap.add_argument("--target", action="store_true", help="measure the rate control (encode_colors_target) and write colorcodec_rc.txt alone")
     a = ap.parse_args()
     import _raht_ref as ref
     from pcgcv1_amd import _lib, metrics, synthetic
@@ -155,6 +258,8 @@ def main():
     from pcgcv1_amd.transform import compress_hyper
     _lib.require_gpu()
     os.makedirs(a.out_dir, exist_ok=True)
+    if a.target:
+        return target_report(a, cc, rc, synthetic, model, postprocess_points, preprocess_points, compress_hyper)
     if a.coder != "range":
         return rans_report(a, ref, cc, rc, synthetic, model, postprocess_points, preprocess_points, compress_hyper)
 
