@@ -35,7 +35,13 @@ levels' whole payload.
     36  14 L  per coded level: amax u16, ratio[Y, Co, Cg] u16 (Q16), coder u16 (0 = range, 1 = rANS), stream bytes u32
     then, for the rANS levels in level order, one u32 per chunk: the chunk's bytes (ceil(3 leaves / (64 RANS_STEPS)) chunks per
     level; they add up to the level's stream bytes), then the L streams, the escapes and the raw tail as in version 1.
+
+In the code the two versions are one format: a version 1 file is a file whose levels are all range coded.  _FORMATS says what a
+version decides (the level row, and whether it names a coder and a chunk table follows); _write lays out and _read checks and
+reads either version (pack / assemble_v2 and unpack / unpack_v2 are their callers); _encode_coef and decode_colors code every
+level with the coder level_coders gives it, from the same device-side sums, tables and escapes.
 """
+import itertools
 import struct
 
 import numpy as np
@@ -44,11 +50,14 @@ from . import _lib
 
 MAGIC = b"PCRA"
 VERSION = 1
-HEADER_BYTES = 36
-LEVEL_BYTES = 12
 VERSION_RANS = 2           # the stream version coder="rans" writes
-LEVEL_BYTES_RANS = 14
+HEADER_BYTES = 36
 CODER_RANGE, CODER_RANS = 0, 1
+# all that a stream version decides: the layout of a level row and whether the rows name a coder (then rANS levels exist and
+# their chunk table follows the rows; without the field every level is range coded)
+_FORMATS = {VERSION: (struct.Struct("<HHHHI"), False), VERSION_RANS: (struct.Struct("<HHHHHI"), True)}
+_VERSION_OF = {"range": VERSION, "rans": VERSION_RANS}
+LEVEL_BYTES, LEVEL_BYTES_RANS = _FORMATS[VERSION][0].size, _FORMATS[VERSION_RANS][0].size          # 12, 14
 RANS_LANES = 64
 # format constants of version 2, confirmed from profiles/colorcodec_rans_rd.txt (bytes of the alternatives on both clouds) and
 # profiles/colorcodec_rans_bench.txt (times at S = 512 ... 4096); DESIGN.md 7d gives the reasoning
@@ -58,6 +67,8 @@ RANS_LOW = 1 << 16         # L: the lower bound of a lane's state, and its value
 RAW_LEAVES = 48            # the top of the tree, at most this many leaves (DC included), is stored raw
 AMAX_CAP = 2047            # largest |q| with a symbol of its own; larger values take the escape symbol
 MAX_COORD = 4095           # 12-bit clouds, as recolor
+SUBBANDS = 37              # subbands of a 12-bit cloud, the DC included: 3 * 12 + 1 (kBins in the kernels)
+LEVEL_SLOTS = 64           # entries of the per-level int32 device buffers (amax, max |q|): SUBBANDS and room to spare
 
 
 # ---------------------------------------------------------------------------------------------------------------- colour space
@@ -103,18 +114,25 @@ def build_tables(amax, ratios):
     return cdf.astype(np.int32)
 
 
-def choose_ratio(abs_hist):
-    """Q16 ratio of the geometric table for a subband with abs_hist[k] values of magnitude k: the moment fit
-    E|q| = 2 r / (1 - r^2).  The encoder's choice only: the decoder reads the 16 bits."""
-    return ratio_of_sum(int((abs_hist * np.arange(len(abs_hist))).sum()), int(abs_hist.sum()))
+def ratios_of_sums(abs_sums, n):
+    """Q16 ratios of the geometric tables for subbands of n values (broadcast) whose magnitudes add up to abs_sums int [...]
+    (pcgc_raht_abs_sums) -> int64 [...]: the moment fit E|q| = 2 r / (1 - r^2).  The encoder's choice only: the decoder reads
+    the 16 bits."""
+    a = np.asarray(abs_sums, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(np.asarray(n) > 0, a / np.asarray(n, np.float64), 0.0)
+        r = np.where(mean > 0, (np.sqrt(1.0 + mean * mean) - 1.0) / mean, 0.0)
+    return np.clip(np.rint(r * 65536), 1, 65535).astype(np.int64)
 
 
 def ratio_of_sum(abs_sum, n):
-    """choose_ratio from the integer sum of the n magnitudes (pcgc_raht_abs_sums): the same double, the same ratio"""
-    n = float(n)
-    mean = float(abs_sum) / n if n else 0.0
-    r = (np.sqrt(1.0 + mean * mean) - 1.0) / mean if mean > 0 else 0.0
-    return int(min(65535, max(1, int(round(r * 65536)))))
+    """ratios_of_sums for one subband -> int"""
+    return int(ratios_of_sums(abs_sum, n))
+
+
+def choose_ratio(abs_hist):
+    """ratio_of_sum for a subband with abs_hist[k] values of magnitude k"""
+    return ratio_of_sum(int((abs_hist * np.arange(len(abs_hist))).sum()), int(abs_hist.sum()))
 
 
 # ---------------------------------------------------------------------------------------------------------------- container
@@ -173,61 +191,73 @@ def _geometry_crc(counts):
     return _crc(np.asarray(counts, "<i8").tobytes())
 
 
-def pack(d, m, qstep, level_counts, amax, symbols, tail, esc_pos=(), esc_val=()):
-    """The file's bytes.  level_counts [3d + 1] leaves per subband; amax [L] alphabet half-widths of the coded levels; symbols
-    int16 [K,3] of the K leaves of the coded levels in subband order (q + amax, or 2 amax + 1 = escape); tail int [M - K, 3]
-    = q of the raw leaves; esc_pos / esc_val: positions k * 3 + c (ascending) and values of the escaped q."""
-    from . import coder_ops
+def _row_base(counts, n_coded):
+    """int64 [n_coded + 1]: the first row of every coded level in the [K,3] symbol array, and K"""
+    return np.concatenate([[0], np.cumsum(counts[:n_coded], dtype=np.int64)]).astype(np.int64)
+
+
+def rans_chunk_count(n_symbols, steps=None):
+    """chunks of a level of n_symbols symbols"""
+    per = RANS_LANES * (RANS_STEPS if steps is None else steps)
+    return -(-int(n_symbols) // per)
+
+
+def level_coders(level_counts, version=VERSION_RANS):
+    """the coder of every coded level: rANS from RANS_MIN_SYMBOLS symbols on where the version has it, else the range coder"""
+    counts = [int(c) for c in level_counts]
+    rans = _FORMATS[version][1]
+    return [CODER_RANS if rans and 3 * c >= RANS_MIN_SYMBOLS else CODER_RANGE for c in counts[:coded_levels(counts)]]
+
+
+def _write(version, d, m, qstep, level_counts, amax, ratios, streams, chunk_sizes, tail, esc_pos, esc_val, what="streams"):
+    """The file's bytes, either version.  level_counts [3d + 1] leaves per subband; per coded level amax[l], ratios[l] [3], streams[l]
+    = its bytes from the coder level_coders names and chunk_sizes[l] = the bytes of each of its chunks (rANS levels; anything
+    empty otherwise); tail int [M - K, 3] = q of the raw leaves; esc_pos / esc_val: positions k * 3 + c (ascending) and values of
+    the escaped q."""
+    row, names_coder = _FORMATS[version]
     counts = [int(c) for c in level_counts]
     n_coded = coded_levels(counts)
-    k_raw = sum(counts[:n_coded])
-    symbols = np.ascontiguousarray(symbols, np.int16).reshape(-1, 3)
+    kinds = level_coders(counts, version)
     tail = np.asarray(tail, np.int64).reshape(-1, 3)
-    if len(counts) != 3 * d + 1 or sum(counts) != m or len(symbols) != k_raw or len(tail) != m - k_raw or len(amax) != n_coded:
-        raise ValueError("colour container: the symbols do not fit the level counts")
-    table, streams = [], []
-    at = 0
+    if len(counts) != 3 * d + 1 or sum(counts) != m or len(tail) != m - sum(counts[:n_coded]) or not (
+            len(amax) == len(ratios) == len(streams) == len(chunk_sizes) == n_coded):
+        raise ValueError("colour container: the %s do not fit the level counts" % what)
+    table, chunk_table = [], []
     for l in range(n_coded):
-        s = symbols[at:at + counts[l]]
-        at += counts[l]
-        a = int(amax[l])
-        ratios = [choose_ratio(np.bincount(np.abs(s[:, c].astype(np.int64) - a).clip(max=a + 1), minlength=a + 2)) for c in range(3)]
-        stream = coder_ops.range_encode(s, build_tables(a, ratios)[None]) if len(s) else b""
-        table.append(struct.pack("<HHHHI", a, ratios[0], ratios[1], ratios[2], len(stream)))
-        streams.append(stream)
+        if kinds[l] == CODER_RANS:
+            sizes = np.asarray(chunk_sizes[l], np.int64).reshape(-1)
+            if len(sizes) != rans_chunk_count(3 * counts[l]) or int(sizes.sum()) != len(streams[l]):
+                raise ValueError("colour container: the chunks of level %d do not fit its stream" % l)
+            chunk_table.append(sizes.astype("<u4").tobytes())
+        table.append(row.pack(int(amax[l]), *(int(r) for r in ratios[l]), *([kinds[l]] if names_coder else []), len(streams[l])))
     esc_pos = np.asarray(esc_pos, np.int64).reshape(-1)
     esc = np.stack([np.diff(esc_pos, prepend=0), _zigzag(esc_val)], -1) if len(esc_pos) else np.zeros((0, 2), np.int64)
-    payload = b"".join(table) + b"".join(streams) + _put_varints(esc) + _put_varints(_zigzag(tail))
-    head = MAGIC + struct.pack("<BBHQdIII", VERSION, d, n_coded, m, float(qstep), _crc(payload), len(esc_pos), _geometry_crc(counts))
+    payload = b"".join(table) + b"".join(chunk_table) + b"".join(bytes(x) for x in streams) + _put_varints(esc) + _put_varints(_zigzag(tail))
+    head = MAGIC + struct.pack("<BBHQdIII", version, d, n_coded, m, float(qstep), _crc(payload), len(esc_pos), _geometry_crc(counts))
     return head + payload
 
 
-def _read_header(data, d, m, level_counts, want_version, level_bytes):
-    """the checks both versions share -> (counts, n_coded, qstep, n_esc, payload)"""
-    data = bytes(data)
-    if len(data) < HEADER_BYTES:
-        raise ValueError(".colors: %d bytes, shorter than its %d-byte header (truncated file)" % (len(data), HEADER_BYTES))
-    if data[:4] != MAGIC:
-        raise ValueError(".colors: wrong magic %r (want %r): not a colour stream" % (data[:4], MAGIC))
-    version, fd, n_coded, fm, qstep, crc, n_esc, gcrc = struct.unpack("<BBHQdIII", data[4:HEADER_BYTES])
-    if version != want_version:
-        raise ValueError(".colors: version %d, this decoder reads version %d" % (version, want_version))
-    if fd != d or fm != m:
-        raise ValueError(".colors was coded for other geometry: it holds d = %d, M = %d, the decoded points have d = %d, M = %d"
-                         % (fd, fm, d, m))
+def pack(d, m, qstep, level_counts, amax, symbols, tail, esc_pos=(), esc_val=()):
+    """The bytes of a version 1 file from symbols: _write's arguments, but symbols int16 [K,3] of the K leaves of the coded levels
+    in subband order (q + amax, or 2 amax + 1 = escape) for the streams; the tables are fitted to them here."""
+    from . import coder_ops
     counts = [int(c) for c in level_counts]
-    if n_coded != coded_levels(counts):
-        raise ValueError(".colors was coded for other geometry: %d coded levels, the decoded points give %d" % (n_coded, coded_levels(counts)))
-    if gcrc != _geometry_crc(counts):
-        raise ValueError(".colors was coded for other geometry: same d and M, but the octree of the decoded points has other level sizes")
-    if not (qstep > 0 and np.isfinite(qstep)):
-        raise ValueError(".colors: color_qstep %r is not a positive number" % (qstep,))
-    payload = data[HEADER_BYTES:]
-    if len(payload) < level_bytes * n_coded:
-        raise ValueError(".colors: truncated in the level table")
-    if _crc(payload) != crc:
-        raise ValueError(".colors: checksum mismatch (truncated or corrupt payload)")
-    return counts, n_coded, qstep, n_esc, payload
+    n_coded = coded_levels(counts)
+    base = _row_base(counts, n_coded)
+    symbols = np.ascontiguousarray(symbols, np.int16).reshape(-1, 3)
+    if len(symbols) != base[-1] or len(amax) != n_coded:
+        raise ValueError("colour container: the symbols do not fit the level counts")
+    level = [symbols[base[l]:base[l + 1]] for l in range(n_coded)]
+    sums = [np.minimum(np.abs(s.astype(np.int64) - int(a)), int(a) + 1).sum(0) for s, a in zip(level, amax)]       # the escape counts as amax + 1
+    ratios = ratios_of_sums(np.reshape(sums, (n_coded, 3)), np.reshape(counts[:n_coded], (n_coded, 1)))
+    streams = [coder_ops.range_encode(s, build_tables(a, r)[None]) if len(s) else b"" for s, a, r in zip(level, amax, ratios)]
+    return _write(VERSION, d, m, qstep, counts, amax, ratios, streams, [()] * n_coded, tail, esc_pos, esc_val, what="symbols")
+
+
+def assemble_v2(d, m, qstep, level_counts, amax, ratios, streams, chunk_sizes, tail, esc_pos=(), esc_val=()):
+    """The bytes of a version 2 file from coded streams: streams[l] = the bytes of level l (range or rANS, level_coders says
+    which), chunk_sizes[l] = the bytes of each of its chunks (rANS levels; anything empty otherwise)."""
+    return _write(VERSION_RANS, d, m, qstep, level_counts, amax, ratios, streams, chunk_sizes, tail, esc_pos, esc_val)
 
 
 def _read_patch(payload, at, n_esc, k_raw, m):
@@ -245,93 +275,53 @@ def _read_patch(payload, at, n_esc, k_raw, m):
     return patch
 
 
-def unpack(data, d, m, level_counts):
-    """-> (qstep, amax int32 [L], symbols int16 [K,3], patch int32 [P,2]): patch rows (k * 3 + c, q) hold the escaped values and
-    the raw tail.  d, m and level_counts are the decoded geometry's; every disagreement is a ValueError that says which."""
+def _read(data, d, m, level_counts, want_version=None):
+    """The host's half of reading a file of either version (want_version: that one alone): every check that needs no symbol, and
+    the range-coded levels.  -> (qstep, amax int32 [L], ratios int32 [L,3], kinds [L], streams [L] (bytes; b"" for a range level),
+    chunk_sizes [L] (int64 arrays), symbols int16 [K,3] with the rows of the range-coded levels filled in and the others 0, patch
+    int32 [P,2]: rows (k * 3 + c, q) of the escaped values and the raw tail).  d, m and level_counts are the decoded geometry's;
+    every disagreement is a ValueError that says which."""
     from . import coder_ops
-    counts, n_coded, qstep, n_esc, payload = _read_header(data, d, m, level_counts, VERSION, LEVEL_BYTES)
-    rows = [struct.unpack("<HHHHI", payload[LEVEL_BYTES * l:LEVEL_BYTES * (l + 1)]) for l in range(n_coded)]
-    at = LEVEL_BYTES * n_coded
-    k_raw = sum(counts[:n_coded])
-    symbols = np.empty((k_raw, 3), np.int16)
-    k = 0
-    for l, (a, r0, r1, r2, nbytes) in enumerate(rows):
-        if at + nbytes > len(payload) or (counts[l] == 0 and nbytes != 0):   # a level of zeros alone may take no bytes
-            raise ValueError(".colors: the stream of level %d does not fit the file" % l)
-        if counts[l]:
-            symbols[k:k + counts[l]] = coder_ops.range_decode(payload[at:at + nbytes], (counts[l], 3), build_tables(a, [r0, r1, r2])[None])
-        at += nbytes
-        k += counts[l]
-    patch = _read_patch(payload, at, n_esc, k_raw, m)
-    return float(qstep), np.array([r[0] for r in rows], np.int32), symbols, patch
-
-
-def header_bytes(data):
-    """bytes of the header and the level table (what the rate test does not count as payload); version 2's chunk table is payload"""
-    per_level = LEVEL_BYTES_RANS if bytes(data[4:5]) == bytes([VERSION_RANS]) else LEVEL_BYTES
-    return HEADER_BYTES + per_level * struct.unpack("<H", bytes(data[6:8]))[0]
-
-
-# ---------------------------------------------------------------------------------------------------------------- container, version 2
-def rans_chunk_count(n_symbols, steps=None):
-    """chunks of a level of n_symbols symbols"""
-    per = RANS_LANES * (RANS_STEPS if steps is None else steps)
-    return -(-int(n_symbols) // per)
-
-
-def level_coders(level_counts):
-    """the coder of every coded level: rANS from RANS_MIN_SYMBOLS symbols on"""
+    data = bytes(data)
+    if len(data) < HEADER_BYTES:
+        raise ValueError(".colors: %d bytes, shorter than its %d-byte header (truncated file)" % (len(data), HEADER_BYTES))
+    if data[:4] != MAGIC:
+        raise ValueError(".colors: wrong magic %r (want %r): not a colour stream" % (data[:4], MAGIC))
+    version, fd, n_coded, fm, qstep, crc, n_esc, gcrc = struct.unpack("<BBHQdIII", data[4:HEADER_BYTES])
+    if (version not in _FORMATS) if want_version is None else (version != want_version):
+        raise ValueError(".colors: version %d, this decoder reads version %d" % (version, want_version or VERSION))
+    if fd != d or fm != m:
+        raise ValueError(".colors was coded for other geometry: it holds d = %d, M = %d, the decoded points have d = %d, M = %d"
+                         % (fd, fm, d, m))
     counts = [int(c) for c in level_counts]
-    return [CODER_RANS if 3 * c >= RANS_MIN_SYMBOLS else CODER_RANGE for c in counts[:coded_levels(counts)]]
-
-
-def assemble_v2(d, m, qstep, level_counts, amax, ratios, streams, chunk_sizes, tail, esc_pos=(), esc_val=()):
-    """The bytes of a version 2 file from coded streams: streams[l] = the bytes of level l (range or rANS, level_coders says
-    which), chunk_sizes[l] = the bytes of each of its chunks (rANS levels; anything empty otherwise)."""
-    counts = [int(c) for c in level_counts]
-    n_coded = coded_levels(counts)
-    kinds = level_coders(counts)
-    tail = np.asarray(tail, np.int64).reshape(-1, 3)
-    if len(counts) != 3 * d + 1 or sum(counts) != m or len(tail) != m - sum(counts[:n_coded]) or not (
-            len(amax) == len(ratios) == len(streams) == len(chunk_sizes) == n_coded):
-        raise ValueError("colour container: the streams do not fit the level counts")
-    table, chunk_table = [], []
-    for l in range(n_coded):
-        if kinds[l] == CODER_RANS:
-            sizes = np.asarray(chunk_sizes[l], np.int64).reshape(-1)
-            if len(sizes) != rans_chunk_count(3 * counts[l]) or int(sizes.sum()) != len(streams[l]):
-                raise ValueError("colour container: the chunks of level %d do not fit its stream" % l)
-            chunk_table.append(sizes.astype("<u4").tobytes())
-        table.append(struct.pack("<HHHHHI", int(amax[l]), int(ratios[l][0]), int(ratios[l][1]), int(ratios[l][2]), kinds[l], len(streams[l])))
-    esc_pos = np.asarray(esc_pos, np.int64).reshape(-1)
-    esc = np.stack([np.diff(esc_pos, prepend=0), _zigzag(esc_val)], -1) if len(esc_pos) else np.zeros((0, 2), np.int64)
-    payload = b"".join(table) + b"".join(chunk_table) + b"".join(bytes(x) for x in streams) + _put_varints(esc) + _put_varints(_zigzag(tail))
-    head = MAGIC + struct.pack("<BBHQdIII", VERSION_RANS, d, n_coded, m, float(qstep), _crc(payload), len(esc_pos), _geometry_crc(counts))
-    return head + payload
-
-
-def unpack_v2(data, d, m, level_counts):
-    """The host's half of reading a version 2 file: every check that needs no symbol, and the range-coded levels.
-    -> (qstep, amax int32 [L], ratios int32 [L,3], kinds [L], streams [L] (bytes; b"" for a range level), chunk_sizes [L] (int64
-    arrays), symbols int16 [K,3] with the rows of the range-coded levels filled in and the others 0, patch int32 [P,2]).
-    d, m and level_counts are the decoded geometry's; every disagreement is a ValueError that says which."""
-    from . import coder_ops
-    counts, n_coded, qstep, n_esc, payload = _read_header(data, d, m, level_counts, VERSION_RANS, LEVEL_BYTES_RANS)
-    rows = [struct.unpack("<HHHHHI", payload[LEVEL_BYTES_RANS * l:LEVEL_BYTES_RANS * (l + 1)]) for l in range(n_coded)]
-    kinds = level_coders(counts)
-    at = LEVEL_BYTES_RANS * n_coded
+    if n_coded != coded_levels(counts):
+        raise ValueError(".colors was coded for other geometry: %d coded levels, the decoded points give %d" % (n_coded, coded_levels(counts)))
+    if gcrc != _geometry_crc(counts):
+        raise ValueError(".colors was coded for other geometry: same d and M, but the octree of the decoded points has other level sizes")
+    if not (qstep > 0 and np.isfinite(qstep)):
+        raise ValueError(".colors: color_qstep %r is not a positive number" % (qstep,))
+    row, names_coder = _FORMATS[version]
+    payload = data[HEADER_BYTES:]
+    if len(payload) < row.size * n_coded:
+        raise ValueError(".colors: truncated in the level table")
+    if _crc(payload) != crc:
+        raise ValueError(".colors: checksum mismatch (truncated or corrupt payload)")
+    rows = [row.unpack_from(payload, row.size * l) for l in range(n_coded)]
+    kinds = level_coders(counts, version)
+    at = row.size * n_coded
     chunk_sizes = []
-    for l, (a, r0, r1, r2, kind, nbytes) in enumerate(rows):
-        if kind != kinds[l]:
-            raise ValueError(".colors: level %d (%d symbols) names coder %d, the format gives it coder %d" % (l, 3 * counts[l], kind, kinds[l]))
+    for l, (a, r0, r1, r2, *kind, nbytes) in enumerate(rows):
+        if names_coder and kind[0] != kinds[l]:
+            raise ValueError(".colors: level %d (%d symbols) names coder %d, the format gives it coder %d" % (l, 3 * counts[l], kind[0], kinds[l]))
         if a > AMAX_CAP or min(r0, r1, r2) < 1:
             raise ValueError(".colors: the table of level %d (amax %d, ratios %d %d %d) is outside the format" % (l, a, r0, r1, r2))
-        n_chunks = rans_chunk_count(3 * counts[l]) if kind == CODER_RANS else 0
-        if at + 4 * n_chunks > len(payload):
-            raise ValueError(".colors: truncated in the chunk table of level %d" % l)
-        sizes = np.frombuffer(payload, "<u4", n_chunks, at).astype(np.int64)
-        at += 4 * n_chunks
-        if kind == CODER_RANS:
+        sizes = np.zeros(0, np.int64)
+        if kinds[l] == CODER_RANS:
+            n_chunks = rans_chunk_count(3 * counts[l])
+            if at + 4 * n_chunks > len(payload):
+                raise ValueError(".colors: truncated in the chunk table of level %d" % l)
+            sizes = np.frombuffer(payload, "<u4", n_chunks, at).astype(np.int64)
+            at += 4 * n_chunks
             per = RANS_LANES * RANS_STEPS
             n_of = np.minimum(per, 3 * counts[l] - per * np.arange(n_chunks, dtype=np.int64))
             states = 4 * np.minimum(n_of, RANS_LANES)
@@ -342,24 +332,39 @@ def unpack_v2(data, d, m, level_counts):
             if int(sizes.sum()) != nbytes:
                 raise ValueError(".colors: the chunks of level %d hold %d bytes, its stream %d" % (l, int(sizes.sum()), nbytes))
         chunk_sizes.append(sizes)
-    k_raw = sum(counts[:n_coded])
-    symbols = np.zeros((k_raw, 3), np.int16)
+    base = _row_base(counts, n_coded)
+    symbols = np.zeros((int(base[-1]), 3), np.int16)
     streams = []
-    k = 0
-    for l, (a, r0, r1, r2, kind, nbytes) in enumerate(rows):
+    for l, (a, r0, r1, r2, *_, nbytes) in enumerate(rows):
         if at + nbytes > len(payload) or (counts[l] == 0 and nbytes != 0):   # a level of zeros alone may take no bytes
             raise ValueError(".colors: the stream of level %d does not fit the file (byte counts overrun the payload)" % l)
-        if kind == CODER_RANS:
+        if kinds[l] == CODER_RANS:
             streams.append(payload[at:at + nbytes])
         else:
             streams.append(b"")
             if counts[l]:
-                symbols[k:k + counts[l]] = coder_ops.range_decode(payload[at:at + nbytes], (counts[l], 3), build_tables(a, [r0, r1, r2])[None])
+                symbols[base[l]:base[l + 1]] = coder_ops.range_decode(payload[at:at + nbytes], (counts[l], 3), build_tables(a, [r0, r1, r2])[None])
         at += nbytes
-        k += counts[l]
-    patch = _read_patch(payload, at, n_esc, k_raw, m)
+    patch = _read_patch(payload, at, n_esc, int(base[-1]), m)
     return (float(qstep), np.array([r[0] for r in rows], np.int32), np.array([r[1:4] for r in rows], np.int32).reshape(-1, 3), kinds, streams,
             chunk_sizes, symbols, patch)
+
+
+def unpack(data, d, m, level_counts):
+    """a version 1 file -> (qstep, amax int32 [L], symbols int16 [K,3], patch int32 [P,2]) of _read"""
+    qstep, amax, _, _, _, _, symbols, patch = _read(data, d, m, level_counts, VERSION)
+    return qstep, amax, symbols, patch
+
+
+def unpack_v2(data, d, m, level_counts):
+    """a version 2 file -> all that _read returns; the rANS levels' rows of symbols are left for the kernel"""
+    return _read(data, d, m, level_counts, VERSION_RANS)
+
+
+def header_bytes(data):
+    """bytes of the header and the level table (what the rate test does not count as payload); version 2's chunk table is payload"""
+    row = _FORMATS.get(bytes(data[4:5])[0], _FORMATS[VERSION])[0]
+    return HEADER_BYTES + row.size * struct.unpack("<H", bytes(data[6:8]))[0]
 
 
 def write_colors_file(filename, data):
@@ -520,13 +525,13 @@ class _RansJob:
         _lib.check(lib.pcgc_rans_encode(_lib.dptr(sym_d), n, _lib.dptr(self.chunks_d), self.n_chunks, _lib.dptr(self.cdfs_d), _lib.dptr(self.off_d),
                                         self.n_runs, self.cdf_total, self.max_entries, self.steps, _lib.dptr(out), out.numel(), _lib.dptr(offsets),
                                         _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_rans_encode")
-        t = _clock(timings, "v2: rANS encode kernels", t)
+        t = _clock(timings, "sub: rANS encode kernels", t)
         off = offsets.cpu().numpy()
         sizes = np.diff(off)
         if (sizes < 4).any():
             raise _lib.PcgcError("pcgc_rans_encode refused chunk %d" % int(np.flatnonzero(sizes < 4)[0]))
         payload = out[:int(off[-1])].cpu().numpy().tobytes()
-        _clock(timings, "v2: read-back of offsets and bytes", t)
+        _clock(timings, "sub: read-back of offsets and bytes", t)
         return payload, sizes
 
     def decode(self, payload, sizes, sym_d, timings=None):
@@ -542,11 +547,11 @@ class _RansJob:
         pay_d = torch.from_numpy(np.frombuffer(bytearray(payload), np.uint8)).to(self.dev)
         off_d = torch.from_numpy(off).to(self.dev)
         status = torch.empty(self.n_chunks, dtype=torch.int32, device=self.dev)
-        t = _clock(timings, "v2: upload of the rANS bytes", t)
+        t = _clock(timings, "sub: upload of the rANS bytes", t)
         _lib.check(lib.pcgc_rans_decode(_lib.dptr(pay_d), pay_d.numel(), _lib.dptr(off_d), _lib.dptr(self.chunks_d), self.n_chunks,
                                         _lib.dptr(self.cdfs_d), _lib.dptr(self.off_d), self.n_runs, self.cdf_total, self.max_entries, self.steps,
                                         _lib.dptr(sym_d), sym_d.numel(), _lib.dptr(status), _lib.stream()), "pcgc_rans_decode")
-        _clock(timings, "v2: rANS decode kernel", t)
+        _clock(timings, "sub: rANS decode kernel", t)
         return status.cpu().numpy()
 
 
@@ -598,18 +603,86 @@ def _check_step(qstep):
     return q
 
 
-def _encode_rans(plan, q, sym, maxabs, amax, amax_d, n_coded, k_raw, qstep, timings, t):
-    """the version 2 tail of encode_colors: nothing per symbol leaves the device except the small levels' symbols, the escapes
-    (rare) and the raw tail; the tables come from per-subband sums, the large levels' bytes from the rANS kernels"""
+class _Coefficients:
+    """The encoder's front end, for encode_colors and the rate control alike: the colours checked, the tree (plan), the colours
+    (rgb) and their transform coefficients (coef float64 [M,3], leaf order) on the device."""
+
+    def __init__(self, points, colors, timings=None, fuse_top=True):
+        import torch
+        col = np.asarray(colors)
+        n = len(np.asarray(points))
+        if col.shape != (n, 3) or col.dtype != np.uint8:
+            raise ValueError("colour codec: colors must be uint8 [%d, 3] (got %s %s)" % (n, col.dtype, col.shape))
+        t = _start(timings)
+        self.plan = plan = Plan(points)
+        t = _clock(timings, "sort + structure", t)
+        self.rgb = torch.from_numpy(np.ascontiguousarray(col)).to(plan.dev)
+        self.coef = torch.empty((plan.m, 3), dtype=torch.float64, device=plan.dev)
+        _lib.check(_lib.hip().pcgc_raht_load_colors(_lib.dptr(self.rgb), _lib.dptr(plan.point_of_leaf), plan.m, _lib.dptr(self.coef), _lib.stream()),
+                   "pcgc_raht_load_colors")
+        plan.transform(self.coef, fuse_top=fuse_top)
+        _clock(timings, "transform", t)
+        self.timings = timings
+
+
+def _range_runs(kinds, base):
+    """rows [lo, hi) of the symbol array for every run of neighbouring range-coded levels that holds symbols, one copy between
+    host and device each: the whole array in version 1, usually the top of the tree alone in version 2"""
+    runs = []
+    for kind, levels in itertools.groupby(range(len(kinds)), kinds.__getitem__):
+        levels = list(levels)
+        lo, hi = int(base[levels[0]]), int(base[levels[-1] + 1])
+        if kind == CODER_RANGE and hi > lo:
+            runs.append((lo, hi))
+    return runs
+
+
+def _coder_version(coder):
+    if coder not in _VERSION_OF:
+        raise ValueError("colour codec: coder must be 'range' or 'rans' (got %r)" % (coder,))
+    return _VERSION_OF[coder]
+
+
+def encode_colors(points, colors, qstep, fuse_top=True, timings=None, coder="range"):
+    """points int [M,3] unique voxels in [0, 4095], colors uint8 [M,3], qstep > 0 -> the bytes of <name>.colors.  coder: "range" =
+    stream version 1 (the host's range coder), "rans" = version 2 (the large levels coded by csrc/rans.hip)"""
+    qstep = _check_step(qstep)
+    _coder_version(coder)
+    front = _Coefficients(points, colors, timings, fuse_top)
+    return _encode_coef(front.plan, front.coef, qstep, coder, timings)
+
+
+def _encode_coef(plan, attr, qstep, coder, timings):
+    """encode_colors from the coefficients on: quantiser, symbols, entropy coding, container (attr is left as it is, so the
+    rate control codes the same coefficients at one step after another).  Nothing per symbol leaves the device except the symbols
+    of the range-coded levels (all of them for coder="range"), the escapes (rare) and the raw tail; the tables come from
+    per-subband sums, the rANS levels' bytes from the rANS kernels."""
     import torch
     from . import coder_ops
-    lib, dev, s = _lib.hip(), plan.dev, _lib.stream()
+    lib = _lib.hip()
+    m, dev, s = plan.m, plan.dev, _lib.stream()
+    version = _coder_version(coder)
     counts = [int(c) for c in plan.level_counts]
+    t = _start(timings)
+    q = torch.empty((m, 3), dtype=torch.int32, device=dev)
+    maxabs_d = torch.empty(LEVEL_SLOTS, dtype=torch.int32, device=dev)
+    _lib.check(lib.pcgc_raht_quantize(_lib.dptr(attr), _lib.dptr(plan.order), _lib.dptr(plan.subband), m, qstep, _lib.dptr(q),
+                                      _lib.dptr(maxabs_d), s), "pcgc_raht_quantize")
+    maxabs = maxabs_d.cpu().numpy()
+    n_coded = coded_levels(counts)
+    base = _row_base(counts, n_coded)
+    k_raw = int(base[-1])
+    amax = np.minimum(maxabs[:n_coded], AMAX_CAP).astype(np.int32)
+    amax_d = torch.zeros(LEVEL_SLOTS, dtype=torch.int32, device=dev)
+    amax_d[:n_coded] = torch.from_numpy(amax).to(dev)
+    sym = torch.empty((k_raw, 3), dtype=torch.int16, device=dev)
+    _lib.check(lib.pcgc_raht_symbols(_lib.dptr(q), _lib.dptr(plan.order), _lib.dptr(plan.subband), k_raw, _lib.dptr(amax_d), _lib.dptr(sym), s),
+               "pcgc_raht_symbols")
     ts = _start(timings)
-    sums_d = torch.empty(37 * 3, dtype=torch.int64, device=dev)      # one per (subband, channel), as pcgc.h says
+    sums_d = torch.empty(SUBBANDS * 3, dtype=torch.int64, device=dev)      # one per (subband, channel), as pcgc.h says
     _lib.check(lib.pcgc_raht_abs_sums(_lib.dptr(q), _lib.dptr(plan.order), _lib.dptr(plan.subband), k_raw, _lib.dptr(amax_d), _lib.dptr(sums_d), s),
                "pcgc_raht_abs_sums")
-    _clock(timings, "v2: abs sums kernel", ts)
+    _clock(timings, "sub: abs sums kernel", ts)
     tail = q[k_raw:].cpu().numpy()
     esc_pos, esc_val = np.zeros(0, np.int64), np.zeros(0, np.int64)
     if (maxabs[:n_coded] > AMAX_CAP).any():              # rare: an escape is a |q| above AMAX_CAP in a level whose amax is the cap
@@ -618,16 +691,13 @@ def _encode_rans(plan, q, sym, maxabs, amax, amax_d, n_coded, k_raw, qstep, timi
         esc_pos, esc_val = pos_d.cpu().numpy(), flat[pos_d].cpu().numpy()
     t = _clock(timings, "quantise + symbols", t)
     ts = _start(timings)
-    sums = sums_d.cpu().numpy().reshape(-1, 3)
-    kinds = level_coders(counts)
-    base = np.concatenate([[0], np.cumsum(counts[:n_coded])]).astype(np.int64)
-    ratios = [[ratio_of_sum(int(sums[l, c]), counts[l]) for c in range(3)] for l in range(n_coded)]
+    kinds = level_coders(counts, version)
+    ratios = ratios_of_sums(sums_d.cpu().numpy().reshape(SUBBANDS, 3)[:n_coded], np.reshape(counts[:n_coded], (n_coded, 1)))
     cdfs = [build_tables(int(amax[l]), ratios[l]) for l in range(n_coded)]
     on_gpu = [l for l in range(n_coded) if kinds[l] == CODER_RANS]
-    on_host = [l for l in range(n_coded) if kinds[l] == CODER_RANGE and counts[l]]
     streams, chunk_sizes = [b""] * n_coded, [np.zeros(0, np.int64)] * n_coded
     job = _RansJob([3 * base[l] for l in on_gpu], [3 * counts[l] for l in on_gpu], [cdfs[l] for l in on_gpu], RANS_STEPS, dev)
-    ts = _clock(timings, "v2: tables (host) and their upload", ts)
+    ts = _clock(timings, "sub: tables (host) and their upload", ts)
     payload, sizes = job.encode(sym.reshape(-1), timings)
     ts = _start(timings)
     at = 0
@@ -635,112 +705,15 @@ def _encode_rans(plan, q, sym, maxabs, amax, amax_d, n_coded, k_raw, qstep, timi
         chunk_sizes[l] = sz
         streams[l] = payload[at:at + int(sz.sum())]
         at += int(sz.sum())
-    if on_host:
-        small = torch.cat([sym[base[l]:base[l + 1]] for l in on_host]).cpu().numpy()
-        at = 0
-        for l in on_host:
-            streams[l] = coder_ops.range_encode(small[at:at + counts[l]], cdfs[l][None])
-            at += counts[l]
-    data = assemble_v2(plan.d, plan.m, qstep, counts, amax, ratios, streams, chunk_sizes, tail, esc_pos, esc_val)
-    _clock(timings, "v2: small levels (host range coder), varints, crc", ts)
-    _clock(timings, "host coding", t)
-    return data
-
-
-def _decode_rans(plan, data, timings=None):
-    """the version 2 head of decode_colors -> (qstep, amax, symbols on the device, patch); everything about the file is checked on
-    the host before the kernel is launched"""
-    import torch
-    dev = plan.dev
-    counts = [int(c) for c in plan.level_counts]
-    ts = _start(timings)
-    qstep, amax, ratios, kinds, streams, chunk_sizes, symbols, patch = unpack_v2(data, plan.d, plan.m, counts)
-    ts = _clock(timings, "v2: host checks, small levels (host range coder), varints, crc", ts)
-    n_coded = len(amax)
-    base = np.concatenate([[0], np.cumsum(counts[:n_coded])]).astype(np.int64)
-    sym = torch.empty((int(base[-1]), 3), dtype=torch.int16, device=dev)
-    l = 0
-    while l < n_coded:                                   # one upload per run of neighbouring range-coded levels (usually one: the top)
-        if kinds[l] != CODER_RANGE:
-            l += 1
-            continue
-        e = l
-        while e < n_coded and kinds[e] == CODER_RANGE:
-            e += 1
-        if base[e] > base[l]:
-            sym[base[l]:base[e]] = torch.from_numpy(symbols[base[l]:base[e]]).to(dev)
-        l = e
-    on_gpu = [l for l in range(n_coded) if kinds[l] == CODER_RANS]
-    job = _RansJob([3 * base[l] for l in on_gpu], [3 * counts[l] for l in on_gpu],
-                   [build_tables(int(amax[l]), ratios[l]) for l in on_gpu], RANS_STEPS, dev)
-    _clock(timings, "v2: tables (host) and their upload", ts)
-    if job.n_chunks:
-        status = job.decode(b"".join(streams[l] for l in on_gpu), np.concatenate([chunk_sizes[l] for l in on_gpu]), sym.reshape(-1), timings)
-        if status.any():
-            c = int(np.flatnonzero(status)[0])
-            raise ValueError(".colors: corrupt rANS chunk %d of level %d (status %d: %s)" % (
-                c, on_gpu[int(job.chunks[c, 0])], int(status[c]),
-                "its states do not return to 2^16" if status[c] & 1 else "words left over or missing" if status[c] & 2 else "refused"))
-    return qstep, amax, sym, patch
-
-
-def encode_colors(points, colors, qstep, fuse_top=True, timings=None, coder="range"):
-    """points int [M,3] unique voxels in [0, 4095], colors uint8 [M,3], qstep > 0 -> the bytes of <name>.colors.  coder: "range" =
-    stream version 1 (the host's range coder), "rans" = version 2 (the large levels coded by csrc/rans.hip)"""
-    import torch
-    lib = _lib.hip()
-    qstep = _check_step(qstep)
-    if coder not in ("range", "rans"):
-        raise ValueError("colour codec: coder must be 'range' or 'rans' (got %r)" % (coder,))
-    col = np.asarray(colors)
-    n = len(np.asarray(points))
-    if col.shape != (n, 3) or col.dtype != np.uint8:
-        raise ValueError("colour codec: colors must be uint8 [%d, 3] (got %s %s)" % (n, col.dtype, col.shape))
-    t = _start(timings)
-    plan = Plan(points)
-    t = _clock(timings, "sort + structure", t)
-    m, dev, s = plan.m, plan.dev, _lib.stream()
-    rgb = torch.from_numpy(np.ascontiguousarray(col)).to(dev)
-    attr = torch.empty((m, 3), dtype=torch.float64, device=dev)
-    _lib.check(lib.pcgc_raht_load_colors(_lib.dptr(rgb), _lib.dptr(plan.point_of_leaf), m, _lib.dptr(attr), s), "pcgc_raht_load_colors")
-    plan.transform(attr, fuse_top=fuse_top)
-    t = _clock(timings, "transform", t)
-    return _encode_coef(plan, attr, qstep, coder, timings, t)
-
-
-def _encode_coef(plan, attr, qstep, coder, timings, t):
-    """encode_colors from the coefficients on: quantiser, symbols, entropy coding, container (attr is left as it is, so the
-    rate control codes the same coefficients at one step after another)"""
-    import torch
-    lib = _lib.hip()
-    m, dev, s = plan.m, plan.dev, _lib.stream()
-    q = torch.empty((m, 3), dtype=torch.int32, device=dev)
-    maxabs_d = torch.empty(64, dtype=torch.int32, device=dev)
-    _lib.check(lib.pcgc_raht_quantize(_lib.dptr(attr), _lib.dptr(plan.order), _lib.dptr(plan.subband), m, qstep, _lib.dptr(q),
-                                      _lib.dptr(maxabs_d), s), "pcgc_raht_quantize")
-    maxabs = maxabs_d.cpu().numpy()
-    n_coded = coded_levels(plan.level_counts)
-    k_raw = int(plan.level_counts[:n_coded].sum())
-    amax = np.minimum(maxabs[:n_coded], AMAX_CAP).astype(np.int32)
-    amax_d = torch.zeros(64, dtype=torch.int32, device=dev)
-    amax_d[:n_coded] = torch.from_numpy(amax).to(dev)
-    sym = torch.empty((k_raw, 3), dtype=torch.int16, device=dev)
-    _lib.check(lib.pcgc_raht_symbols(_lib.dptr(q), _lib.dptr(plan.order), _lib.dptr(plan.subband), k_raw, _lib.dptr(amax_d), _lib.dptr(sym), s),
-               "pcgc_raht_symbols")
-    if coder == "rans":
-        data = _encode_rans(plan, q, sym, maxabs, amax, amax_d, n_coded, k_raw, qstep, timings, t)
-        if timings is not None:
-            timings["launches"] = plan.launches
-        return data
-    symbols = sym.cpu().numpy()
-    tail = q[k_raw:].cpu().numpy()
-    esc_pos, esc_val = np.zeros(0, np.int64), np.zeros(0, np.int64)
-    if (maxabs[:n_coded] > AMAX_CAP).any():              # rare: only then can a symbol be the escape
-        esc_of_row = np.repeat(2 * amax.astype(np.int64) + 1, plan.level_counts[:n_coded])
-        esc_pos = np.flatnonzero((symbols == esc_of_row[:, None].astype(np.int16)).reshape(-1))
-        esc_val = q.reshape(-1)[torch.from_numpy(esc_pos).to(dev)].cpu().numpy()
-    t = _clock(timings, "quantise + symbols", t)
-    data = pack(plan.d, m, qstep, plan.level_counts, amax, symbols, tail, esc_pos, esc_val)
+    symbols = torch.empty((k_raw, 3), dtype=torch.int16)  # the host coder's: only the rows of the range-coded levels are filled
+    for lo, hi in _range_runs(kinds, base):
+        symbols[lo:hi].copy_(sym[lo:hi])
+    symbols = symbols.numpy()
+    for l in range(n_coded):
+        if kinds[l] == CODER_RANGE and counts[l]:
+            streams[l] = coder_ops.range_encode(symbols[base[l]:base[l + 1]], cdfs[l][None])
+    data = _write(version, plan.d, m, qstep, counts, amax, ratios, streams, chunk_sizes, tail, esc_pos, esc_val)
+    _clock(timings, "sub: range-coded levels (host range coder), varints, crc", ts)
     _clock(timings, "host coding", t)
     if timings is not None:
         timings["launches"] = plan.launches
@@ -748,23 +721,38 @@ def _encode_coef(plan, attr, qstep, coder, timings, t):
 
 
 def decode_colors(points, data, fuse_top=True, timings=None):
-    """points: the decoded geometry the stream was coded for, data: the bytes of <name>.colors -> uint8 [M,3] in the order of
-    `points`.  A stream coded for other geometry, a truncated or a corrupt one raises ValueError."""
+    """points: the decoded geometry the stream was coded for, data: the bytes of <name>.colors (either version) -> uint8 [M,3] in
+    the order of `points`.  A stream coded for other geometry, a truncated or a corrupt one raises ValueError; everything about
+    the file is checked on the host before a kernel reads it."""
     import torch
     lib = _lib.hip()
     t = _start(timings)
     plan = Plan(points)
     t = _clock(timings, "sort + structure", t)
     m, dev, s = plan.m, plan.dev, _lib.stream()
-    head = bytes(data[:HEADER_BYTES])
-    if len(head) == HEADER_BYTES and head[:4] == MAGIC and head[4] == VERSION_RANS:
-        qstep, amax, symbols, patch = _decode_rans(plan, data, timings)
-    else:                                                # version 1, and every refusal in version 1's words
-        qstep, amax, symbols, patch = unpack(data, plan.d, m, plan.level_counts)
+    counts = [int(c) for c in plan.level_counts]
+    ts = _start(timings)
+    qstep, amax, ratios, kinds, streams, chunk_sizes, symbols, patch = _read(data, plan.d, m, counts)
+    ts = _clock(timings, "sub: host checks, range-coded levels (host range coder), varints, crc", ts)
+    n_coded = len(amax)
+    base = _row_base(counts, n_coded)
+    sym = torch.empty((len(symbols), 3), dtype=torch.int16, device=dev)
+    for lo, hi in _range_runs(kinds, base):
+        sym[lo:hi].copy_(torch.from_numpy(symbols[lo:hi]))
+    on_gpu = [l for l in range(n_coded) if kinds[l] == CODER_RANS]
+    job = _RansJob([3 * base[l] for l in on_gpu], [3 * counts[l] for l in on_gpu],
+                   [build_tables(int(amax[l]), ratios[l]) for l in on_gpu], RANS_STEPS, dev)
+    _clock(timings, "sub: tables (host) and their upload", ts)
+    if job.n_chunks:
+        status = job.decode(b"".join(streams[l] for l in on_gpu), np.concatenate([chunk_sizes[l] for l in on_gpu]), sym.reshape(-1), timings)
+        if status.any():
+            c = int(np.flatnonzero(status)[0])
+            raise ValueError(".colors: corrupt rANS chunk %d of level %d (status %d: %s)" % (
+                c, on_gpu[int(job.chunks[c, 0])], int(status[c]),
+                "its states do not return to 2^16" if status[c] & 1 else "words left over or missing" if status[c] & 2 else "refused"))
     t = _clock(timings, "host coding", t)
-    amax_d = torch.zeros(64, dtype=torch.int32, device=dev)
-    amax_d[:len(amax)] = torch.from_numpy(amax).to(dev)
-    sym = symbols if torch.is_tensor(symbols) else torch.from_numpy(symbols).to(dev)
+    amax_d = torch.zeros(LEVEL_SLOTS, dtype=torch.int32, device=dev)
+    amax_d[:n_coded] = torch.from_numpy(amax).to(dev)
     patch_d = torch.from_numpy(np.ascontiguousarray(patch)).to(dev)
     attr = torch.empty((m, 3), dtype=torch.float64, device=dev)
     _lib.check(lib.pcgc_raht_dequantize(_lib.dptr(sym) if len(symbols) else None, len(symbols), _lib.dptr(patch_d), len(patch),
@@ -832,15 +820,6 @@ def psnr_of_mse(mse):
     return float("inf") if not mse > 0 else float(-10.0 * np.log10(mse))
 
 
-def ratios_of_sums(abs_sums, n):
-    """ratio_of_sum for arrays: abs_sums int [...], n the subband's size (broadcast) -> Q16 ratios int64 [...]"""
-    a = np.asarray(abs_sums, np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        mean = np.where(np.asarray(n) > 0, a / np.asarray(n, np.float64), 0.0)
-        r = np.where(mean > 0, (np.sqrt(1.0 + mean * mean) - 1.0) / mean, 0.0)
-    return np.clip(np.rint(r * 65536), 1, 65535).astype(np.int64)
-
-
 def estimate_bits(abs_sums, n):
     """Bits of a subband of n values whose magnitudes add up to abs_sums, under the two-sided geometric table the encoder would
     choose for it (ratio r): a value q costs -log2((1 - r) / (1 + r)) - |q| log2(r), linear in |q|, so the sum suffices.  The
@@ -852,63 +831,49 @@ def estimate_bits(abs_sums, n):
 
 
 def estimate_bytes(level_counts, abs_sums, coder="range"):
-    """The size of the file encode_colors would write, from a sweep's sums: abs_sums int64 [K, 37, 3] -> float64 [K].  Header,
+    """The size of the file encode_colors would write, from a sweep's sums: abs_sums int64 [K, SUBBANDS, 3] -> float64 [K].  Header,
     level rows, per coded level the bytes of estimate_bits over its three channels (rounded up), RAW_VALUE_BYTES per value of
     the raw tail and, for coder="rans", a rANS level's chunk table entries and final states."""
+    version = _coder_version(coder)
     counts = np.asarray(level_counts, np.int64)
     n_coded = coded_levels(counts)
-    sums = np.asarray(abs_sums, np.int64).reshape(-1, 37, 3)[:, :n_coded]
+    sums = np.asarray(abs_sums, np.int64).reshape(-1, SUBBANDS, 3)[:, :n_coded]
     bits = estimate_bits(sums, counts[None, :n_coded, None]).sum(-1)                      # [K, L]
-    fixed = HEADER_BYTES + (LEVEL_BYTES_RANS if coder == "rans" else LEVEL_BYTES) * n_coded
+    fixed = HEADER_BYTES + _FORMATS[version][0].size * n_coded
     fixed += RAW_VALUE_BYTES * 3 * int(counts.sum() - counts[:n_coded].sum())
-    if coder == "rans":
-        per = RANS_LANES * RANS_STEPS
-        for l, kind in enumerate(level_coders(counts)):
-            if kind == CODER_RANS:
-                n = 3 * int(counts[l])
-                chunks = rans_chunk_count(n)
-                fixed += 4 * chunks + 4 * (RANS_LANES * (chunks - 1) + min(RANS_LANES, n - per * (chunks - 1)))
+    per = RANS_LANES * RANS_STEPS
+    for l, kind in enumerate(level_coders(counts, version)):
+        if kind == CODER_RANS:
+            n = 3 * int(counts[l])
+            chunks = rans_chunk_count(n)
+            fixed += 4 * chunks + 4 * (RANS_LANES * (chunks - 1) + min(RANS_LANES, n - per * (chunks - 1)))
     return fixed + np.ceil(bits / 8.0).sum(-1)
 
 
-class _Search:
-    """What both targets share: the tree, the colours and their coefficients on the device, and the three device-side tools —
-    the sweep, the closed-loop probe and the real encode from the same coefficients."""
+class _Search(_Coefficients):
+    """What both targets share: the encoder's front end, and the three device-side tools that work on its coefficients — the
+    sweep, the closed-loop probe and the real encode."""
 
     def __init__(self, points, colors, timings=None):
         import torch
-        lib = _lib.hip()
-        col = np.asarray(colors)
-        n = len(np.asarray(points))
-        if col.shape != (n, 3) or col.dtype != np.uint8:
-            raise ValueError("colour codec: colors must be uint8 [%d, 3] (got %s %s)" % (n, col.dtype, col.shape))
-        t = _start(timings)
-        self.plan = plan = Plan(points)
-        t = _clock(timings, "sort + structure", t)
-        m, dev, s = plan.m, plan.dev, _lib.stream()
-        self.rgb = torch.from_numpy(np.ascontiguousarray(col)).to(dev)
-        self.coef = torch.empty((m, 3), dtype=torch.float64, device=dev)
-        _lib.check(lib.pcgc_raht_load_colors(_lib.dptr(self.rgb), _lib.dptr(plan.point_of_leaf), m, _lib.dptr(self.coef), s), "pcgc_raht_load_colors")
-        plan.transform(self.coef)
-        _clock(timings, "transform", t)
-        self.n_coded = coded_levels(plan.level_counts)
-        self.k_raw = int(plan.level_counts[:self.n_coded].sum())
+        super().__init__(points, colors, timings)
+        self.n_coded = coded_levels(self.plan.level_counts)
+        self.k_raw = int(self.plan.level_counts[:self.n_coded].sum())
         self.work = torch.empty_like(self.coef)
-        self.out = torch.empty((m, 3), dtype=torch.uint8, device=dev)
-        self.sums6 = torch.empty(6, dtype=torch.int64, device=dev)
-        self.timings = timings
+        self.out = torch.empty((self.plan.m, 3), dtype=torch.uint8, device=self.plan.dev)
+        self.sums6 = torch.empty(6, dtype=torch.int64, device=self.plan.dev)
         self.probes = self.real_encodes = 0
 
     def sweep(self, steps):
-        """-> (abs_sums int64 [K, 37, 3], max_abs int32 [K, 37]) of the K steps, SWEEP_MAX_STEPS per launch"""
+        """-> (abs_sums int64 [K, SUBBANDS, 3], max_abs int32 [K, SUBBANDS]) of the K steps, SWEEP_MAX_STEPS per launch"""
         import torch
         lib, plan = _lib.hip(), self.plan
         steps = np.ascontiguousarray(steps, np.float64).reshape(-1)
         if len(steps) == 0 or not (np.isfinite(steps) & (steps > 0)).all():
             raise ValueError("colour codec: the sweep wants at least one step, all positive numbers (got %r)" % (steps,))
         t = _start(self.timings)
-        sums = torch.empty((len(steps), 37, 3), dtype=torch.int64, device=plan.dev)
-        tops = torch.empty((len(steps), 37), dtype=torch.int32, device=plan.dev)
+        sums = torch.empty((len(steps), SUBBANDS, 3), dtype=torch.int64, device=plan.dev)
+        tops = torch.empty((len(steps), SUBBANDS), dtype=torch.int32, device=plan.dev)
         for k0 in range(0, len(steps), SWEEP_MAX_STEPS):
             part = np.ascontiguousarray(steps[k0:k0 + SWEEP_MAX_STEPS])
             _lib.check(lib.pcgc_raht_rate_sweep(_lib.dptr(self.coef), _lib.dptr(plan.order), _lib.dptr(plan.subband), plan.m, self.k_raw,
@@ -940,7 +905,7 @@ class _Search:
 
     def encode(self, qstep, coder):
         t = _start(self.timings)
-        data = _encode_coef(self.plan, self.coef, _check_step(qstep), coder, None, 0.0)
+        data = _encode_coef(self.plan, self.coef, _check_step(qstep), coder, None)
         self.real_encodes += 1
         _clock(self.timings, "rate control: real encodes", t)
         return data
@@ -948,7 +913,7 @@ class _Search:
 
 def rate_sweep(points, colors, steps):
     """pcgc_raht_rate_sweep on its own: for every step, what a real encode at that step would hand its tables — abs_sums int64
-    [K, 37, 3] (per subband and channel, the sum of min(|q|, 2048) over the coded levels) and max_abs int32 [K, 37]"""
+    [K, SUBBANDS, 3] (per subband and channel, the sum of min(|q|, 2048) over the coded levels) and max_abs int32 [K, SUBBANDS]"""
     return _Search(points, colors).sweep(steps)
 
 
@@ -981,8 +946,7 @@ def encode_colors_target(points, colors, psnr=None, bpp=None, coder="range", tim
     report: j, qstep, psnr_y, bytes, bpp, probes, real_encodes (and est_bytes, j_est with bpp)."""
     if (psnr is None) == (bpp is None):
         raise ValueError("colour codec: give exactly one target, psnr (dB) or bpp (bits per point)")
-    if coder not in ("range", "rans"):
-        raise ValueError("colour codec: coder must be 'range' or 'rans' (got %r)" % (coder,))
+    _coder_version(coder)
     target = float(psnr if bpp is None else bpp)
     if np.isnan(target) or (bpp is not None and not (target > 0)):
         raise ValueError("colour codec: the target must be a number, a bpp positive (got %r)" % (target,))

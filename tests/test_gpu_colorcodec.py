@@ -2,6 +2,7 @@
 (tests/_raht_ref.py): transform, inverse, decoded colours, the file's rate against the reference's empirical entropy, the
 command line (compress --colors raht, decompress with <name>.colors) and eval's color_qstep."""
 import csv
+import functools
 import os
 import sys
 
@@ -12,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _raht_ref as ref                                                  # noqa: E402
+import _rans_ref as rans                                                 # noqa: E402
 from pcgcv1_amd import _lib, metrics, synthetic                          # noqa: E402
 from pcgcv1_amd import colorcodec as cc                                  # noqa: E402
 from pcgcv1_amd import recolor as rc                                     # noqa: E402
@@ -130,6 +132,63 @@ def test_codec_round_trip_bit_identical_and_within_the_bound(name):
         print(name, step, "rms YCoCg", rms, "bytes", len(data))
         assert (rms <= step / 2 + 0.5 + 1e-9).all(), (name, step, rms)
         assert np.array_equal(np.clip(ref.ycocg_to_rgb(ycc.astype(np.int32)), 0, 255), got)
+
+
+ESCAPE_CLOUDS = dict(CASES, dense_res48=_dense(21, 48, 30000))
+
+
+@functools.lru_cache(maxsize=None)
+def _escape_reference(name, step):
+    """the numpy rule's decoded colours and what it hands to the container, as test_gpu_rans._reference builds it, with both
+    files: version 1 from colorcodec.pack (tables from the symbols' histogram sums, on the host), version 2 from the reference"""
+    p, c = ESCAPE_CLOUDS[name]
+    want, q, sub, _ = ref.codec(p, c, step)
+    d = ref.depth_of(p)
+    counts = np.bincount(sub, minlength=3 * d + 1)
+    qg = q[ref.subband_order(sub)]
+    n_coded = cc.coded_levels(counts)
+    k = int(counts[:n_coded].sum())
+    lev = np.repeat(np.arange(n_coded), counts[:n_coded])
+    biggest = np.zeros(n_coded, np.int64)
+    np.maximum.at(biggest, lev, np.abs(qg[:k]).max(1))
+    amax = np.minimum(biggest, cc.AMAX_CAP).astype(np.int32)
+    a = amax[lev][:, None]
+    inside = np.abs(qg[:k]) <= a
+    sym = np.where(inside, qg[:k] + a, 2 * a + 1).astype(np.int16)
+    pos = np.flatnonzero(~inside.reshape(-1))
+    args = (d, len(p), step, counts, amax, sym, qg[k:], pos, qg[:k].reshape(-1)[pos])
+    return want, counts, amax, np.bincount(lev[pos // 3], minlength=n_coded), cc.pack(*args), rans.pack_v2(*args)
+
+
+@pytest.mark.parametrize("name,step", [("dense_res20", 0.0625), ("dense_res20", 1), ("dense_res32", 0.0625), ("dense_res48", 0.0625)])
+def test_escapes_through_the_one_encoder_tail(name, step):
+    """Both coders take their tables from pcgc_raht_abs_sums and their escapes from the device-side search; the files must be
+    the host's, byte for byte, where escapes are many.  dense_res20 at step 1 / 16: 555 escapes over all 8 coded levels, every
+    level at AMAX_CAP; at step 1: none.  An escape inside a rANS level: the level sizes follow from the geometry alone, and
+    dense_res32's largest level has 4125 leaves (12 375 symbols < RANS_MIN_SYMBOLS) whatever the step, so that condition is
+    asserted on dense_res48 (26 266 points: level 2 is a rANS level between range-coded ones) and dense_res32 keeps the rest."""
+    p, c = ESCAPE_CLOUDS[name]
+    want, counts, amax, escapes, want_v1, want_v2 = _escape_reference(name, step)
+    if name == "dense_res20":
+        assert len(p) == 1378 and len(amax) == 8
+        if step == 1:
+            assert escapes.sum() == 0
+        else:
+            assert escapes.sum() == 555 and (escapes > 0).all() and (amax == cc.AMAX_CAP).all()
+    else:
+        assert escapes.sum() > 0
+    kinds = cc.level_coders(counts)
+    if name == "dense_res48":
+        assert any(3 * counts[l] >= cc.RANS_MIN_SYMBOLS and kinds[l] == cc.CODER_RANS and escapes[l] > 0 for l in range(len(amax)))
+        assert kinds[:4] == [cc.CODER_RANGE, cc.CODER_RANGE, cc.CODER_RANS, cc.CODER_RANGE]
+    v1 = cc.encode_colors(p, c, step)
+    assert v1 == want_v1, (name, step, len(v1), len(want_v1))
+    v2 = cc.encode_colors(p, c, step, coder="rans")
+    assert v2 == want_v2, (name, step, len(v2), len(want_v2))
+    shuffle = np.random.default_rng(1).permutation(len(p))
+    for data in (v1, v2):
+        assert np.array_equal(cc.decode_colors(p, data), want)
+        assert np.array_equal(cc.decode_colors(p[shuffle], data), want[shuffle])
 
 
 def test_input_checks():

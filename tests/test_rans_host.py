@@ -1,6 +1,7 @@
 """Colour stream version 2 on the host, no GPU: the numpy statement of the chunked 64-way interleaved rANS coder
 (tests/_rans_ref.py) round trips and ends every chunk in its valid state, and the version 2 container (colorcodec.assemble_v2 /
 unpack_v2, the reference's pack_v2 / unpack_v2) holds mixed range and rANS levels and names every structural error."""
+import hashlib
 import os
 import struct
 import sys
@@ -209,6 +210,23 @@ def test_container_v2_round_trip_and_refusals():
     cc.unpack_v2(damaged, d, m, counts)
     with pytest.raises(ValueError, match="corrupt rANS chunk 0 of level 0"):
         rans.unpack_v2(damaged, d, m, counts)
+
+
+def test_container_bytes_are_frozen():
+    """Both files of _fabricated()'s input (58 032 points, 8 coded levels, two rANS levels, an empty level, escapes in levels
+    with amax <= 6), by their sha256.  The digests were taken at the commit before the two writers became one (numpy 2.2.6),
+    never from the code under test: no byte of a .colors file may move."""
+    d, m, counts, amax, sym, q, k, pos = _fabricated()
+    assert m == 58032 and cc.coded_levels(counts) == 8 and cc.level_coders(counts).count(1) == 2 and counts[1] == 0 and amax.max() <= 6
+    args = (d, m, 2.0, counts, amax, sym, q[k:], pos, q[:k].reshape(-1)[pos])
+    v1 = cc.pack(*args)
+    assert len(v1) == 116269 and hashlib.sha256(v1).hexdigest() == "12b471ef6268b55c273636e5be6ce9e42e2646ba059fc5a1992359a317c8ead0"
+    data = rans.pack_v2(*args)
+    assert len(data) == 117003 and hashlib.sha256(data).hexdigest() == "67a782ad13bafa255c70448c58bc7e114a45b67a3059b110067c56993abf6a30"
+    _, amax2, ratios, kinds, streams, chunk_sizes, _, _ = cc.unpack_v2(data, d, m, counts)
+    again = cc.assemble_v2(d, m, 2.0, counts, amax2, ratios, [streams[l] if kinds[l] else _range_stream(data, counts, l) for l in range(8)],
+                           chunk_sizes, q[k:], pos, q[:k].reshape(-1)[pos])
+    assert hashlib.sha256(again).hexdigest() == "67a782ad13bafa255c70448c58bc7e114a45b67a3059b110067c56993abf6a30"
 
 
 def _range_stream(data, counts, level):

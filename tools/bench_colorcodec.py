@@ -126,10 +126,10 @@ def rans_report(a, ref, cc, rc, synthetic, model, postprocess_points, preprocess
             for k in coders:
                 out.append("  %-5s %s: %s | total %.3f | .colors %d bytes" % (k, w, "  ".join("%s %.3f" % (key, med[(k, w)][key]) for key in STAGES),
                                                                              med[(k, w)]["total"], size[k]))
-            if "rans" in coders:
-                sub = sorted(key for key in runs[("rans", w)][0] if key.startswith("v2: "))
-                out.append("        rans %s, inside the stages above (each ended by its own synchronise): %s" % (
-                    w, "; ".join("%s %.3f" % (key[4:], 1e3 * float(np.median([x[key] for x in runs[("rans", w)]]))) for key in sub)))
+            for k in coders:
+                sub = sorted(key for key in runs[(k, w)][0] if key.startswith("sub: "))
+                out.append("        %-5s %s, inside the stages above (each ended by its own synchronise): %s" % (
+                    k, w, "; ".join("%s %.3f" % (key[5:], 1e3 * float(np.median([x[key] for x in runs[(k, w)]]))) for key in sub)))
             if len(coders) == 2:
                 out.append("        %s: range / rans  host coding %.2fx  total %.2fx" % (w, med[("range", w)]["host coding"] / med[("rans", w)]["host coding"],
                                                                                        med[("range", w)]["total"] / med[("rans", w)]["total"]))
