@@ -1,24 +1,23 @@
 // Colour kernels (gfx950): recolouring of a decoded cloud from the original, and the colour distortion of MPEG pc_error
 // 0.13.4 (`--color=1`).  DESIGN.md "Colours" states both rules; tests/_color_ref.py restates them in numpy.
 //
-// Clouds are voxelised (integer coordinates < res, unique).  The cloud that is SEARCHED becomes an occupancy bit set, as in
-// the D1 / D2 kernels of tail.hip, and every point of the other cloud walks Chebyshev shells of growing radius until no
-// unvisited cell can be nearer.  The index of an occupied cell among the cloud's points in key order (key = (x*res + y)*res
-// + z) comes from a rank structure over the bit set: the exclusive prefix of the words' popcounts, one 32-bit entry per
-// word, so a cell's index is rank[word] + popcount(bits below it) — two loads, no search, no hash table.
+// Clouds are voxelised (integer coordinates < res, unique).  The cloud that is SEARCHED becomes the occupancy bit set of
+// voxel_grid.h, and every point of the other cloud finds its nearest cells there (nearest_d2, for_each_at_distance).  The
+// index of an occupied cell among the cloud's points in key order (key = (x*res + y)*res + z) comes from a rank structure
+// over the bit set: the exclusive prefix of the words' popcounts, one 32-bit entry per word, so a cell's index is
+// rank[word] + popcount(bits below it) — two loads, no search, no hash table.
 //
 // Everything that decides an output is integer arithmetic (32-bit atomic adds of colours and counts: order-free), so
 // recolouring is defined bit for bit; the colour mse sums float64 terms in a fixed order (per thread, then a tree per
 // workgroup, then the workgroups in index order).
 #include <algorithm>
 #include "common.h"
+#include "voxel_grid.h"
 
 namespace pcgc {
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- bit set + rank
-// The bit set is padded to a whole number of scan blocks (kScanWords words each) and zeroed, so the scan reads no bound.
-constexpr int kScanThreads = 256, kWordsPerThread = 16, kScanWords = kScanThreads * kWordsPerThread;
 constexpr int kSumBlocks = 1024;
 constexpr int64_t kMaxSource = 0xFFFFFFFFll / 255;      // 255 * n_s fits the 32-bit sums of the scatter pass
 
@@ -29,102 +28,13 @@ struct Grid {
   int res;
 };
 
-__device__ __forceinline__ int64_t cell_of(int res, int x, int y, int z) { return ((int64_t)x * res + y) * res + z; }
-
-__device__ __forceinline__ bool in_grid(int res, int x, int y, int z) {
-  return (unsigned)x < (unsigned)res && (unsigned)y < (unsigned)res && (unsigned)z < (unsigned)res;
-}
-
-__device__ __forceinline__ bool bit_at(const Grid& g, int x, int y, int z) {
-  if (!in_grid(g.res, x, y, z)) return false;
-  const int64_t idx = cell_of(g.res, x, y, z);
-  return (g.bits[idx >> 5] >> (idx & 31)) & 1u;
-}
-
 // index of the occupied cell idx among the set bits in key order
 __device__ __forceinline__ int64_t rank_of(const Grid& g, int64_t idx) {
   const int64_t w = idx >> 5;
   return (int64_t)g.rank[w] + __popc(g.bits[w] & ((1u << (idx & 31)) - 1u));
 }
 
-__global__ void bits_from_points_kernel(const int32_t* p, int64_t n, int res, unsigned* bits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-  if (!in_grid(res, x, y, z)) return;
-  const int64_t idx = cell_of(res, x, y, z);
-  atomicOr(&bits[idx >> 5], 1u << (idx & 31));
-}
-
-__global__ void bits_from_keys_kernel(const int64_t* keys, int64_t n, int64_t cells, unsigned* bits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int64_t idx = keys[i];
-  if (idx < 0 || idx >= cells) return;
-  atomicOr(&bits[idx >> 5], 1u << (idx & 31));
-}
-
-__device__ __forceinline__ unsigned load_words(const unsigned* bits, int64_t blk, unsigned w[kWordsPerThread]) {
-  const uint4* src = reinterpret_cast<const uint4*>(bits + blk * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
-  unsigned c = 0;
-#pragma unroll
-  for (int k = 0; k < kWordsPerThread / 4; ++k) {
-    const uint4 u = src[k];
-    w[4 * k] = u.x; w[4 * k + 1] = u.y; w[4 * k + 2] = u.z; w[4 * k + 3] = u.w;
-    c += __popc(u.x) + __popc(u.y) + __popc(u.z) + __popc(u.w);
-  }
-  return c;
-}
-
-// exclusive prefix of v over the workgroup's threads (in thread order) and the workgroup total
-__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[kScanThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kScanThreads / 64; ++k) {
-    before += k < wave ? wsum[k] : 0u;
-    all += wsum[k];
-  }
-  *total = all;
-  return before + incl - v;
-}
-
-__global__ void __launch_bounds__(kScanThreads) rank_count_kernel(const unsigned* bits, int64_t* block_count) {
-  unsigned w[kWordsPerThread];
-  const unsigned c = load_words(bits, blockIdx.x, w);
-  unsigned total;
-  block_scan(c, &total);
-  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// exclusive prefix of the per-block counts in place, the sum in *n_set: one workgroup, each thread a contiguous run
-__global__ void __launch_bounds__(1024) rank_block_scan_kernel(int64_t* block_count, int64_t nblk, int64_t* n_set) {
-  __shared__ int64_t part[1024];
-  const int64_t per = (nblk + 1023) / 1024;
-  const int64_t b0 = std::min<int64_t>(nblk, (int64_t)threadIdx.x * per), b1 = std::min<int64_t>(nblk, b0 + per);
-  int64_t s = 0;
-  for (int64_t b = b0; b < b1; ++b) s += block_count[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t acc = 0;
-    for (int t = 0; t < 1024; ++t) { const int64_t x = part[t]; part[t] = acc; acc += x; }
-    *n_set = acc;
-  }
-  __syncthreads();
-  int64_t acc = part[threadIdx.x];
-  for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
-}
-
+// rank[w] of every word, from the per-block offsets the scan of voxel_grid.h left
 __global__ void __launch_bounds__(kScanThreads) rank_write_kernel(const unsigned* bits, const int64_t* block_offset, unsigned* rank) {
   unsigned w[kWordsPerThread];
   const unsigned c = load_words(bits, blockIdx.x, w);
@@ -152,50 +62,16 @@ __global__ void colors_to_rank_order_kernel(const int32_t* p, const uint8_t* col
 }
 
 // ---------------------------------------------------------------------------------------------------------------- search
-constexpr unsigned kNone = 0xFFFFFFFFu;
-
-// squared distance from (x, y, z) to the nearest occupied cell (the shell search of tail.hip's D1 / D2 kernels): after
-// shell w every unvisited cell is farther than w, so the search stops as soon as best <= (w+1)^2
+// squared distance to the nearest occupied cell, kNoCell for an empty set (the shell walk would find nothing, slowly)
 __device__ __forceinline__ unsigned nearest_d2(const Grid& g, int x, int y, int z) {
-  if (*g.n_set == 0) return kNone;
-  unsigned best = kNone;
-  for (int w = 0; w < 2 * g.res; ++w) {
-    for (int dx = -w; dx <= w; ++dx)
-      for (int dy = -w; dy <= w; ++dy) {
-        const bool edge = (dx == -w || dx == w || dy == -w || dy == w);
-        const unsigned dxy = (unsigned)(dx * dx + dy * dy);
-        if (dxy >= best) continue;
-        if (edge) {
-          for (int dz = -w; dz <= w; ++dz)
-            if (bit_at(g, x + dx, y + dy, z + dz)) best = min(best, dxy + (unsigned)(dz * dz));
-        } else {
-          if (bit_at(g, x + dx, y + dy, z - w)) best = min(best, dxy + (unsigned)(w * w));
-          if (bit_at(g, x + dx, y + dy, z + w)) best = min(best, dxy + (unsigned)(w * w));
-        }
-      }
-    if (best <= (unsigned)((w + 1) * (w + 1))) break;
-  }
-  return best;
+  return *g.n_set == 0 ? kNoCell : nearest_d2(g.bits, g.res, x, y, z);
 }
 
 // calls f(j) with the key-order index j of every occupied cell at squared distance `best` from (x, y, z): ties are kept
 template <typename F>
 __device__ __forceinline__ void for_each_nearest(const Grid& g, int x, int y, int z, unsigned best, F f) {
-  if (best == kNone) return;
-  const int r = (int)sqrtf((float)best) + 1;
-  for (int dx = -r; dx <= r; ++dx)
-    for (int dy = -r; dy <= r; ++dy) {
-      const int rest = (int)best - dx * dx - dy * dy;
-      if (rest < 0) continue;
-      int dz = (int)sqrtf((float)rest);
-      while (dz * dz > rest) --dz;
-      while ((dz + 1) * (dz + 1) <= rest) ++dz;
-      if (dz * dz != rest) continue;
-      for (int sgn = 0; sgn < (dz ? 2 : 1); ++sgn) {
-        const int qz = sgn ? z - dz : z + dz;
-        if (bit_at(g, x + dx, y + dy, qz)) f(rank_of(g, cell_of(g.res, x + dx, y + dy, qz)));
-      }
-    }
+  if (best == kNoCell) return;
+  for_each_at_distance(g.bits, g.res, x, y, z, best, [&](int dx, int dy, int qz) { f(rank_of(g, cell_of(g.res, x + dx, y + dy, qz))); });
 }
 
 // mean rounded half up, in integers
@@ -286,13 +162,6 @@ __global__ void color_mse_final_kernel(const double* partial, int nb, int64_t na
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-int64_t scan_blocks(int res) {
-  const int64_t cells = (int64_t)res * res * res;
-  return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32);
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct RankBuffers {
   unsigned* bits;
   unsigned* rank;
@@ -302,18 +171,18 @@ struct RankBuffers {
 };
 
 size_t rank_bytes(int res) {
-  const int64_t nblk = scan_blocks(res);
-  return 2 * align256((size_t)nblk * kScanWords * sizeof(unsigned)) + align256((size_t)nblk * sizeof(int64_t)) + 256;
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  return 2 * align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) + 256;
 }
 
 RankBuffers rank_layout(int res, void* workspace) {
-  const int64_t nblk = scan_blocks(res);
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
   RankBuffers r;
   char* w = static_cast<char*>(workspace);
   r.bits = reinterpret_cast<unsigned*>(w);
-  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  w += align256(padded_bits_bytes(nblk));
   r.rank = reinterpret_cast<unsigned*>(w);
-  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  w += align256(padded_bits_bytes(nblk));
   r.block_count = reinterpret_cast<int64_t*>(w);
   w += align256((size_t)nblk * sizeof(int64_t));
   r.n_set = reinterpret_cast<int64_t*>(w);
@@ -323,15 +192,15 @@ RankBuffers rank_layout(int res, void* workspace) {
 
 // bit set of a cloud given as points (keys == NULL) or as linear keys, and its rank structure
 int build_rank(const RankBuffers& r, int res, const int32_t* points, const int64_t* keys, int64_t n, hipStream_t s) {
-  const int64_t nblk = scan_blocks(res);
-  PCGC_CHECK_HIP(hipMemsetAsync(r.bits, 0, (size_t)nblk * kScanWords * sizeof(unsigned), s));
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  PCGC_CHECK_HIP(hipMemsetAsync(r.bits, 0, padded_bits_bytes(nblk), s));
   const unsigned grid = (unsigned)((n + 255) / 256);
   if (keys)
     hipLaunchKernelGGL(bits_from_keys_kernel, dim3(grid), dim3(256), 0, s, keys, n, (int64_t)res * res * res, r.bits);
   else
     hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, r.bits);
-  hipLaunchKernelGGL(rank_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count);
-  hipLaunchKernelGGL(rank_block_scan_kernel, dim3(1), dim3(1024), 0, s, r.block_count, nblk, r.n_set);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, r.block_count, nblk, r.n_set);
   hipLaunchKernelGGL(rank_write_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count, r.rank);
   return 0;
 }

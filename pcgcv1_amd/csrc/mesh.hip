@@ -7,8 +7,8 @@
 //
 // Every floating-point step of the sampler and the voxeliser is one IEEE double operation in a fixed order (the file is
 // built with -ffp-contract=off), so tests/_mesh_ref.py restates them in numpy bit for bit.  Integer sets are formed as
-// an occupancy bit set, and np.unique's lexicographic order is the bit order: a two-pass scan over per-word popcounts
-// compacts the set bits in linear-key order.
+// the occupancy bit set of voxel_grid.h, and np.unique's lexicographic order is the bit order: its two-pass scan over
+// per-word popcounts, then bits_compact_kernel here, lists the set bits in linear-key order.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -16,6 +16,7 @@
 #include <mutex>
 #include <vector>
 #include "common.h"
+#include "voxel_grid.h"
 
 namespace pcgc {
 namespace {
@@ -120,84 +121,17 @@ __global__ void __launch_bounds__(256) mesh_quantize_kernel(const double* p, int
     if (!(r >= 0.0 && r <= (double)resolution)) return;                                     // unreachable for finite input
   }
   const int64_t key = (q[0] * G + q[1]) * G + q[2];
-  atomicOr(&bits[key >> 5], 1u << (key & 31));
+  set_bit(bits, key);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- bit set scan
-// The bit set is padded to a whole number of scan blocks (kScanWords words each) and zeroed, so the scan reads no bound.
-constexpr int kScanThreads = 256, kWordsPerThread = 16, kScanWords = kScanThreads * kWordsPerThread;
-
-__device__ __forceinline__ void load_words(const unsigned* bits, int64_t blk, unsigned w[kWordsPerThread]) {
-  const uint4* src = reinterpret_cast<const uint4*>(bits + blk * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
-#pragma unroll
-  for (int k = 0; k < kWordsPerThread / 4; ++k) {
-    const uint4 u = src[k];
-    w[4 * k] = u.x; w[4 * k + 1] = u.y; w[4 * k + 2] = u.z; w[4 * k + 3] = u.w;
-  }
-}
-
-// exclusive prefix of v over the workgroup's threads (in thread order) and the workgroup total
-__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[kScanThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kScanThreads / 64; ++k) {
-    before += k < wave ? wsum[k] : 0u;
-    all += wsum[k];
-  }
-  *total = all;
-  return before + incl - v;
-}
-
-__global__ void __launch_bounds__(kScanThreads) bits_count_kernel(const unsigned* bits, int64_t* block_count) {
-  unsigned w[kWordsPerThread];
-  load_words(bits, blockIdx.x, w);
-  unsigned c = 0;
-#pragma unroll
-  for (int k = 0; k < kWordsPerThread; ++k) c += __popc(w[k]);
-  unsigned total;
-  block_scan(c, &total);
-  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// exclusive prefix of the per-block counts in place, the sum in *n_set: one workgroup, each thread a contiguous run
-__global__ void __launch_bounds__(1024) bits_block_scan_kernel(int64_t* block_count, int64_t nblk, int64_t* n_set) {
-  __shared__ int64_t part[1024];
-  const int64_t per = (nblk + 1023) / 1024;
-  const int64_t b0 = std::min<int64_t>(nblk, (int64_t)threadIdx.x * per), b1 = std::min<int64_t>(nblk, b0 + per);
-  int64_t s = 0;
-  for (int64_t b = b0; b < b1; ++b) s += block_count[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t acc = 0;
-    for (int t = 0; t < 1024; ++t) { const int64_t x = part[t]; part[t] = acc; acc += x; }
-    *n_set = acc;
-  }
-  __syncthreads();
-  int64_t acc = part[threadIdx.x];
-  for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
-}
-
 // every set bit in key order: voxelize writes the cell's coordinates (int32 x, y, z of the G^3 grid), the normals path
 // its key.  Writes stop at cap (the callers size cap to the number of input points, which bounds the set bits).
 template <bool kCoords>
 __global__ void __launch_bounds__(kScanThreads) bits_compact_kernel(const unsigned* bits, const int64_t* block_offset, int64_t G,
                                                                     int64_t cap, int32_t* coords, int64_t* keys) {
   unsigned w[kWordsPerThread];
-  load_words(bits, blockIdx.x, w);
-  unsigned c = 0;
-#pragma unroll
-  for (int k = 0; k < kWordsPerThread; ++k) c += __popc(w[k]);
+  const unsigned c = load_words(bits, blockIdx.x, w);
   unsigned total;
   int64_t o = block_offset[blockIdx.x] + block_scan(c, &total);
   if (c == 0) return;
@@ -223,21 +157,6 @@ __global__ void __launch_bounds__(kScanThreads) bits_compact_kernel(const unsign
 }
 
 // ---------------------------------------------------------------------------------------------------------------- normals
-__global__ void __launch_bounds__(256) normals_bitset_kernel(const int32_t* p, int64_t n, int res, unsigned* bits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-  if ((unsigned)x >= (unsigned)res || (unsigned)y >= (unsigned)res || (unsigned)z >= (unsigned)res) return;
-  const int64_t key = ((int64_t)x * res + y) * res + z;
-  atomicOr(&bits[key >> 5], 1u << (key & 31));
-}
-
-__device__ __forceinline__ bool occupied(const unsigned* bits, int res, int x, int y, int z) {
-  if ((unsigned)x >= (unsigned)res || (unsigned)y >= (unsigned)res || (unsigned)z >= (unsigned)res) return false;
-  const int64_t key = ((int64_t)x * res + y) * res + z;
-  return (bits[key >> 5] >> (key & 31)) & 1u;
-}
-
 // cyclic Jacobi on the symmetric 3x3 a (destroyed): eigenvalues on the diagonal, eigenvectors in the columns of v
 __device__ void jacobi3(double a[3][3], double v[3][3]) {
   for (int r = 0; r < 3; ++r)
@@ -341,7 +260,7 @@ __global__ void __launch_bounds__(256) normals_kernel(const unsigned* bits, cons
     if (!__any(need)) break;
     const int e = table[j];
     const int dx = (e & 63) - 32, dy = ((e >> 6) & 63) - 32, dz = ((e >> 12) & 63) - 32;
-    if (need && occupied(bits, res, x + dx, y + dy, z + dz)) {
+    if (need && bit_at(bits, res, x + dx, y + dy, z + dz)) {
       ++K;
       sx += dx; sy += dy; sz += dz;
       qxx += dx * dx; qxy += dx * dy; qxz += dx * dz; qyy += dy * dy; qyz += dy * dz; qzz += dz * dz;
@@ -366,15 +285,10 @@ __global__ void __launch_bounds__(256) normals_gather_kernel(const int32_t* p, i
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-  const int64_t key = ((int64_t)x * res + y) * res + z;
+  const int64_t key = cell_of(res, x, y, z);
   const int64_t nc = *n_cells;
-  int64_t lo = 0, hi = nc;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ukeys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  const bool found = (unsigned)x < (unsigned)res && (unsigned)y < (unsigned)res && (unsigned)z < (unsigned)res && lo < nc &&
-                     ukeys[lo] == key;
+  const int64_t lo = find_sorted_key(ukeys, nc, key);
+  const bool found = in_grid(res, x, y, z) && lo < nc && ukeys[lo] == key;
   for (int k = 0; k < 3; ++k) normals[i * 3 + k] = found ? unormals[lo * 3 + k] : 0.f;
   if (cov) {
     for (int k = 0; k < 6; ++k) cov[i * 6 + k] = found ? ucov[lo * 6 + k] : 0;
@@ -408,10 +322,6 @@ const std::vector<int32_t>& offset_table(int r2) {
 
 int radius2(double radius) { return (int)std::floor(radius * radius); }
 
-int64_t scan_blocks(int64_t cells) { return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32); }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace pcgc
 
@@ -433,7 +343,7 @@ int pcgc_mesh_sample(const double* vertices, int64_t n_vertices, const int32_t* 
 size_t pcgc_mesh_voxelize_workspace_bytes(int resolution) {
   if (resolution < 1 || resolution > 4095) return 0;
   const int64_t G = resolution + 1, nblk = scan_blocks(G * G * G);
-  return align256((size_t)nblk * kScanWords * sizeof(unsigned)) + align256((size_t)nblk * sizeof(int64_t)) +
+  return align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) +
          align256(2 * kMinMaxBlocks * sizeof(double)) + 256;
 }
 
@@ -447,20 +357,20 @@ int pcgc_mesh_voxelize(const double* points, int64_t n, int resolution, int32_t*
   const int64_t G = resolution + 1, nblk = scan_blocks(G * G * G);
   char* w = static_cast<char*>(workspace);
   unsigned* bits = reinterpret_cast<unsigned*>(w);
-  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  w += align256(padded_bits_bytes(nblk));
   int64_t* block_count = reinterpret_cast<int64_t*>(w);
   w += align256((size_t)nblk * sizeof(int64_t));
   double* partial = reinterpret_cast<double*>(w);
   w += align256(2 * kMinMaxBlocks * sizeof(double));
   double* mm = reinterpret_cast<double*>(w);
-  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)nblk * kScanWords * sizeof(unsigned), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, padded_bits_bytes(nblk), s));
   const int64_t m = 3 * n;
   const int nb = (int)std::min<int64_t>(kMinMaxBlocks, (m + 255) / 256);
   hipLaunchKernelGGL(mesh_minmax_partial_kernel, dim3(nb), dim3(256), 0, s, points, m, partial);
   hipLaunchKernelGGL(mesh_minmax_final_kernel, dim3(1), dim3(64), 0, s, partial, nb, mm);
   hipLaunchKernelGGL(mesh_quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, mm, resolution, bits);
-  hipLaunchKernelGGL(bits_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
-  hipLaunchKernelGGL(bits_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_out);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_out);
   hipLaunchKernelGGL(bits_compact_kernel<true>, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count, G, cap, out,
                      (int64_t*)nullptr);
   return launch_ok("mesh voxelize kernels");
@@ -475,7 +385,7 @@ size_t pcgc_normals_workspace_bytes(int res, int64_t n, double radius) {
   if (res < 1 || res > 4096 || n < 0 || !(radius >= 0.0 && radius <= 16.0)) return 0;
   const int64_t nblk = scan_blocks((int64_t)res * res * res);
   const size_t nt = offset_table(radius2(radius)).size();
-  return align256((size_t)nblk * kScanWords * sizeof(unsigned)) + align256((size_t)nblk * sizeof(int64_t)) + 256 +
+  return align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) + 256 +
          align256((size_t)n * sizeof(int64_t)) + align256((size_t)n * 3 * sizeof(float)) +
          align256((size_t)n * 6 * sizeof(int64_t)) + align256((size_t)n * sizeof(int32_t)) + align256(nt * sizeof(int32_t));
 }
@@ -491,7 +401,7 @@ int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radi
   const int64_t nblk = scan_blocks((int64_t)res * res * res);
   char* w = static_cast<char*>(workspace);
   unsigned* bits = reinterpret_cast<unsigned*>(w);
-  w += align256((size_t)nblk * kScanWords * sizeof(unsigned));
+  w += align256(padded_bits_bytes(nblk));
   int64_t* block_count = reinterpret_cast<int64_t*>(w);
   w += align256((size_t)nblk * sizeof(int64_t));
   int64_t* n_cells = reinterpret_cast<int64_t*>(w);
@@ -506,11 +416,11 @@ int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radi
   w += align256((size_t)n * sizeof(int32_t));
   int32_t* dtable = reinterpret_cast<int32_t*>(w);
   PCGC_CHECK_HIP(hipMemcpyAsync(dtable, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)nblk * kScanWords * sizeof(unsigned), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, padded_bits_bytes(nblk), s));
   const unsigned grid = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(normals_bitset_kernel, dim3(grid), dim3(256), 0, s, points, n, res, bits);
-  hipLaunchKernelGGL(bits_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
-  hipLaunchKernelGGL(bits_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_cells);
+  hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, bits);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_cells);
   hipLaunchKernelGGL(bits_compact_kernel<false>, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count, (int64_t)res, n,
                      (int32_t*)nullptr, ukeys);
   hipLaunchKernelGGL(normals_kernel, dim3(grid), dim3(256), 0, s, bits, ukeys, n_cells, res, dtable, (int)table.size(), max_nn,

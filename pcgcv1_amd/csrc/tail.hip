@@ -1,5 +1,5 @@
 // Decoder-tail and loss kernels (gfx950): adaptive top-k threshold, BCE sums,
-// device voxelisation.
+// device voxelisation, D1 / D2 distortion (on the voxel grid of voxel_grid.h).
 //
 //   dataprocess/inout_points.py:147-179  select_voxels / get_adaptive_thres
 //   loss.py:8-33                         get_bce_loss
@@ -9,6 +9,7 @@
 #include <algorithm>
 #include "loss_sums.h"
 #include "common.h"
+#include "voxel_grid.h"
 
 namespace pcgc {
 
@@ -216,25 +217,9 @@ __global__ void voxelize_points_kernel(const int32_t* pts, const int32_t* cube_o
 // ---------------------------------------------------------------------------
 // D1 (point-to-point) geometry distortion, as MPEG pc_error computes it for the reference's eval
 // (myutils/pc_error_wrapper.py:26-75, eval.py:194-207): mean over A of the squared distance to the nearest
-// point of B.  Clouds are voxelised (integer coordinates < res), so B becomes an occupancy bit set and every
-// point of A searches Chebyshev shells of growing radius; after shell w every unvisited cell is farther than w,
-// so the search stops as soon as best <= (w+1)^2.  Exact; typical reconstructions need w <= 2.
+// point of B.  Clouds are voxelised (integer coordinates < res), so B becomes an occupancy bit set and every point of A
+// searches it with nearest_d2 (voxel_grid.h).  Exact.
 // ---------------------------------------------------------------------------
-__global__ void bitset_build_kernel(const int32_t* p, int64_t n, int res, unsigned* bits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-  if ((unsigned)x >= (unsigned)res || (unsigned)y >= (unsigned)res || (unsigned)z >= (unsigned)res) return;
-  const int64_t idx = ((int64_t)x * res + y) * res + z;
-  atomicOr(&bits[idx >> 5], 1u << (idx & 31));
-}
-
-__device__ __forceinline__ bool bit_at(const unsigned* bits, int res, int x, int y, int z) {
-  if ((unsigned)x >= (unsigned)res || (unsigned)y >= (unsigned)res || (unsigned)z >= (unsigned)res) return false;
-  const int64_t idx = ((int64_t)x * res + y) * res + z;
-  return (bits[idx >> 5] >> (idx & 31)) & 1u;
-}
-
 constexpr int kD1Blocks = 1024;
 
 __global__ void __launch_bounds__(256) d1_partial_kernel(const int32_t* pa, int64_t na, const unsigned* bits, int res,
@@ -244,23 +229,7 @@ __global__ void __launch_bounds__(256) d1_partial_kernel(const int32_t* pa, int6
   unsigned worst = 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < na; i += (int64_t)gridDim.x * 256) {
     const int x = pa[i * 3], y = pa[i * 3 + 1], z = pa[i * 3 + 2];
-    unsigned best = 0xFFFFFFFFu;
-    for (int w = 0; w < 2 * res; ++w) {
-      for (int dx = -w; dx <= w; ++dx)
-        for (int dy = -w; dy <= w; ++dy) {
-          const bool edge = (dx == -w || dx == w || dy == -w || dy == w);
-          const unsigned dxy = (unsigned)(dx * dx + dy * dy);
-          if (dxy >= best) continue;
-          if (edge) {
-            for (int dz = -w; dz <= w; ++dz)
-              if (bit_at(bits, res, x + dx, y + dy, z + dz)) best = min(best, dxy + (unsigned)(dz * dz));
-          } else {
-            if (bit_at(bits, res, x + dx, y + dy, z - w)) best = min(best, dxy + (unsigned)(w * w));
-            if (bit_at(bits, res, x + dx, y + dy, z + w)) best = min(best, dxy + (unsigned)(w * w));
-          }
-        }
-      if (best <= (unsigned)((w + 1) * (w + 1))) break;
-    }
+    const unsigned best = nearest_d2(bits, res, x, y, z);
     acc += (double)best;
     worst = max(worst, best);
   }
@@ -294,56 +263,13 @@ __global__ void d1_final_kernel(const double* partial, int nb, int64_t na, const
 // The target cloud is given sorted by linear key so that a grid cell maps to its point index by binary search.
 // Normal sums use 64-bit fixed-point integer atomics (exact, order-free), so the result is reproducible.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned nn_best_d2(const unsigned* bits, int res, int x, int y, int z) {
-  unsigned best = 0xFFFFFFFFu;
-  for (int w = 0; w < 2 * res; ++w) {
-    for (int dx = -w; dx <= w; ++dx)
-      for (int dy = -w; dy <= w; ++dy) {
-        const bool edge = (dx == -w || dx == w || dy == -w || dy == w);
-        const unsigned dxy = (unsigned)(dx * dx + dy * dy);
-        if (dxy >= best) continue;
-        if (edge) {
-          for (int dz = -w; dz <= w; ++dz)
-            if (bit_at(bits, res, x + dx, y + dy, z + dz)) best = min(best, dxy + (unsigned)(dz * dz));
-        } else {
-          if (bit_at(bits, res, x + dx, y + dy, z - w)) best = min(best, dxy + (unsigned)(w * w));
-          if (bit_at(bits, res, x + dx, y + dy, z + w)) best = min(best, dxy + (unsigned)(w * w));
-        }
-      }
-    if (best <= (unsigned)((w + 1) * (w + 1))) break;
-  }
-  return best;
-}
-
-__device__ __forceinline__ int64_t find_key(const int64_t* keys, int64_t n, int64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;          // caller guarantees presence (the bit is set)
-}
-
 // calls f(j, ex, ey, ez) for every target point j at squared distance `best` from (x, y, z); e = p - q
 template <typename F>
 __device__ __forceinline__ void for_each_tied(const unsigned* bits, const int64_t* keys, int64_t nq, int res, int x, int y, int z,
                                               unsigned best, F f) {
-  const int r = (int)sqrtf((float)best) + 1;
-  for (int dx = -r; dx <= r; ++dx)
-    for (int dy = -r; dy <= r; ++dy) {
-      const int rest = (int)best - dx * dx - dy * dy;
-      if (rest < 0) continue;
-      int dz = (int)sqrtf((float)rest);
-      while (dz * dz > rest) --dz;
-      while ((dz + 1) * (dz + 1) <= rest) ++dz;
-      if (dz * dz != rest) continue;
-      for (int sgn = 0; sgn < (dz ? 2 : 1); ++sgn) {
-        const int qz = sgn ? z - dz : z + dz;
-        if (!bit_at(bits, res, x + dx, y + dy, qz)) continue;
-        const int64_t key = ((int64_t)(x + dx) * res + (y + dy)) * res + qz;
-        f(find_key(keys, nq, key), -dx, -dy, z - qz);
-      }
-    }
+  for_each_at_distance(bits, res, x, y, z, best, [&](int dx, int dy, int qz) {
+    f(find_sorted_key(keys, nq, cell_of(res, x + dx, y + dy, qz)), -dx, -dy, z - qz);     // present: the bit is set
+  });
 }
 
 constexpr double kNormalFix = 1099511627776.0;      // 2^40 fixed point for the normal sums
@@ -352,7 +278,7 @@ __global__ void __launch_bounds__(256) d2_transfer_kernel(const int32_t* p, int6
                                                           const int64_t* qkeys, int64_t nq, int res, long long* sums, int* counts) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
     const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-    const unsigned best = nn_best_d2(bits, res, x, y, z);
+    const unsigned best = nearest_d2(bits, res, x, y, z);
     long long fx[3];
     for (int c = 0; c < 3; ++c) fx[c] = (long long)llrint((double)normals_p[i * 3 + c] * kNormalFix);
     for_each_tied(bits, qkeys, nq, res, x, y, z, best, [&](int64_t j, int, int, int) {
@@ -376,7 +302,7 @@ __global__ void __launch_bounds__(256) d2_partial_kernel(const int32_t* p, int64
   double acc = 0.0, worst = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
     const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-    const unsigned best = nn_best_d2(bits, res, x, y, z);
+    const unsigned best = nearest_d2(bits, res, x, y, z);
     double s = 0.0;
     int cnt = 0;
     for_each_tied(bits, qkeys, nq, res, x, y, z, best, [&](int64_t j, int ex, int ey, int ez) {
@@ -409,12 +335,6 @@ __global__ void d2_final_kernel(const double* partial, const double* partial_max
     out2[0] = s / (double)np;
     out2[1] = m;
   }
-}
-
-__global__ void bitset_from_keys_kernel(const int64_t* keys, int64_t n, unsigned* bits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  atomicOr(&bits[keys[i] >> 5], 1u << (keys[i] & 31));
 }
 
 }  // namespace pcgc
@@ -518,7 +438,7 @@ int pcgc_d1_mse(const int32_t* pa, int64_t na, const int32_t* pb, int64_t nb, in
   unsigned* maxd = reinterpret_cast<unsigned*>(partial + kD1Blocks);
   PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, words * sizeof(unsigned), s));
   PCGC_CHECK_HIP(hipMemsetAsync(maxd, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(bitset_build_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, pb, nb, res, bits);
+  hipLaunchKernelGGL(bits_from_points_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, pb, nb, res, bits);
   int blocks = (int)((na + 255) / 256);
   if (blocks > kD1Blocks) blocks = kD1Blocks;
   hipLaunchKernelGGL(d1_partial_kernel, dim3(blocks), dim3(256), 0, s, pa, na, bits, res, partial, maxd);
@@ -541,7 +461,8 @@ static int d2_layout(int res, int64_t nq, const int64_t* qkeys, void* workspace,
   *counts = reinterpret_cast<int*>(*sums + 3 * nq);
   *partial = reinterpret_cast<double*>(reinterpret_cast<char*>(*counts) + (((size_t)nq * sizeof(int) + 15) & ~(size_t)15));
   PCGC_CHECK_HIP(hipMemsetAsync(*bits, 0, words * sizeof(unsigned), s));
-  hipLaunchKernelGGL(bitset_from_keys_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, qkeys, nq, *bits);
+  hipLaunchKernelGGL(bits_from_keys_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, qkeys, nq,
+                     (int64_t)res * res * res, *bits);
   return 0;
 }
 

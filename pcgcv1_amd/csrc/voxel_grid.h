@@ -1,0 +1,182 @@
+// The voxel grid the D1 / D2 kernels (tail.hip), the colour kernels (color.hip) and the mesh kernels (mesh.hip) share:
+// a cloud of integer points < res per axis as an occupancy bit set over res^3 cells, bit (x*res + y)*res + z of a flat
+// array of 32-bit words (the cell's linear key: ascending keys are np.unique's lexicographic order).  One copy each of
+//   * addressing: cell_of, in_grid, bit_at, and the two kernels that fill a zeroed bit set;
+//   * nearest_d2: the exact squared distance to the nearest occupied cell, by Chebyshev shells;
+//   * for_each_at_distance: every occupied cell at that distance, in a fixed order (the callers' float sums follow it);
+//   * the popcount scan that turns a bit set into per-block offsets of its set bits in key order;
+//   * find_sorted_key: lower bound in a sorted key list.
+// Everything here has internal linkage: the three objects link into one library.
+#pragma once
+#include <algorithm>
+#include "common.h"
+
+namespace pcgc {
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- addressing
+__device__ __forceinline__ int64_t cell_of(int res, int x, int y, int z) { return ((int64_t)x * res + y) * res + z; }
+
+__device__ __forceinline__ bool in_grid(int res, int x, int y, int z) {
+  return (unsigned)x < (unsigned)res && (unsigned)y < (unsigned)res && (unsigned)z < (unsigned)res;
+}
+
+// false outside the grid
+__device__ __forceinline__ bool bit_at(const unsigned* bits, int res, int x, int y, int z) {
+  if (!in_grid(res, x, y, z)) return false;
+  const int64_t idx = cell_of(res, x, y, z);
+  return (bits[idx >> 5] >> (idx & 31)) & 1u;
+}
+
+__device__ __forceinline__ void set_bit(unsigned* bits, int64_t idx) { atomicOr(&bits[idx >> 5], 1u << (idx & 31)); }
+
+// one thread per point (int32 x, y, z) or per linear key; what lies outside the grid sets nothing
+__global__ void __launch_bounds__(256) bits_from_points_kernel(const int32_t* p, int64_t n, int res, unsigned* bits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+  if (in_grid(res, x, y, z)) set_bit(bits, cell_of(res, x, y, z));
+}
+
+__global__ void __launch_bounds__(256) bits_from_keys_kernel(const int64_t* keys, int64_t n, int64_t cells, unsigned* bits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t idx = keys[i];
+  if (idx >= 0 && idx < cells) set_bit(bits, idx);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- search
+constexpr unsigned kNoCell = 0xFFFFFFFFu;
+
+// Squared distance from (x, y, z) to the nearest occupied cell; kNoCell when 2 res shells hold none (an empty set: the
+// callers that can meet one skip the walk).  Shell w is the surface of the cube of half-width w; after it every unvisited
+// cell is farther than w, so the search stops as soon as best <= (w+1)^2.  Exact; typical reconstructions need w <= 2.
+__device__ __forceinline__ unsigned nearest_d2(const unsigned* bits, int res, int x, int y, int z) {
+  unsigned best = kNoCell;
+  for (int w = 0; w < 2 * res; ++w) {
+    for (int dx = -w; dx <= w; ++dx)
+      for (int dy = -w; dy <= w; ++dy) {
+        const bool edge = (dx == -w || dx == w || dy == -w || dy == w);
+        const unsigned dxy = (unsigned)(dx * dx + dy * dy);
+        if (dxy >= best) continue;
+        if (edge) {
+          for (int dz = -w; dz <= w; ++dz)
+            if (bit_at(bits, res, x + dx, y + dy, z + dz)) best = min(best, dxy + (unsigned)(dz * dz));
+        } else {
+          if (bit_at(bits, res, x + dx, y + dy, z - w)) best = min(best, dxy + (unsigned)(w * w));
+          if (bit_at(bits, res, x + dx, y + dy, z + w)) best = min(best, dxy + (unsigned)(w * w));
+        }
+      }
+    if (best <= (unsigned)((w + 1) * (w + 1))) break;
+  }
+  return best;
+}
+
+// Calls f(dx, dy, qz) for every occupied cell (x + dx, y + dy, qz) at squared distance `best` from (x, y, z): ties are
+// kept.  Order: dx ascending, dy ascending, then z + dz before z - dz.  `best` is what nearest_d2 found, not kNoCell.
+template <typename F>
+__device__ __forceinline__ void for_each_at_distance(const unsigned* bits, int res, int x, int y, int z, unsigned best, F f) {
+  const int r = (int)sqrtf((float)best) + 1;
+  for (int dx = -r; dx <= r; ++dx)
+    for (int dy = -r; dy <= r; ++dy) {
+      const int rest = (int)best - dx * dx - dy * dy;
+      if (rest < 0) continue;
+      int dz = (int)sqrtf((float)rest);
+      while (dz * dz > rest) --dz;
+      while ((dz + 1) * (dz + 1) <= rest) ++dz;
+      if (dz * dz != rest) continue;
+      for (int sgn = 0; sgn < (dz ? 2 : 1); ++sgn) {
+        const int qz = sgn ? z - dz : z + dz;
+        if (bit_at(bits, res, x + dx, y + dy, qz)) f(dx, dy, qz);
+      }
+    }
+}
+
+// first index whose key is not below `key` (n when there is none)
+__device__ __forceinline__ int64_t find_sorted_key(const int64_t* keys, int64_t n, int64_t key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- popcount scan
+// A bit set that is scanned is padded to a whole number of scan blocks (kScanWords words each) and zeroed, so the scan
+// reads no bound.  grid_count_kernel, then grid_block_scan_kernel, leave in block_count[b] the number of set bits before
+// scan block b; a consumer adds block_scan of its threads' popcounts to reach every word (color.hip's rank table,
+// mesh.hip's compaction).
+constexpr int kScanThreads = 256, kWordsPerThread = 16, kScanWords = kScanThreads * kWordsPerThread;
+
+// the calling thread's words of scan block blk; returns their popcount
+__device__ __forceinline__ unsigned load_words(const unsigned* bits, int64_t blk, unsigned w[kWordsPerThread]) {
+  const uint4* src = reinterpret_cast<const uint4*>(bits + blk * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
+  unsigned c = 0;
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread / 4; ++k) {
+    const uint4 u = src[k];
+    w[4 * k] = u.x; w[4 * k + 1] = u.y; w[4 * k + 2] = u.z; w[4 * k + 3] = u.w;
+    c += __popc(u.x) + __popc(u.y) + __popc(u.z) + __popc(u.w);
+  }
+  return c;
+}
+
+// exclusive prefix of v over the workgroup's threads (in thread order) and the workgroup total
+__device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* total) {
+  __shared__ unsigned wsum[kScanThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kScanThreads / 64; ++k) {
+    before += k < wave ? wsum[k] : 0u;
+    all += wsum[k];
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kScanThreads) grid_count_kernel(const unsigned* bits, int64_t* block_count) {
+  unsigned w[kWordsPerThread];
+  const unsigned c = load_words(bits, blockIdx.x, w);
+  unsigned total;
+  block_scan(c, &total);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// exclusive prefix of the per-block counts in place, the sum in *n_set: one workgroup, each thread a contiguous run
+__global__ void __launch_bounds__(1024) grid_block_scan_kernel(int64_t* block_count, int64_t nblk, int64_t* n_set) {
+  __shared__ int64_t part[1024];
+  const int64_t per = (nblk + 1023) / 1024;
+  const int64_t b0 = std::min<int64_t>(nblk, (int64_t)threadIdx.x * per), b1 = std::min<int64_t>(nblk, b0 + per);
+  int64_t s = 0;
+  for (int64_t b = b0; b < b1; ++b) s += block_count[b];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t acc = 0;
+    for (int t = 0; t < 1024; ++t) { const int64_t x = part[t]; part[t] = acc; acc += x; }
+    *n_set = acc;
+  }
+  __syncthreads();
+  int64_t acc = part[threadIdx.x];
+  for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
+}
+
+// host side: scan blocks of a grid of `cells` cells, bytes of its padded bit set, 256-byte rounding of a workspace part
+int64_t scan_blocks(int64_t cells) { return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32); }
+
+size_t padded_bits_bytes(int64_t nblk) { return (size_t)nblk * kScanWords * sizeof(unsigned); }
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+}  // namespace pcgc

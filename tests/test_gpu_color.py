@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _color_ref as ref                                                 # noqa: E402
+from _clouds import dense as _dense, faces as _faces                     # noqa: E402
 from pcgcv1_amd import _lib, metrics, synthetic                          # noqa: E402
 from pcgcv1_amd import recolor as rc                                     # noqa: E402
 from pcgcv1_amd.dataprocess import inout_points as iop                   # noqa: E402
@@ -20,29 +21,6 @@ from pcgcv1_amd.dataprocess import inout_points as iop                   # noqa:
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
     _lib.require_gpu()
-
-
-def _dense(seed, res, n):
-    rng = np.random.default_rng(seed)
-    p = np.unique(rng.integers(0, res, (n, 3)), axis=0).astype(np.int32)
-    p = p[rng.permutation(len(p))]
-    return p, rng.integers(0, 256, (len(p), 3)).astype(np.uint8)
-
-
-def _faces(seed, res, n):
-    """a cloud that touches all six faces of the grid: a coarse lattice that includes the eight corners, each point moved by up
-    to two cells (clipped, so the faces keep points), plus n random points near lattice points — the two clouds of a pair stay
-    within a few cells of each other, which keeps the shell search short at res 1024"""
-    rng = np.random.default_rng(seed)
-    axis = np.unique(np.r_[0:res:max(8, res // 8), res - 1])
-    lattice = np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), -1).reshape(-1, 3)
-    corners = lattice[np.all((lattice == 0) | (lattice == res - 1), 1)]
-    moved = lattice + rng.integers(-2, 3, lattice.shape)
-    extra = lattice[rng.integers(0, len(lattice), n)] + rng.integers(-3, 4, (n, 3))
-    p = np.unique(np.clip(np.concatenate([corners, moved, extra]), 0, res - 1), axis=0).astype(np.int32)
-    assert p.min(0).tolist() == [0, 0, 0] and p.max(0).tolist() == [res - 1] * 3
-    p = p[rng.permutation(len(p))]
-    return p, rng.integers(0, 256, (len(p), 3)).astype(np.uint8)
 
 
 def _cases():

@@ -1,5 +1,6 @@
 """Time recolouring and the colour distortion (csrc/color.hip) on the synthetic bench cloud's 205 cubes against its
-reconstruction under the a6 checkpoint, next to pcgc_d1_mse on the same pair (the same shell search, the yardstick).
+reconstruction under the a6 checkpoint, next to pcgc_d1_mse and the pcgc_d2_* calls on the same pair (the same shell search
+and tie walk, csrc/voxel_grid.h; the source carries seeded normals).
 
     python tools/bench_recolor.py [--reps 50] [--warmup 5] [--out FILE]
 
@@ -25,7 +26,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from pcgcv1_amd import _lib, synthetic
+    from pcgcv1_amd import _lib, metrics, synthetic
     from pcgcv1_amd import recolor as rc
     from pcgcv1_amd.models import model_voxception as model
     from pcgcv1_amd.process import postprocess_points, preprocess_points
@@ -47,7 +48,13 @@ def main():
     out = torch.empty(6, dtype=torch.float64, device=dev)
     ws = torch.empty(int(max(lib.pcgc_recolor_workspace_bytes(res, len(pts), len(cells)),
                              lib.pcgc_color_mse_workspace_bytes(res, max(len(pts), len(cells))),
-                             lib.pcgc_d1_workspace_bytes(res))), dtype=torch.uint8, device=dev)
+                             lib.pcgc_d1_workspace_bytes(res), lib.pcgc_d2_workspace_bytes(res, max(len(pts), len(cells))))),
+                     dtype=torch.uint8, device=dev)
+    # D2 takes both clouds in key order
+    (ks_d, order), (kt_d, order_t) = metrics._sorted_keys(s_d, res), metrics._sorted_keys(t_d, res)
+    ss_d, ts_d = s_d[order].contiguous(), t_d[order_t].contiguous()
+    ns_d = torch.from_numpy(np.random.default_rng(1301).normal(size=(len(pts), 3)).astype(np.float32)).to(dev)
+    nt_d = torch.empty((len(cells), 3), dtype=torch.float32, device=dev)
     st = _lib.stream()
 
     def recolor():
@@ -70,6 +77,18 @@ def main():
         _lib.check(lib.pcgc_d1_mse(_lib.dptr(t_d), len(cells), _lib.dptr(s_d), len(pts), res, _lib.dptr(out), _lib.dptr(ws), ws.numel(), st),
                    "pcgc_d1_mse")
 
+    def d2_transfer():
+        _lib.check(lib.pcgc_d2_transfer_normals(_lib.dptr(ss_d), len(pts), _lib.dptr(ns_d), _lib.dptr(kt_d), len(cells), res,
+                                                _lib.dptr(nt_d), _lib.dptr(ws), ws.numel(), st), "pcgc_d2_transfer_normals")
+
+    def d2_ab():
+        _lib.check(lib.pcgc_d2_mse(_lib.dptr(ss_d), len(pts), _lib.dptr(kt_d), len(cells), _lib.dptr(nt_d), res, _lib.dptr(out),
+                                   _lib.dptr(ws), ws.numel(), st), "pcgc_d2_mse")
+
+    def d2_ba():
+        _lib.check(lib.pcgc_d2_mse(_lib.dptr(ts_d), len(cells), _lib.dptr(ks_d), len(pts), _lib.dptr(ns_d), res, _lib.dptr(out),
+                                   _lib.dptr(ws), ws.numel(), st), "pcgc_d2_mse")
+
     def timed(fn):
         for _ in range(a.warmup):
             fn()
@@ -88,6 +107,9 @@ def main():
          "workspace_MB": round(lib.pcgc_recolor_workspace_bytes(res, len(pts), len(cells)) / 2 ** 20, 1)}
     r["pcgc_d1_mse A->B"] = timed(d1_ab)
     r["pcgc_d1_mse B->A"] = timed(d1_ba)
+    r["pcgc_d2_transfer_normals A->B"] = timed(d2_transfer)
+    r["pcgc_d2_mse A->B"] = timed(d2_ab)
+    r["pcgc_d2_mse B->A"] = timed(d2_ba)
     r["pcgc_recolor"] = timed(recolor)
     r["pcgc_color_mse A->B"] = timed(color_mse_ab)
     r["pcgc_color_mse B->A"] = timed(color_mse_ba)
