@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/pcgc.h"
+#include "net_plan.h"      // kSkipLaunches, kSkipLaunchesMid, kSegLaunches, kSegMaxChunk
 
 namespace pcgc {
 
@@ -135,8 +136,6 @@ struct TileCfg {
   int need = 0;
 };
 constexpr unsigned kTileUnread = 0x80000000u;
-constexpr int kSkipLaunches = 8;                // conv_in, A / BC of the three C = 16 blocks, down_1
-constexpr int kSkipLaunchesMid = 6;             // A / BC of the three C = 32 blocks (32^3 stage of the analysis)
 // Tile orders of every chunk of `chunk` cubes among `total` cubes for the n_cfg launch configurations of a stage, in one
 // launch: chunk k (first cube c0 = k * chunk, n cubes) gets order + (c0 * n_cfg + cfg * n) * tiles_cap, n_heavy[k * n_cfg + cfg]
 // and — 64^3 stage — the table virt + (c0 * n_cfg + cfg * n) * 64 of rows that lie in its empty tiles (RowSkip::in_virtual).
@@ -176,8 +175,6 @@ struct ConvInSegArgs {
   int relu = 0;
 };
 int launch_conv_in_seg(const ConvInSegArgs& a, int max_slots, hipStream_t s);
-constexpr int kSegMaxChunk = 48;                // cubes per launch of the segment form (slot codes hold the cube above bit 10)
-constexpr int kSegLaunches = 7;                 // conv_in, kernel A / BC of the three C = 16 blocks
 // voxel occupancy words of B cubes (occ[(b * 64 + d) * 64 + h] bit w) + the row words launch_rowocc writes; slot lists, counts
 // and "not written" tables of every chunk for the kSegLaunches launches (vrn_seg.hip: seg_order_kernel)
 int launch_voxocc(const float* x, unsigned long long* occ, unsigned long long* rowocc, int B, hipStream_t s);

@@ -1324,3 +1324,93 @@ def test_empty_space_skipping_is_exact_and_happens(monkeypatch):
             monkeypatch.setenv("PCGC_SKIP_EMPTY", mode)
             o1 = transform.compress_hyper(cubes, model, d)
             assert list(o0[0]) == list(o1[0]) and bytes(o0[4]) == bytes(o1[4]), mode
+
+
+# Frozen from commit 042b3e5 (the parent of the workspace-plan refactor of csrc/net.hip) on an MI355X.
+_PLAN_MODES = (("0", None), ("1", None), ("2", None), ("3", None), ("3", "1"))        # PCGC_SKIP_EMPTY, PCGC_SEG_COPY_EMPTY
+_PLAN_LATENTS_SHA = "00eb7807e16dad55511f24413f9de3f9395da3c4c06eb58f8d362399523740e2"
+_PLAN_SYNTHESIS_SHA = "cda786f4fbe98dc0a884d6e09b3dc0b5c1158ac40131bf6e7bfb78a8e541a28b"
+_PLAN_ROW_TILES = "409c8fe491f92a4ef0f0fe2da2058aa68b907343683e3c1e0c6f3ab9525179b6"
+_PLAN_SLOTS = "ad66e7622e70a66d790317bd2340e09474269234877149c49ab49b1d29933d68"
+_PLAN_LAUNCHES_SHA = {          # (PCGC_SKIP_EMPTY, PCGC_SEG_COPY_EMPTY) -> sha256 of the (layer, kernel, B, Din) rows, analysis then synthesis
+    ("0", None): _PLAN_ROW_TILES, ("1", None): _PLAN_ROW_TILES, ("2", None): _PLAN_ROW_TILES, ("3", None): _PLAN_SLOTS, ("3", "1"): _PLAN_SLOTS,
+}
+_PLAN_WORKSPACE_BYTES = {       # (net, B, D, PCGC_SKIP_EMPTY) -> pcgc_net_workspace_bytes, default chunk sizes; the parent's value beside it
+    ("analysis", 1, 64, "0"): 126968576,            # 126969684
+    ("analysis", 7, 64, "0"): 335129344,            # 335130444
+    ("analysis", 41, 64, "0"): 611883008,           # 611884148
+    ("analysis", 205, 64, "0"): 1655370240,         # 1655371332
+    ("analysis", 1, 64, "3"): 126968576,            # 126969684
+    ("analysis", 7, 64, "3"): 335129344,            # 335130444
+    ("analysis", 41, 64, "3"): 1485346816,          # 1485347956
+    ("analysis", 205, 64, "3"): 2360013312,         # 2360014404
+    ("synthesis", 7, 16, "3"): 235071624,           # 235071880
+    ("synthesis", 205, 16, "3"): 1335168984,        # 1335169240
+    ("hyper_encoder", 205, 16, "3"): 60457216,      # 60457216
+    ("hyper_decoder", 205, 8, "3"): 167936256,      # 167936256
+}
+
+
+def test_net_plan_is_the_parents(monkeypatch):
+    """The host-side plan of pcgc_net_forward (csrc/net_plan.h: workspace regions, chunk views, launch numbers) computes what
+    the hand-written layout before it computed.  Seven 64^3 cubes (five of the bench cloud, an empty one, a single voxel in
+    a corner) with PCGC_CHUNKS=2,3,5 give two super chunks (5 + 2), ragged last chunks at all three resolutions and
+    equal-size 64^3 chunks 2 / 2 / 1 and 2.  For every skip mode, on a poisoned workspace: (a) the analysis latents, (b) the
+    synthesis output for them, (c) the launch sequences of both transforms are the parent commit's, frozen as sha256; (d) the
+    workspace sizes are pinned, none above the parent's."""
+    import hashlib
+
+    def sha(t):
+        return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()
+
+    def launches(net, x):
+        net.set_profiling(True)
+        try:
+            y = net(x).clone()
+            torch.cuda.synchronize()
+            rows = ["%d %s %d %d" % (r["layer"], r["kernel"], r["B"], r["Din"]) for r in net.profile_report()]
+        finally:
+            net.set_profiling(False)
+        return y, rows
+
+    pts = synthetic.make_cloud(seed=1300)
+    cubes, _, _ = process.preprocess_points(pts, 1.0, 64, 64)
+    special = torch.zeros((2, 64, 64, 64, 1), device=cubes.device)
+    special[1, 0, 0, 0, 0] = 1.0
+    x = torch.cat([cubes[10:15], special], 0).contiguous()
+    c = transform.get_codec(model, "synthetic:77:dense")
+    ana, syn = c.analysis_transform, c.synthesis_transform
+    monkeypatch.setenv("PCGC_CHUNKS", "2,3,5")
+    got = {}
+    for mode, copy in _PLAN_MODES:
+        monkeypatch.setenv("PCGC_SKIP_EMPTY", mode)
+        if copy is None:
+            monkeypatch.delenv("PCGC_SEG_COPY_EMPTY", raising=False)
+        else:
+            monkeypatch.setenv("PCGC_SEG_COPY_EMPTY", copy)
+        ana(x), syn(ana(x))                                               # the workspaces exist: poison them
+        for net in (ana, syn):
+            for ws in net._ws.values():
+                ws.fill_(255)
+        y, rows_a = launches(ana, x)
+        xs, rows_s = launches(syn, y)
+        got[(mode, copy)] = (sha(y), sha(xs), hashlib.sha256("\n".join(rows_a + ["--"] + rows_s).encode()).hexdigest(), rows_a, rows_s)
+        print("plan mode %s copy %s: latents %s synthesis %s launches %s (%d + %d rows)" % (mode, copy, got[(mode, copy)][0], got[(mode, copy)][1],
+                                                                                           got[(mode, copy)][2], len(rows_a), len(rows_s)))
+    monkeypatch.delenv("PCGC_SEG_COPY_EMPTY", raising=False)
+    monkeypatch.delenv("PCGC_CHUNKS")
+    lib = _lib.hip()
+    sizes = {}
+    for name, net, shapes, modes in (("analysis", ana, [(1, 64), (7, 64), (41, 64), (205, 64)], ("0", "3")), ("synthesis", syn, [(7, 16), (205, 16)], ("3",)),
+                                     ("hyper_encoder", c.hyper_encoder, [(205, 16)], ("3",)), ("hyper_decoder", c.hyper_decoder, [(205, 8)], ("3",))):
+        for mode in modes:
+            monkeypatch.setenv("PCGC_SKIP_EMPTY", mode)
+            for B, D in shapes:
+                sizes[(name, B, D, mode)] = int(lib.pcgc_net_workspace_bytes(net._handle, B, D))
+                print("plan workspace %r: %d," % ((name, B, D, mode), sizes[(name, B, D, mode)]))
+    for key in _PLAN_MODES:
+        y_sha, xs_sha, l_sha, rows_a, rows_s = got[key]
+        assert y_sha == _PLAN_LATENTS_SHA, key
+        assert xs_sha == _PLAN_SYNTHESIS_SHA, key
+        assert l_sha == _PLAN_LAUNCHES_SHA[key], (key, rows_a, rows_s)
+    assert sizes == _PLAN_WORKSPACE_BYTES
