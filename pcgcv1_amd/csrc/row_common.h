@@ -1,7 +1,9 @@
-// Device helpers shared by the row kernels on v_mfma_f32_4x4x1_16B_f32 (vrn_row.hip: 64^3 / C = 16, vrn_row32.hip:
-// 32^3 / C = 32): the 16-block MFMA with A broadcast (cbsz = 4, abid = k), DPP lane shifts, raw buffer loads / stores
-// whose out-of-range offsets read zeros / drop the store.  See vrn_row.hip for the mapping.
+// Device helpers shared by the row kernels on v_mfma_f32_4x4x1_16B_f32 (vrn_row.hip / vrn_seg.hip: 64^3 / C = 16,
+// vrn_row32.hip: 32^3 / C = 32, vrn_row16.hip: 16^3 / C = 64): the 16-block MFMA with A broadcast (cbsz = 4, abid = k), DPP
+// lane shifts, raw buffer loads / stores whose out-of-range offsets read zeros / drop the store, the 3^3 tap walk of the 64^3
+// kernels and the role rotation of the plane loops.  See vrn_row.hip for the mapping.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace pcgc {
@@ -82,6 +84,112 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v) {
   return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
 }
 __device__ __forceinline__ float comp(const f32x4& v, int c) { return v[c]; }
+// on a lambda handed to one of the templates below: its body belongs into the unrolled nest whatever the inliner's cost model says
+// (left to that model, loops around it stay rolled: -Wpass-failed)
+#define PCGC_INLINE __attribute__((always_inline))
+
+// ---------------------------------------------------------------------------------------------------------------
+// The 3^3 tap walk of the 64^3 kernels (vrn_row.hip, vrn_seg.hip), written once.  A wave holds TH rows of three output
+// planes in three accumulator sets and reads input planes one at a time: input plane p feeds the output planes p - 1, p,
+// p + 1 (kd = 2, 1, 0), held in sets P0, P1, P2 (vJ: set J takes part — wave-uniform, ONE branch per set), and its row r (of
+// TH + 2: one halo row on either side) feeds output row jr = r - kh.  For NC channels of that plane the walk calls
+//   mac(set, jr, r, kw, tap, born, c)   for every (c, r, kh, kw) that lands on one of the TH output rows, then
+//   rider(j, c)                         once per (output plane j = 0, 1, 2, channel): a 1^3 layer riding in plane j's branch
+// so every accumulator receives its contributions in the order (plane, channel, kh, kw), the planes coming from the kernel's
+// plane loop.  tap = (kd * 3 + kh) * NKW + kw (NKW = 1: the site folds kw into its MFMA rows, deconv_out).  born (FRESH only):
+// this is the first (channel, kh) that reaches accumulator row jr of set P2, the plane that gets its first contribution
+// (kd = 0) in this step — with the site's own "first kw" test, the MFMA that takes the bias as its C operand (mfa_new)
+// instead of the stale accumulator: no initialisation moves.
+// Call it from a function under the kernel (a_quad, bc_channel12, a step's quad lambda).  Where the nest sits in the kernel's
+// own body (conv_in, vrn16bc_bwd_row_kernel) it stays written out: the compiler optimises the walk with the site's closure on
+// its own before it becomes part of the caller, and a kernel that never had a function there comes out with another schedule.
+// ---------------------------------------------------------------------------------------------------------------
+struct NoRider {
+  __device__ __forceinline__ void operator()(int, int) const {}
+};
+template <int TH, int P0, int P1, int P2, bool FRESH = false, int NKW = 3, int NC = 1, class MAC, class RIDER = NoRider>
+__device__ __forceinline__ void tap_walk(bool v0, bool v1, bool v2, MAC mac, RIDER rider = RIDER()) {
+  const bool vj[3] = {v0, v1, v2};
+  constexpr int P[3] = {P0, P1, P2};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int kd = 2 - j;                      // input plane p feeds output plane p + 1 - kd = p - 1 + j
+    if (vj[j]) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+#pragma unroll
+        for (int r = 0; r < TH + 2; ++r)
+#pragma unroll
+          for (int kh = 0; kh < 3; ++kh) {
+            const int jr = r - kh;
+            if (jr >= 0 && jr < TH) {
+#pragma unroll
+              for (int kw = 0; kw < NKW; ++kw) mac(P[j], jr, r, kw, (kd * 3 + kh) * NKW + kw, FRESH && c == 0 && j == 2 && kh == 0, c);
+            }
+          }
+        rider(j, c);
+      }
+    }
+  }
+}
+
+// The driver of a plane loop whose accumulator sets keep their registers: the ROLES rotate instead.  step(p, R0, R1, R2) runs
+// for p = first, first + 1, ... while `p cmp bound` (cmp: < or <=), unrolled three times, with R0 / R1 / R2 = integral
+// constants naming the set that plays the step's first / second / third role.  Forward (back = false; the 3^3 kernels: roles = output planes p - 1, p, p + 1) the set that
+// was second becomes first; back = true (up2_row_kernel: roles = output planes 2p, 2p + 1, 2p + 2) the set that was third does.
+// A macro, not a template: a function that takes the kernel's step closure is optimised on its own, with the three step
+// bodies inlined into it and the kernel's registers behind pointers, BEFORE it becomes part of the kernel, and the kernels
+// come out with other schedules and register allocations (tried by value, by reference, with constant bounds).
+using I0 = std::integral_constant<int, 0>;
+using I1 = std::integral_constant<int, 1>;
+using I2 = std::integral_constant<int, 2>;
+template <bool BACK, class FWD, class BWD>
+using RotateRole = std::conditional_t<BACK, BWD, FWD>;
+#define PCGC_ROTATE3(first, cmp, bound, step, back)                                                                      \
+  _Pragma("unroll 1") for (int p_ = (first); p_ cmp (bound); p_ += 3) {                                                   \
+    step(p_, I0{}, I1{}, I2{});                                                                                          \
+    if (!(p_ + 1 cmp (bound))) break;                                                                                    \
+    step(p_ + 1, RotateRole<back, I1, I2>{}, RotateRole<back, I2, I0>{}, RotateRole<back, I0, I1>{});                    \
+    if (!(p_ + 2 cmp (bound))) break;                                                                                    \
+    step(p_ + 2, RotateRole<back, I2, I1>{}, RotateRole<back, I0, I2>{}, RotateRole<back, I1, I0>{});                    \
+  }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Kernel BC of the C = 16 block at 64^3, one input channel ci of conv1_2 (4 -> 8; weights [27][4][8]: VGPR tap >> 1, abid =
+// (tap & 1) * 8 + ci * 2 + half) / conv2_2 (4 -> 4; [27][4][4]: VGPR tap >> 2, abid = (tap & 3) * 4 + ci), for the row
+// kernel and the segment kernel alike.  rows(r, ci, x0, xm, xp) is the site's shift source: channel ci of input row r and
+// its kw = 0 / 2 neighbours (vrn_row.hip: wave shifts with zero fill, vrn_seg.hip: shifts inside a slot with edge values).
+// P0, P1, P2: which of the three accumulator sets holds output plane p-1, p, p+1 in this step (PCGC_ROTATE3: the sets
+// never move between registers).  FRESH: this call holds the first tap that reaches each accumulator of set P2 (tap_walk: born).
+// ---------------------------------------------------------------------------------------------------------------
+template <int TH, int P0, int P1, int P2, bool FRESH, class ROWS>
+__device__ __forceinline__ void bc_channel12(f32x4 (&acc)[3][TH][2], const f32x4 (&bias)[2], const float (&W)[14], int ci, ROWS rows, bool v0,
+                                             bool v1, bool v2) {
+  float x0[TH + 2], xm[TH + 2], xp[TH + 2];
+#pragma unroll
+  for (int r = 0; r < TH + 2; ++r) rows(r, ci, x0[r], xm[r], xp[r]);
+  tap_walk<TH, P0, P1, P2, FRESH>(v0, v1, v2, [&](int set, int jr, int r, int kw, int t, bool born, int) PCGC_INLINE {
+    const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const bool first = born && kw == 0;
+      acc[set][jr][hf] = first ? mfa_new((t & 1) * 8 + ci * 2 + hf, W[t >> 1], xv, bias[hf])
+                               : mfa((t & 1) * 8 + ci * 2 + hf, W[t >> 1], xv, acc[set][jr][hf]);
+    }
+  });
+}
+template <int TH, int P0, int P1, int P2, bool FRESH, class ROWS>
+__device__ __forceinline__ void bc_channel22(f32x4 (&acc)[3][TH], const f32x4& bias, const float (&W)[7], int ci, ROWS rows, bool v0, bool v1,
+                                             bool v2) {
+  float x0[TH + 2], xm[TH + 2], xp[TH + 2];
+#pragma unroll
+  for (int r = 0; r < TH + 2; ++r) rows(r, ci, x0[r], xm[r], xp[r]);
+  tap_walk<TH, P0, P1, P2, FRESH>(v0, v1, v2, [&](int set, int jr, int r, int kw, int t, bool born, int) PCGC_INLINE {
+    const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
+    const bool first = born && kw == 0;
+    acc[set][jr] = first ? mfa_new((t & 3) * 4 + ci, W[t >> 2], xv, bias) : mfa((t & 3) * 4 + ci, W[t >> 2], xv, acc[set][jr]);
+  });
+}
 
 // lds[i] = f(i) for i < N by 256 threads, the loads of 16 elements per thread in flight before their LDS writes (the
 // plain `for (i = tid; ...) lds[i] = w[index(i)]` loop waits for every load in turn)

@@ -21,7 +21,6 @@
 // A wave walks LD planes of TH rows along d with three rotating plane accumulators (sliding window over kd).
 // Summation order per output: bias, then (plane, channel, kh, kw) — fixed, independent of batch and placement.
 #include <cstdlib>
-#include <type_traits>
 #include "row_common.h"
 
 namespace pcgc {
@@ -129,7 +128,7 @@ __device__ __forceinline__ unsigned long long virtual_rows(const unsigned long l
 struct Tile {
   int b, h0, d0;
 };
-// block = index of the wave's workgroup among those of its kernel role (blockIdx.x unless the launch mixes roles)
+// block = index of the wave's workgroup in the tile order (deconv_out's XCD remap passes another than blockIdx.x)
 template <int TH, int LD>
 __device__ __forceinline__ Tile wave_tile(int block = blockIdx.x) {
   int wv = __builtin_amdgcn_readfirstlane(block * 4 + (threadIdx.x >> 6));
@@ -143,8 +142,8 @@ __device__ __forceinline__ Tile wave_tile(int block = blockIdx.x) {
 // --- exact skipping of empty space (RowSkip, common.h) -----------------------------------------------------------
 // The wave's tile through the launch's permutation; *heavy = false: copy the tile from the empty-cube response.
 template <int TH, int LD>
-__device__ __forceinline__ Tile wave_tile_ordered(const RowSkip& k, bool* heavy, int block = blockIdx.x, bool* unread = nullptr) {
-  const int wid = __builtin_amdgcn_readfirstlane(block * 4 + (threadIdx.x >> 6));
+__device__ __forceinline__ Tile wave_tile_ordered(const RowSkip& k, bool* heavy, bool* unread = nullptr) {
+  const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   int wv = wid;
   *heavy = true;
   if (k.order) {
@@ -337,81 +336,38 @@ __device__ __forceinline__ float* exp_lds_ptr() {
 // first MFMA takes bias / zero as its C operand (no register moves).  Summation order per output: per kw column
 // (plane, channel, kh) in program order, then S_1 + shr(S_0) + shl(S_2).
 // ---------------------------------------------------------------------------------------------------------------
-template <int TH, int P0, int P1, int P2, bool FRESH>
-__device__ __forceinline__ void a_channel(f32x4 (&S)[3][3][TH], f32x4 (&acc2)[TH], const f32x4& bias, const f32x4& bias2,
-                                           const float (&W)[27], float W2, int ci, const f32x4 (&buf)[TH + 2], int c, bool v0, bool v1,
-                                           bool v2) {
-  float x0[TH + 2];
-#pragma unroll
-  for (int r = 0; r < TH + 2; ++r) x0[r] = comp(buf[r], c);
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;                      // input plane p feeds output plane p + 1 - kd = p - 1 + j
-    if (vj[j]) {
-#pragma unroll
-      for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int jr = r - kh;
-          if (jr >= 0 && jr < TH) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const bool first = FRESH && j == 2 && kh == 0;       // first tap that reaches this accumulator of the new plane
-              if (first) S[P[j]][kw][jr] = mfa_new(ci, W[(kd * 3 + kh) * 3 + kw], x0[r], kw == 1 ? bias : zero);
-              else S[P[j]][kw][jr] = mfa(ci, W[(kd * 3 + kh) * 3 + kw], x0[r], S[P[j]][kw][jr]);
-            }
-          }
-        }
-    }
-  }
-  if (v1) {
-#pragma unroll
-    for (int jr = 0; jr < TH; ++jr) acc2[jr] = FRESH ? mfa_new(ci, W2, x0[jr + 1], bias2) : mfa(ci, W2, x0[jr + 1], acc2[jr]);
-  }
-}
-
-// The same MFMAs for the four channels of one loaded quad with the validity tests hoisted: ONE wave-uniform branch per
-// (quad, output plane) instead of one per (channel, output plane) — 12 instead of 48 per plane step, and with them three
+// The MFMAs of the four channels of one loaded quad; the validity tests sit outside the channel loop (tap_walk): ONE wave-uniform
+// branch per (quad, output plane) instead of one per (channel, output plane) — 12 instead of 48 per plane step, and with them three
 // quarters of the s_waitcnt the compiler puts at the head of every conditional block (kernel A: 391 branches + 635 waits per
 // 2 688 MFMAs; scalar instructions are free only up to about one per two MFMAs, tools/exp/exp_mfma_issue.hip).  Every
-// accumulator still receives its contributions in the order (plane, channel, kh, kw): bit-identical to a_channel.
+// accumulator still receives its contributions in the order (plane, channel, kh, kw): bit-identical to the per-channel form.
 template <int TH, int P0, int P1, int P2, bool FRESH>
 __device__ __forceinline__ void a_quad(f32x4 (&S)[3][3][TH], f32x4 (&acc2)[TH], const f32x4& bias, const f32x4& bias2,
                                         const float (&W)[27], float W2, int ci0, const f32x4 (&buf)[TH + 2], bool v0, bool v1, bool v2) {
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;                      // input plane p feeds output plane p + 1 - kd = p - 1 + j
-    if (vj[j]) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-          for (int kh = 0; kh < 3; ++kh) {
-            const int jr = r - kh;
-            if (jr >= 0 && jr < TH) {
-#pragma unroll
-              for (int kw = 0; kw < 3; ++kw) {
-                const bool first = FRESH && c == 0 && j == 2 && kh == 0;   // first tap that reaches this accumulator of the new plane
-                if (first) S[P[j]][kw][jr] = mfa_new(ci0 + c, W[(kd * 3 + kh) * 3 + kw], comp(buf[r], c), kw == 1 ? bias : zero);
-                else S[P[j]][kw][jr] = mfa(ci0 + c, W[(kd * 3 + kh) * 3 + kw], comp(buf[r], c), S[P[j]][kw][jr]);
-              }
-            }
-          }
+  tap_walk<TH, P0, P1, P2, FRESH, 3, 4>(
+      v0, v1, v2,
+      [&](int set, int jr, int r, int kw, int t, bool born, int c) PCGC_INLINE {
+        if (born) S[set][kw][jr] = mfa_new(ci0 + c, W[t], comp(buf[r], c), kw == 1 ? bias : zero);
+        else S[set][kw][jr] = mfa(ci0 + c, W[t], comp(buf[r], c), S[set][kw][jr]);
+      },
+      [&](int j, int c) PCGC_INLINE {
         if (j == 1) {                            // conv2_1 (1^3) of the wave's own rows rides in the centre plane's block
 #pragma unroll
           for (int jr = 0; jr < TH; ++jr)
             acc2[jr] = (FRESH && c == 0) ? mfa_new(ci0 + c, W2, comp(buf[jr + 1], c), bias2) : mfa(ci0 + c, W2, comp(buf[jr + 1], c), acc2[jr]);
         }
-      }
-    }
-  }
+      });
+}
+
+// the shift source of the tap walks (row_common.h): channel c of row r and its kw = 0 / 2 neighbours — the whole wave shifts, zero fill
+template <int TH>
+__device__ __forceinline__ auto wave_rows(const f32x4 (&buf)[TH + 2]) {
+  return [&buf](int r, int c, float& x0, float& xm, float& xp) PCGC_INLINE {
+    x0 = comp(buf[r], c);
+    xm = shr1(x0);
+    xp = shl1(x0);
+  };
 }
 
 __device__ __forceinline__ f32x4 shr4(f32x4 v) { return f32x4{shr1(v[0]), shr1(v[1]), shr1(v[2]), shr1(v[3])}; }
@@ -423,13 +379,15 @@ __device__ __forceinline__ f32x4 shl4(f32x4 v) { return f32x4{shl1(v[0]), shl1(v
 // NHWC: the 16-channel tensors (x / out / pre) are NDHWC — the training step's original layout; TRAIN with NHWC = false is
 // the training step with its 64^3 stage in the Q4 layout of the inference path (1 KiB per wave instruction instead of
 // 16 B per lane at a 64 B stride)
-template <int TH, int LD, bool TRAIN = false, bool SKIP = false, bool NHWC = TRAIN, bool QUADJ = true>
-__device__ __forceinline__ void vrn16a_row_body(const VrnRowArgs& a, int block) {
+// (A function of its own under the kernel, vrn16a_row_kernel below, like vrn16bc_row_body: the compiler optimises it before it becomes
+// part of the kernel, and written straight into the kernel the same source comes out with another schedule and register allocation.)
+template <int TH, int LD, bool TRAIN = false, bool SKIP = false, bool NHWC = TRAIN>
+__device__ __forceinline__ void vrn16a_row_body(const VrnRowArgs& a) {
   static_assert(!(TRAIN && SKIP), "the training step computes every tile");
   static_assert(TRAIN || !NHWC, "the inference tensors are Q4");
   const int lane = threadIdx.x & 63;
   bool heavy = true;
-  const Tile tl = SKIP ? wave_tile_ordered<TH, LD>(a.skip, &heavy, block) : wave_tile<TH, LD>(block);
+  const Tile tl = SKIP ? wave_tile_ordered<TH, LD>(a.skip, &heavy) : wave_tile<TH, LD>();
   const int h0 = tl.h0, d0 = tl.d0;
   if (SKIP && !heavy) {
     if (a.skip.materialize) copy_empty_tile<TH, LD, 2>(a.skip.empty, a.t12 + (size_t)tl.b * kD * kD * kD * 8, tl, lane);
@@ -483,28 +441,13 @@ __device__ __forceinline__ void vrn16a_row_body(const VrnRowArgs& a, int block) 
     // operand of their first MFMA), and an input plane outside the cube reads zeros
     const bool v0 = pin && p - 1 >= d0, v1 = pin && p >= d0 && p < d0 + LD, v2 = p + 1 < d0 + LD;
     rows(buf[P2], p, 2);
-    if constexpr (QUADJ) {
-      a_quad<TH, P0, P1, P2, true>(S, acc2, bi, bi2, W, W2, 0, buf[P0], v0, v1, v2);
-      rows(buf[P0], p, 3);
-      a_quad<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 4, buf[P1], v0, v1, v2);
-      rows(buf[P1], p + 1, 0);
-      a_quad<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 8, buf[P2], v0, v1, v2);
-      rows(buf[P2], p + 1, 1);
-      a_quad<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 12, buf[P0], v0, v1, v2);
-    } else {
-    a_channel<TH, P0, P1, P2, true>(S, acc2, bi, bi2, W, W2, 0, buf[P0], 0, v0, v1, v2);
-#pragma unroll
-    for (int c = 1; c < 4; ++c) a_channel<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, c, buf[P0], c, v0, v1, v2);
+    a_quad<TH, P0, P1, P2, true>(S, acc2, bi, bi2, W, W2, 0, buf[P0], v0, v1, v2);
     rows(buf[P0], p, 3);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a_channel<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 4 + c, buf[P1], c, v0, v1, v2);
+    a_quad<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 4, buf[P1], v0, v1, v2);
     rows(buf[P1], p + 1, 0);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a_channel<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 8 + c, buf[P2], c, v0, v1, v2);
+    a_quad<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 8, buf[P2], v0, v1, v2);
     rows(buf[P2], p + 1, 1);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) a_channel<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 12 + c, buf[P0], c, v0, v1, v2);
-    }
+    a_quad<TH, P0, P1, P2, false>(S, acc2, bi, bi2, W, W2, 12, buf[P0], v0, v1, v2);
 #ifdef PCGC_EXPERIMENTS
     if (PCGC_ABL(a, 64)) {
       // fusion probe (tools/exp/t_fuse_probe.py): what the A phase of a fused A + BC kernel would add to this instruction
@@ -539,17 +482,7 @@ __device__ __forceinline__ void vrn16a_row_body(const VrnRowArgs& a, int block) 
       }
     }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-#pragma unroll 1
-  for (int p = d0 - 1; p <= d0 + LD; p += 3) {
-    step(p, I0{}, I1{}, I2{});
-    if (p + 1 > d0 + LD) break;
-    step(p + 1, I1{}, I2{}, I0{});
-    if (p + 2 > d0 + LD) break;
-    step(p + 2, I2{}, I0{}, I1{});
-  }
+  PCGC_ROTATE3(d0 - 1, <=, d0 + LD, step, false)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -557,88 +490,19 @@ __device__ __forceinline__ void vrn16a_row_body(const VrnRowArgs& a, int block) 
 // weights: conv1_2 [27][4][8]: VGPR tap>>1, abid = (tap&1)*8 + ci*2 + half;  conv2_2 [27][4][4]: VGPR tap>>2,
 //          abid = (tap&3)*4 + ci;  conv2_3 [4][8]: one VGPR (lanes 0..31), abid = ci*2 + half
 // ---------------------------------------------------------------------------------------------------------------
-// P0, P1, P2: which of the three accumulator sets holds output plane p-1, p, p+1 in this step (the plane loop is unrolled
-// three times with the roles rotating, so the sets never move between registers).  FRESH: this call holds the first tap
-// that reaches each accumulator of set P2 (plane p+1 gets its first contribution, kd = 0, from input plane p): that MFMA
-// takes the bias as its C operand instead of the stale accumulator — no initialisation moves.
-template <int TH, int P0, int P1, int P2, bool FRESH>
-__device__ __forceinline__ void bc_channel12(f32x4 (&acc)[3][TH][2], const f32x4 (&bias)[2], const float (&W)[14], int ci,
-                                             const f32x4 (&buf)[TH + 2], bool v0, bool v1, bool v2) {
-  float x0[TH + 2], xm[TH + 2], xp[TH + 2];
-#pragma unroll
-  for (int r = 0; r < TH + 2; ++r) { x0[r] = comp(buf[r], ci); xm[r] = shr1(x0[r]); xp[r] = shl1(x0[r]); }
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;
-    if (vj[j]) {
-#pragma unroll
-      for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int jr = r - kh;
-          if (jr >= 0 && jr < TH) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const int t = (kd * 3 + kh) * 3 + kw;
-              const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
-#pragma unroll
-              for (int hf = 0; hf < 2; ++hf) {
-                const bool first = FRESH && j == 2 && kh == 0 && kw == 0;
-                acc[P[j]][jr][hf] = first ? mfa_new((t & 1) * 8 + ci * 2 + hf, W[t >> 1], xv, bias[hf])
-                                          : mfa((t & 1) * 8 + ci * 2 + hf, W[t >> 1], xv, acc[P[j]][jr][hf]);
-              }
-            }
-          }
-        }
-    }
-  }
-}
-
-template <int TH, int P0, int P1, int P2, bool FRESH>
-__device__ __forceinline__ void bc_channel22(f32x4 (&acc)[3][TH], const f32x4& bias, const float (&W)[7], int ci,
-                                             const f32x4 (&buf)[TH + 2], bool v0, bool v1, bool v2) {
-  float x0[TH + 2], xm[TH + 2], xp[TH + 2];
-#pragma unroll
-  for (int r = 0; r < TH + 2; ++r) { x0[r] = comp(buf[r], ci); xm[r] = shr1(x0[r]); xp[r] = shl1(x0[r]); }
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;
-    if (vj[j]) {
-#pragma unroll
-      for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int jr = r - kh;
-          if (jr >= 0 && jr < TH) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const int t = (kd * 3 + kh) * 3 + kw;
-              const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
-              const bool first = FRESH && j == 2 && kh == 0 && kw == 0;
-              acc[P[j]][jr] = first ? mfa_new((t & 3) * 4 + ci, W[t >> 2], xv, bias) : mfa((t & 3) * 4 + ci, W[t >> 2], xv, acc[P[j]][jr]);
-            }
-          }
-        }
-    }
-  }
-}
-
+// (one input channel of conv1_2 / conv2_2: bc_channel12 / bc_channel22 in row_common.h, shared with vrn_seg.hip)
 // The residual rows of the finished plane are requested BEFORE the conv2_2 phase and every load / store of the loop
 // is unconditional (an out-of-range buffer offset reads zeros / drops the store), so the epilogue never waits on
 // memory and the compiler keeps counted vmcnt waits across the whole loop body.  TH = 2 rows per wave: with 12
 // accumulator registers per output row (8 + 4 channels) TH = 4 leaves no room for the residual prefetch
 // (measured: 74 us per 8 cubes with TH = 4 and the residual loaded in the epilogue, 64 us in this form).
 template <int TH, int LD, bool TRAIN = false, bool NONNEG = false, bool SKIP = false, bool NHWC = TRAIN>
-__device__ __forceinline__ void vrn16bc_row_body(const VrnRowArgs& a, int block) {
+__device__ __forceinline__ void vrn16bc_row_body(const VrnRowArgs& a) {
   static_assert(!(TRAIN && SKIP), "the training step computes every tile");
   static_assert(TRAIN || !NHWC, "the inference tensors are Q4");
   const int lane = threadIdx.x & 63;
   bool heavy = true, unread = false;
-  const Tile tl = SKIP ? wave_tile_ordered<TH, LD>(a.skip, &heavy, block, &unread) : wave_tile<TH, LD>(block);
+  const Tile tl = SKIP ? wave_tile_ordered<TH, LD>(a.skip, &heavy, &unread) : wave_tile<TH, LD>();
   const int h0 = tl.h0, d0 = tl.d0;
   if (SKIP && !heavy) {
     if (a.skip.materialize == 1 || (a.skip.materialize == 2 && !unread))
@@ -709,9 +573,9 @@ __device__ __forceinline__ void vrn16bc_row_body(const VrnRowArgs& a, int block)
     // v2 does not ask for the plane to exist: plane p + 1's accumulators are BORN in this step (bias as the C operand of
     // their first MFMA), and an input plane outside the cube reads zeros
     const bool v0 = pin && p - 1 >= d0, v1 = pin && p >= d0 && p < d0 + LD, v2 = p + 1 < d0 + LD;
-    bc_channel12<TH, P0, P1, P2, true>(acc12, bi12, W12, 0, bufA, v0, v1, v2);
+    bc_channel12<TH, P0, P1, P2, true>(acc12, bi12, W12, 0, wave_rows<TH>(bufA), v0, v1, v2);
 #pragma unroll
-    for (int c = 1; c < 4; ++c) bc_channel12<TH, P0, P1, P2, false>(acc12, bi12, W12, c, bufA, v0, v1, v2);
+    for (int c = 1; c < 4; ++c) bc_channel12<TH, P0, P1, P2, false>(acc12, bi12, W12, c, wave_rows<TH>(bufA), v0, v1, v2);
     unsigned tb_cur[TH];
     if constexpr (TRAIN) {
 #pragma unroll
@@ -734,9 +598,9 @@ __device__ __forceinline__ void vrn16bc_row_body(const VrnRowArgs& a, int block)
       for (int q = 0; q < 4; ++q)
         res[r][q] = PCGC_ABL(a, 8) ? raw_load4(rxo, lane_x, obase + row_off<NHWC, 4>(0, r, q), 2)
                                    : raw_load4(rxo, lane_x, obase + row_off<NHWC, 4>(0, r, q), 0);
-    bc_channel22<TH, P0, P1, P2, true>(acc22, bi22, W22, 0, bufB, v0, v1, v2);
+    bc_channel22<TH, P0, P1, P2, true>(acc22, bi22, W22, 0, wave_rows<TH>(bufB), v0, v1, v2);
 #pragma unroll
-    for (int c = 1; c < 4; ++c) bc_channel22<TH, P0, P1, P2, false>(acc22, bi22, W22, c, bufB, v0, v1, v2);
+    for (int c = 1; c < 4; ++c) bc_channel22<TH, P0, P1, P2, false>(acc22, bi22, W22, c, wave_rows<TH>(bufB), v0, v1, v2);
     if constexpr (TRAIN) {
       if (a.pre_signs) {
 #pragma unroll
@@ -794,17 +658,7 @@ __device__ __forceinline__ void vrn16bc_row_body(const VrnRowArgs& a, int block)
     if (PCGC_ABL(a, 64)) __syncthreads();
 #endif
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-#pragma unroll 1
-  for (int p = d0 - 1; p <= d0 + LD; p += 3) {            // roles rotate instead of registers
-    step(p, I0{}, I1{}, I2{});
-    if (p + 1 > d0 + LD) break;
-    step(p + 1, I1{}, I2{}, I0{});
-    if (p + 2 > d0 + LD) break;
-    step(p + 2, I2{}, I0{}, I1{});
-  }
+  PCGC_ROTATE3(d0 - 1, <=, d0 + LD, step, false)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -828,35 +682,17 @@ struct VrnBwdInArgs {
 template <int TH, int P0, int P1, int P2, bool FRESH>
 __device__ __forceinline__ void bwd_in_channel(f32x4 (&acc)[3][TH][4], const float (&W)[27], int ci, const f32x4 (&buf)[TH + 2], bool v0,
                                                bool v1, bool v2) {
+  const auto rows = wave_rows<TH>(buf);
   float x0[TH + 2], xm[TH + 2], xp[TH + 2];
 #pragma unroll
-  for (int r = 0; r < TH + 2; ++r) { x0[r] = comp(buf[r], ci); xm[r] = shr1(x0[r]); xp[r] = shl1(x0[r]); }
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
+  for (int r = 0; r < TH + 2; ++r) rows(r, ci, x0[r], xm[r], xp[r]);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  tap_walk<TH, P0, P1, P2, FRESH>(v0, v1, v2, [&](int set, int jr, int r, int kw, int t, bool born, int) PCGC_INLINE {
+    const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
+    const bool first = born && kw == 0;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;
-    if (vj[j]) {
-#pragma unroll
-      for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int jr = r - kh;
-          if (jr >= 0 && jr < TH) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const int t = (kd * 3 + kh) * 3 + kw;
-              const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
-              const bool first = FRESH && j == 2 && kh == 0 && kw == 0;
-#pragma unroll
-              for (int q = 0; q < 4; ++q)
-                acc[P[j]][jr][q] = first ? mfa_new(ci * 4 + q, W[t], xv, zero) : mfa(ci * 4 + q, W[t], xv, acc[P[j]][jr][q]);
-            }
-          }
-        }
-    }
-  }
+    for (int q = 0; q < 4; ++q) acc[set][jr][q] = first ? mfa_new(ci * 4 + q, W[t], xv, zero) : mfa(ci * 4 + q, W[t], xv, acc[set][jr][q]);
+  });
 }
 
 template <int TH, int LD, bool MASK, bool NHWC = true>
@@ -929,17 +765,7 @@ __global__ void __launch_bounds__(256, 2) vrn16a_bwd_row_kernel(VrnBwdInArgs a) 
       }
     }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-#pragma unroll 1
-  for (int p = d0 - 1; p <= d0 + LD; p += 3) {
-    step(p, I0{}, I1{}, I2{});
-    if (p + 1 > d0 + LD) break;
-    step(p + 1, I1{}, I2{}, I0{});
-    if (p + 2 > d0 + LD) break;
-    step(p + 2, I2{}, I0{}, I1{});
-  }
+  PCGC_ROTATE3(d0 - 1, <=, d0 + LD, step, false)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -962,7 +788,7 @@ struct VrnBwdTailArgs {
   // SPLIT = true: the block tail's reverse happens here too (pcgc_vrn_bwd_split_signs folded in): dz12 / dz23 are made
   // from the incoming gradient dout [..][16] (already masked by out > 0) and the sign bits of `pre` for every row the
   // wave touches, and WRITTEN to dz12w / dz23w for its own rows (the weight gradients of conv1_2 / conv2_3 read them); the
-  // masks t22 > 0, t11 > 0, t21 > 0 come from bits 16-19 / 20-23 / 24-27 of the same words (vrn16bc_row_body writes them), so
+  // masks t22 > 0, t11 > 0, t21 > 0 come from bits 16-19 / 20-23 / 24-27 of the same words (vrn16bc_row_kernel writes them), so
   // t11 / t21 / t22 are NOT read: 184 instead of 228 bytes per voxel
   const float* dout = nullptr;
   const int* signs = nullptr;
@@ -1066,6 +892,7 @@ __global__ void __launch_bounds__(256, 2) vrn16bc_bwd_row_kernel(VrnBwdTailArgs 
       float x0[TH + 2], xm[TH + 2], xp[TH + 2];
 #pragma unroll
       for (int r = 0; r < TH + 2; ++r) { x0[r] = comp(in12[c8 >> 2][r], c8 & 3); xm[r] = shr1(x0[r]); xp[r] = shl1(x0[r]); }
+      // (the tap walk of row_common.h, written out: a call to tap_walk from the kernel's own body (not from a function under it) gives this kernel another schedule; the same below and in conv_in_row_kernel)
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int kd = 2 - j;
@@ -1175,10 +1002,13 @@ __global__ void __launch_bounds__(256, 2) vrn16bc_bwd_row_kernel(VrnBwdTailArgs 
   }
 }
 
-template <int TH, int LD, bool TRAIN = false, bool SKIP = false, bool NHWC = TRAIN, bool QUADJ = true>
-__global__ void __launch_bounds__(256, 2) vrn16a_row_kernel(VrnRowArgs a) { vrn16a_row_body<TH, LD, TRAIN, SKIP, NHWC, QUADJ>(a, blockIdx.x); }
+// The unnamed last parameter is what is left of a removed switch (per-channel instead of per-quad validity tests, never launched):
+// it keeps the kernels' symbols, and with them the code object's .note and .symtab, byte for byte those of the object code these
+// kernels were validated as.  Drop it with the next change of their instructions.
+template <int TH, int LD, bool TRAIN = false, bool SKIP = false, bool NHWC = TRAIN, bool = true>
+__global__ void __launch_bounds__(256, 2) vrn16a_row_kernel(VrnRowArgs a) { vrn16a_row_body<TH, LD, TRAIN, SKIP, NHWC>(a); }
 template <int TH, int LD, bool TRAIN = false, bool NONNEG = false, bool SKIP = false, bool NHWC = TRAIN>
-__global__ void __launch_bounds__(256, 2) vrn16bc_row_kernel(VrnRowArgs a) { vrn16bc_row_body<TH, LD, TRAIN, NONNEG, SKIP, NHWC>(a, blockIdx.x); }
+__global__ void __launch_bounds__(256, 2) vrn16bc_row_kernel(VrnRowArgs a) { vrn16bc_row_body<TH, LD, TRAIN, NONNEG, SKIP, NHWC>(a); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // conv_in: x [B][64][64][64] (one channel) -> y Q4 [B][64][64][4][64][4], relu(conv 3^3, 1 -> 16 + bias)
@@ -1315,20 +1145,10 @@ __global__ void __launch_bounds__(256, 2) deconv_out_row_kernel(ConvRowArgs a) {
   load_rows<TH, 4>(bufA, rs, lane16, d0 - 1, 0, h0);
   auto quad = [&](const f32x4 (&buf)[TH + 2], int q, const bool (&vj)[3]) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int kd = 2 - j;
-        if (vj[j]) {
-#pragma unroll
-          for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {
-              const int jr = r - kh;
-              if (jr >= 0 && jr < TH) acc[j][jr] = mfa(q * 4 + c, W[kd * 3 + kh], comp(buf[r], c), acc[j][jr]);
-            }
-        }
-      }
+    for (int c = 0; c < 4; ++c)                               // (the plane tests inside the channel loop here)
+      tap_walk<TH, 0, 1, 2, false, 1>(vj[0], vj[1], vj[2], [&](int j, int jr, int r, int, int t, bool, int) PCGC_INLINE {
+        acc[j][jr] = mfa(q * 4 + c, W[t], comp(buf[r], c), acc[j][jr]);
+      });
   };
 #pragma unroll 1
   for (int p = d0 - 1; p <= d0 + LD; ++p) {

@@ -14,7 +14,6 @@
 //   kernel A : t12 = [ relu(conv1_1(x)) 3^3 32->8 | relu(conv2_1(x)) 1^3 32->8 ]
 //   kernel BC: out = relu(x + [ relu(conv1_2(t11)) 3^3 8->16 | relu(conv2_3(relu(conv2_2(t21)))) 3^3 8->8, 1^3 8->16 ])
 // Summation order per output: bias, then (plane, channel, kh, kw): fixed, batch- and placement-independent.
-#include <type_traits>
 #include "row_common.h"
 
 namespace pcgc {
@@ -136,58 +135,29 @@ struct Vrn32Args {
   RowSkip skip;        // inference, analysis only: tile order + empty-cube response (skip.order != nullptr)
 };
 
-// One input channel of a quad step: TP aligned pairs P, TP+1 odd pairs O -> 3^3 taps into NCO output-channel quads.
-// WMAP(tap, coq, c) gives (weight register index, abid) of the layer's packed chunk.
-template <int TP, int NCO, int NW, class WMAP>
-__device__ __forceinline__ void pair_channel(f32x4 (&acc)[3][TP][NCO], const float (&W)[NW], int c, const f32x4 (&P)[TP],
-                                             const f32x4 (&O)[TP + 1], bool v0, bool v1, bool v2, float l32, float l31, WMAP wmap) {
-  float p0[TP], pm[TP], pp[TP], o0[TP + 1], om[TP + 1], op[TP + 1];
+// NC input channels (c0 .. c0 + NC - 1 of the loaded quad) of a quad step: TP aligned pairs P, TP+1 odd pairs O -> 3^3 taps into
+// NCO output-channel quads.  WMAP(tap, coq, c) gives (weight register index, abid) of the layer's packed chunk.  The validity
+// tests sit outside the channel loop, so a call with the whole quad (NC = 4) takes one wave-uniform branch per (quad, output plane)
+// where four calls with one channel each take one per (channel, output plane); the order of contributions per accumulator is
+// the same either way: channel, then kh, kw.
+template <int TP, int NCO, int NW, int NC, class WMAP>
+__device__ __forceinline__ void pair_channels(f32x4 (&acc)[3][TP][NCO], const float (&W)[NW], int c0, const f32x4 (&P)[TP],
+                                              const f32x4 (&O)[TP + 1], bool v0, bool v1, bool v2, float l32, float l31, WMAP wmap) {
+  float p0[NC][TP], pm[NC][TP], pp[NC][TP], o0[NC][TP + 1], om[NC][TP + 1], op[NC][TP + 1];
 #pragma unroll
-  for (int j = 0; j < TP; ++j) { p0[j] = comp(P[j], c); pm[j] = shr1p(p0[j], l32); pp[j] = shl1p(p0[j], l31); }
+  for (int c = 0; c < NC; ++c) {
 #pragma unroll
-  for (int j = 0; j <= TP; ++j) { o0[j] = comp(O[j], c); om[j] = shr1p(o0[j], l32); op[j] = shl1p(o0[j], l31); }
+    for (int j = 0; j < TP; ++j) { p0[c][j] = comp(P[j], c0 + c); pm[c][j] = shr1p(p0[c][j], l32); pp[c][j] = shl1p(p0[c][j], l31); }
+#pragma unroll
+    for (int j = 0; j <= TP; ++j) { o0[c][j] = comp(O[j], c0 + c); om[c][j] = shr1p(o0[c][j], l32); op[c][j] = shl1p(o0[c][j], l31); }
+  }
   const bool vj[3] = {v0, v1, v2};
 #pragma unroll
   for (int jj = 0; jj < 3; ++jj) {
     const int kd = 2 - jj;                     // input plane p feeds output plane p - 1 + jj
     if (vj[jj]) {
 #pragma unroll
-      for (int j = 0; j < TP; ++j)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw) {
-            const int t = (kd * 3 + kh) * 3 + kw;
-            const float xv = kh == 1 ? (kw == 0 ? pm[j] : (kw == 1 ? p0[j] : pp[j]))
-                                     : (kh == 0 ? (kw == 0 ? om[j] : (kw == 1 ? o0[j] : op[j]))
-                                                : (kw == 0 ? om[j + 1] : (kw == 1 ? o0[j + 1] : op[j + 1])));
-#pragma unroll
-            for (int coq = 0; coq < NCO; ++coq) acc[jj][j][coq] = mfa(wmap.abid(t, coq, c), W[wmap.reg(t)], xv, acc[jj][j][coq]);
-          }
-    }
-  }
-}
-
-// pair_channel for the four channels of a quad with the validity tests hoisted: one wave-uniform branch per (quad, output
-// plane) instead of one per (channel, output plane).  Same order of contributions per accumulator (channel, then kh, kw).
-template <int TP, int NCO, int NW, class WMAP>
-__device__ __forceinline__ void pair_quad(f32x4 (&acc)[3][TP][NCO], const float (&W)[NW], const f32x4 (&P)[TP], const f32x4 (&O)[TP + 1],
-                                          bool v0, bool v1, bool v2, float l32, float l31, WMAP wmap) {
-  float p0[4][TP], pm[4][TP], pp[4][TP], o0[4][TP + 1], om[4][TP + 1], op[4][TP + 1];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-#pragma unroll
-    for (int j = 0; j < TP; ++j) { p0[c][j] = comp(P[j], c); pm[c][j] = shr1p(p0[c][j], l32); pp[c][j] = shl1p(p0[c][j], l31); }
-#pragma unroll
-    for (int j = 0; j <= TP; ++j) { o0[c][j] = comp(O[j], c); om[c][j] = shr1p(o0[c][j], l32); op[c][j] = shl1p(o0[c][j], l31); }
-  }
-  const bool vj[3] = {v0, v1, v2};
-#pragma unroll
-  for (int jj = 0; jj < 3; ++jj) {
-    const int kd = 2 - jj;
-    if (vj[jj]) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
+      for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int j = 0; j < TP; ++j)
 #pragma unroll
@@ -199,7 +169,7 @@ __device__ __forceinline__ void pair_quad(f32x4 (&acc)[3][TP][NCO], const float 
                                        : (kh == 0 ? (kw == 0 ? om[c][j] : (kw == 1 ? o0[c][j] : op[c][j]))
                                                   : (kw == 0 ? om[c][j + 1] : (kw == 1 ? o0[c][j + 1] : op[c][j + 1])));
 #pragma unroll
-              for (int coq = 0; coq < NCO; ++coq) acc[jj][j][coq] = mfa(wmap.abid(t, coq, c), W[wmap.reg(t)], xv, acc[jj][j][coq]);
+              for (int coq = 0; coq < NCO; ++coq) acc[jj][j][coq] = mfa(wmap.abid(t, coq, c0 + c), W[wmap.reg(t)], xv, acc[jj][j][coq]);
             }
     }
   }
@@ -214,47 +184,24 @@ struct Map16 {   // chunk [tap][ci4][16 couts]: 64 floats per tap
   __device__ static constexpr int abid(int, int coq, int c) { return c * 4 + coq; }
 };
 
-// Kernel A's form of pair_channel: the lane shifts act on the 8 output channels instead of the 32 input channels (a
+// Kernel A's form of pair_channels: the lane shifts act on the 8 output channels instead of the 32 input channels (a
 // lane shift commutes with the convolution, vrn_row.hip kernel A).  S[set][kw] collects tap column kw applied to the
 // UNSHIFTED pair vectors; a finished plane is S[1] + shr(S[0]) + shl(S[2]) with the row-crossing lane zeroed.  The
 // input-shift form spent 2 x (shift + select) per channel and pair vector — 160 VALU instructions per 896 MFMAs, in the
 // partial plane steps too (VALU : MFMA 0.40 in profiles/r02_vB_pmc_per_kernel.csv); this form spends 48 per finished
 // pair.  Summation order per output: per kw column bias / 0, then (plane, channel, kh); then S1 + shr(S0) + shl(S2).
-template <int TP, int NW, class WMAP>
-__device__ __forceinline__ void pair_channel_os(f32x4 (&S)[3][3][TP][2], const float (&W)[NW], int c, const f32x4 (&P)[TP],
-                                                const f32x4 (&O)[TP + 1], bool v0, bool v1, bool v2, WMAP wmap) {
+// RIDER: conv2_1 (1^3, register 13's upper half) of the centre plane rides in the jj = 1 block behind each channel (a caller that
+// walks one channel at a time adds it behind the call instead).
+template <int TP, int NW, int NC, bool RIDER, class WMAP>
+__device__ __forceinline__ void pair_channels_os(f32x4 (&S)[3][3][TP][2], f32x4 (&acc2)[1][TP][2], const float (&W)[NW], int c0,
+                                                 const f32x4 (&P)[TP], const f32x4 (&O)[TP + 1], bool v0, bool v1, bool v2, WMAP wmap) {
   const bool vj[3] = {v0, v1, v2};
 #pragma unroll
   for (int jj = 0; jj < 3; ++jj) {
     const int kd = 2 - jj;                     // input plane p feeds output plane p - 1 + jj
     if (vj[jj]) {
 #pragma unroll
-      for (int j = 0; j < TP; ++j)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const float xv = kh == 1 ? comp(P[j], c) : (kh == 0 ? comp(O[j], c) : comp(O[j + 1], c));
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw) {
-            const int t = (kd * 3 + kh) * 3 + kw;
-#pragma unroll
-            for (int coq = 0; coq < 2; ++coq) S[jj][kw][j][coq] = mfa(wmap.abid(t, coq, c), W[wmap.reg(t)], xv, S[jj][kw][j][coq]);
-          }
-        }
-    }
-  }
-}
-// pair_channel_os for the four channels of a quad, validity tests hoisted (see pair_quad); conv2_1 (1^3, register 13's upper
-// half) of the centre plane rides in the jj = 1 block.  Same order of contributions per accumulator.
-template <int TP, int NW, class WMAP>
-__device__ __forceinline__ void pair_quad_os(f32x4 (&S)[3][3][TP][2], f32x4 (&acc2)[1][TP][2], const float (&W)[NW], const f32x4 (&P)[TP],
-                                             const f32x4 (&O)[TP + 1], bool v0, bool v1, bool v2, WMAP wmap) {
-  const bool vj[3] = {v0, v1, v2};
-#pragma unroll
-  for (int jj = 0; jj < 3; ++jj) {
-    const int kd = 2 - jj;
-    if (vj[jj]) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
+      for (int c = c0; c < c0 + NC; ++c) {
 #pragma unroll
         for (int j = 0; j < TP; ++j)
 #pragma unroll
@@ -267,7 +214,7 @@ __device__ __forceinline__ void pair_quad_os(f32x4 (&S)[3][3][TP][2], f32x4 (&ac
               for (int coq = 0; coq < 2; ++coq) S[jj][kw][j][coq] = mfa(wmap.abid(t, coq, c), W[wmap.reg(t)], xv, S[jj][kw][j][coq]);
             }
           }
-        if (jj == 1) {
+        if (RIDER && jj == 1) {
 #pragma unroll
           for (int j = 0; j < TP; ++j)
 #pragma unroll
@@ -336,10 +283,10 @@ __global__ void __launch_bounds__(256, 2) vrn32a_row_kernel(Vrn32Args a) {
     float W[14];
 #pragma unroll
     for (int v = 0; v < 14; ++v) W[v] = wl[q * CH + v * 64 + lane];
-    if constexpr (QJ) { pair_quad_os<TP, 14>(S, acc2, W, P, O, v0, v1, v2, Map8()); return; }
+    if constexpr (QJ) { pair_channels_os<TP, 14, 4, true>(S, acc2, W, 0, P, O, v0, v1, v2, Map8()); return; }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      pair_channel_os<TP, 14>(S, W, c, P, O, v0, v1, v2, Map8());
+      pair_channels_os<TP, 14, 1, false>(S, acc2, W, c, P, O, v0, v1, v2, Map8());
       if (v1) {                                             // conv2_1 on the centre voxel: lanes 32..63 of register 13
 #pragma unroll
         for (int j = 0; j < TP; ++j)
@@ -394,7 +341,8 @@ __global__ void __launch_bounds__(256, 2) vrn32a_row_kernel(Vrn32Args a) {
 // ---------------------------------------------------------------------------------------------------------------
 // NONNEG: the caller vouches that x >= 0 (the block follows a ReLU layer); the sum with the ReLU'd branches needs no
 // second ReLU then (bit-identical)
-template <int LD, bool TRAIN = false, bool NONNEG = false, bool QJ = true>
+// (the unnamed last parameter: see vrn16a_row_kernel in vrn_row.hip)
+template <int LD, bool TRAIN = false, bool NONNEG = false, bool = true>
 __global__ void __launch_bounds__(256, 2) vrn32bc_row_kernel(Vrn32Args a) {
   constexpr int C12 = 27 * 64, C22 = 896;                   // floats per quad chunk of conv1_2 / conv2_2
   __shared__ float wl[2 * C12 + 2 * C22];
@@ -465,19 +413,11 @@ __global__ void __launch_bounds__(256, 2) vrn32bc_row_kernel(Vrn32Args a) {
       float W[27];
 #pragma unroll
       for (int v = 0; v < 27; ++v) W[v] = wl[v * 64 + lane];
-      if constexpr (QJ) pair_quad<1, 4, 27>(acc12, W, PA, OA, v0, v1, v2, l32, l31, Map16());
-      else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pair_channel<1, 4, 27>(acc12, W, c, PA, OA, v0, v1, v2, l32, l31, Map16());
-      }
+      pair_channels<1, 4, 27, 4>(acc12, W, 0, PA, OA, v0, v1, v2, l32, l31, Map16());
       load(PA, OA, p, 2);
 #pragma unroll
       for (int v = 0; v < 27; ++v) W[v] = wl[C12 + v * 64 + lane];
-      if constexpr (QJ) pair_quad<1, 4, 27>(acc12, W, PB, OB, v0, v1, v2, l32, l31, Map16());
-      else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pair_channel<1, 4, 27>(acc12, W, c, PB, OB, v0, v1, v2, l32, l31, Map16());
-      }
+      pair_channels<1, 4, 27, 4>(acc12, W, 0, PB, OB, v0, v1, v2, l32, l31, Map16());
       load(PB, OB, p, 3);
     }
     // residual row pair of output plane p-1 (out of range before the first finished plane: zeros, and the stores drop)
@@ -490,19 +430,11 @@ __global__ void __launch_bounds__(256, 2) vrn32bc_row_kernel(Vrn32Args a) {
       float W[14];
 #pragma unroll
       for (int v = 0; v < 14; ++v) W[v] = wl[2 * C12 + v * 64 + lane];
-      if constexpr (QJ) pair_quad<1, 2, 14>(acc22, W, PA, OA, v0, v1, v2, l32, l31, Map8());
-      else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pair_channel<1, 2, 14>(acc22, W, c, PA, OA, v0, v1, v2, l32, l31, Map8());
-      }
+      pair_channels<1, 2, 14, 4>(acc22, W, 0, PA, OA, v0, v1, v2, l32, l31, Map8());
       load(PA, OA, p + 1, 0);
 #pragma unroll
       for (int v = 0; v < 14; ++v) W[v] = wl[2 * C12 + C22 + v * 64 + lane];
-      if constexpr (QJ) pair_quad<1, 2, 14>(acc22, W, PB, OB, v0, v1, v2, l32, l31, Map8());
-      else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pair_channel<1, 2, 14>(acc22, W, c, PB, OB, v0, v1, v2, l32, l31, Map8());
-      }
+      pair_channels<1, 2, 14, 4>(acc22, W, 0, PB, OB, v0, v1, v2, l32, l31, Map8());
       load(PB, OB, p + 1, 1);
     }
     // output plane p-1: conv2_3 on relu(conv2_2), residual, ReLU, store
@@ -643,7 +575,7 @@ __global__ void __launch_bounds__(256, 2) up2_row_kernel(UpRowArgs a) {
     for (int c = 0; c < 4; ++c) { x0[c] = comp(P, c); x1[c] = comp(O, c); r0[c] = shr1p(x0[c], l32); r1[c] = shr1p(x1[c], l32); }
     const bool vj[3] = {v0, v1, v2};
 #pragma unroll
-    for (int s_ = 0; s_ < 3; ++s_) {                        // validity tests hoisted: one branch per (quad, output plane), see pair_quad
+    for (int s_ = 0; s_ < 3; ++s_) {                        // validity tests hoisted: one branch per (quad, output plane), see pair_channels
       const int kd = s_;
       if (vj[s_]) {
 #pragma unroll
@@ -687,9 +619,6 @@ __global__ void __launch_bounds__(256, 2) up2_row_kernel(UpRowArgs a) {
           raw_store4(v, ro, base + (ph * 4 + co) * (64 * 16) + pw * 16, 0, 0);
         }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
   // one input plane: every set holds the bias at the first step of the tile (nothing was born before it), later steps' fresh
   // sets are born by their first MFMA; a set whose step is skipped (v false) is either never stored or still holds the bias
   auto step = [&](int p, auto R0_, auto R1_, auto R2_) {
@@ -713,14 +642,7 @@ __global__ void __launch_bounds__(256, 2) up2_row_kernel(UpRowArgs a) {
   };
   load(PA, OA, d0 - 1, 0);
   load(PB, OB, d0 - 1, 1);
-#pragma unroll 1
-  for (int p = d0 - 1; p < d0 + LD; p += 3) {               // roles rotate instead of registers: (R0, R1, R2) -> (R2, R0, R1)
-    step(p, I0{}, I1{}, I2{});
-    if (p + 1 >= d0 + LD) break;
-    step(p + 1, I2{}, I0{}, I1{});
-    if (p + 2 >= d0 + LD) break;
-    step(p + 2, I1{}, I2{}, I0{});
-  }
+  PCGC_ROTATE3(d0 - 1, <, d0 + LD, step, true)              // (R0, R1, R2) -> (R2, R0, R1)
 }
 
 // LDS images of the two layers' filters (kind 0 = up_2 for up2_row_kernel<., 2>, kind 1 = down_1 for
@@ -968,7 +890,7 @@ int launch_down1_row(const float* x, float* y, const float* w, const float* bias
 // launches of the generic implicit-GEMM kernel per block (0.9 ms of a 10 ms step: profiles/r04_vD_train_kernel_stats.csv).
 // A transposed stride-1 convolution is a convolution with mirrored taps and swapped channel roles:
 //   dx[ci](v) = sum_t K[t][co][ci] g[co](v + off(t)),  K[t] = W[26 - t]^T
-// so the forward kernels' pair_channel machinery applies unchanged to LDS images of K.
+// so the forward kernels' pair_channels machinery applies unchanged to LDS images of K.
 //   vrn32a_bwd : dx = [x > 0] * ( dpre + conv1_1^T(dt11) (3^3, 8 -> 32) + conv2_1^T(dt21) (1^3, 8 -> 32) ); dx may alias dpre
 //   vrn32bc_bwd: dt11 = [t11 > 0] * conv1_2^T(dz12) (3^3, 16 -> 8);  dt22 = [t22 > 0] * conv2_3^T(dz23) (1^3, 16 -> 8), made
 //                on the fly for the three pair vectors conv2_2^T reads and written for the wave's own rows;
@@ -1030,7 +952,7 @@ __global__ void __launch_bounds__(256, 2) vrn32a_bwd_row_kernel(Vrn32BwdInArgs a
 #pragma unroll
       for (int v = 0; v < 27; ++v) W[v] = wl[(q * 2 + h) * C11 + v * 64 + lane];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) pair_channel<1, 4, 27>(acc[h], W, c, P, O, v0, v1, v2, l32, l31, Map16());
+      for (int c = 0; c < 4; ++c) pair_channels<1, 4, 27, 1>(acc[h], W, c, P, O, v0, v1, v2, l32, l31, Map16());
     }
   };
   load(PA, OA, d0 - 1, 0);
@@ -1163,12 +1085,12 @@ __global__ void __launch_bounds__(256, 2) vrn32bc_bwd_row_kernel(Vrn32BwdTailArg
 #pragma unroll
       for (int v = 0; v < 14; ++v) W[v] = wl[q * CK + v * 64 + lane];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) pair_channel<1, 2, 14>(acc12, W, c, PA, OA, v0, v1, v2, l32, l31, Map8());
+      for (int c = 0; c < 4; ++c) pair_channels<1, 2, 14, 1>(acc12, W, c, PA, OA, v0, v1, v2, l32, l31, Map8());
       if (q + 2 < 4) load12(PA, OA, p, q + 2); else load12(PA, OA, p + 1, 0);
 #pragma unroll
       for (int v = 0; v < 14; ++v) W[v] = wl[(q + 1) * CK + v * 64 + lane];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) pair_channel<1, 2, 14>(acc12, W, c, PB, OB, v0, v1, v2, l32, l31, Map8());
+      for (int c = 0; c < 4; ++c) pair_channels<1, 2, 14, 1>(acc12, W, c, PB, OB, v0, v1, v2, l32, l31, Map8());
     }
     // dt22 of this plane on the three pair vectors: the 1^3 layer's reverse, masked by t22 > 0
     f32x4 d22[3][2];
@@ -1198,7 +1120,7 @@ __global__ void __launch_bounds__(256, 2) vrn32bc_bwd_row_kernel(Vrn32BwdTailArg
       const f32x4 Pq[1] = {d22[0][q]};
       const f32x4 Oq[2] = {d22[1][q], d22[2][q]};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) pair_channel<1, 2, 14>(acc22, W, c, Pq, Oq, v0, v1, v2, l32, l31, Map8());
+      for (int c = 0; c < 4; ++c) pair_channels<1, 2, 14, 1>(acc22, W, c, Pq, Oq, v0, v1, v2, l32, l31, Map8());
     }
     // output plane p - 1: masks, stores
 #pragma unroll

@@ -121,6 +121,14 @@ __device__ __forceinline__ float shr_edge(float v, float edge) {
 __device__ __forceinline__ float shl_edge(float v, float edge) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x101, 0xf, 0xf, false));
 }
+// the shift source of the tap walks (row_common.h): channel c of row r and its kw = 0 / 2 neighbours, from the rows b0 and their edge values be
+__device__ __forceinline__ auto edge_rows(const f32x4 (&b0)[TH + 2], const f32x4 (&be)[TH + 2]) {
+  return [&b0, &be](int r, int c, float& x0, float& xm, float& xp) PCGC_INLINE {
+    x0 = comp(b0[r], c);
+    xm = shr_edge(x0, comp(be[r], c));
+    xp = shl_edge(x0, comp(be[r], c));
+  };
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // kernel A:  t12 = [ relu(conv1_1(x)) (3^3, 16 -> 4) | relu(conv2_1(x)) (1^3, 16 -> 4) ]     (vrn_row.hip: a_quad)
@@ -130,48 +138,27 @@ template <int P0, int P1, int P2, bool FRESH>
 __device__ __forceinline__ void a_pair(f32x4 (&S)[3][3][TH], f32x4 (&acc2)[TH], const f32x4& bias, const f32x4& bias2, const float (&W)[27],
                                        float W2, int ci0, int c0, const f32x4 (&b0)[TH + 2], const f32x4 (&be)[TH + 2], bool v0, bool v1,
                                        bool v2) {
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const auto rows = edge_rows(b0, be);
   float x0[2][TH + 2], xm[2][TH + 2], xp[2][TH + 2];
 #pragma unroll
   for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
-    for (int r = 0; r < TH + 2; ++r) {
-      x0[cc][r] = comp(b0[r], c0 + cc);
-      xm[cc][r] = shr_edge(x0[cc][r], comp(be[r], c0 + cc));
-      xp[cc][r] = shl_edge(x0[cc][r], comp(be[r], c0 + cc));
-    }
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;
-    if (vj[j]) {
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc) {
-        const int c = c0 + cc;
-#pragma unroll
-        for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-          for (int kh = 0; kh < 3; ++kh) {
-            const int jr = r - kh;
-            if (jr >= 0 && jr < TH) {
-#pragma unroll
-              for (int kw = 0; kw < 3; ++kw) {
-                const float xv = kw == 0 ? xm[cc][r] : (kw == 1 ? x0[cc][r] : xp[cc][r]);
-                const bool first = FRESH && c == 0 && j == 2 && kh == 0;
-                if (first) S[P[j]][kw][jr] = mfa_new(ci0 + c, W[(kd * 3 + kh) * 3 + kw], xv, kw == 1 ? bias : zero);
-                else S[P[j]][kw][jr] = mfa(ci0 + c, W[(kd * 3 + kh) * 3 + kw], xv, S[P[j]][kw][jr]);
-              }
-            }
-          }
-        if (j == 1) {
+    for (int r = 0; r < TH + 2; ++r) rows(r, c0 + cc, x0[cc][r], xm[cc][r], xp[cc][r]);
+  tap_walk<TH, P0, P1, P2, FRESH, 3, 2>(
+      v0, v1, v2,
+      [&](int set, int jr, int r, int kw, int t, bool born, int cc) PCGC_INLINE {
+        const float xv = kw == 0 ? xm[cc][r] : (kw == 1 ? x0[cc][r] : xp[cc][r]);
+        if (born) S[set][kw][jr] = mfa_new(ci0 + c0 + cc, W[t], xv, kw == 1 ? bias : zero);
+        else S[set][kw][jr] = mfa(ci0 + c0 + cc, W[t], xv, S[set][kw][jr]);
+      },
+      [&](int j, int cc) PCGC_INLINE {
+        if (j == 1) {                            // conv2_1 (1^3) of the wave's own rows rides in the centre plane's block
 #pragma unroll
           for (int jr = 0; jr < TH; ++jr)
-            acc2[jr] = (FRESH && c == 0) ? mfa_new(ci0 + c, W2, x0[cc][jr + 1], bias2) : mfa(ci0 + c, W2, x0[cc][jr + 1], acc2[jr]);
+            acc2[jr] = (FRESH && cc == 0) ? mfa_new(ci0 + c0 + cc, W2, x0[cc][jr + 1], bias2) : mfa(ci0 + c0 + cc, W2, x0[cc][jr + 1], acc2[jr]);
         }
-      }
-    }
-  }
+      });
 }
 template <int P0, int P1, int P2, bool FRESH>
 __device__ __forceinline__ void a_quad(f32x4 (&S)[3][3][TH], f32x4 (&acc2)[TH], const f32x4& bias, const f32x4& bias2, const float (&W)[27],
@@ -239,88 +226,12 @@ __global__ void __launch_bounds__(256, 2) vrn16a_seg_kernel(SegArgs a) {
       for (int r = 0; r < TH; ++r) raw_store4(relu4((S[P0][1][r] + S[P0][0][r]) + S[P0][2][r]), ws, (int)outb + r * kRow2, 0, 0);
     }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-#pragma unroll 1
-  for (int i = 0; i <= LD + 1; i += 3) {
-    step(i, I0{}, I1{}, I2{});
-    if (i + 1 > LD + 1) break;
-    step(i + 1, I1{}, I2{}, I0{});
-    if (i + 2 > LD + 1) break;
-    step(i + 2, I2{}, I0{}, I1{});
-  }
+  PCGC_ROTATE3(0, <=, LD + 1, step, false)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// kernel BC:  out = relu( x + [ relu(conv1_2(t11)) | relu(conv2_3(relu(conv2_2(t21)))) ] )      (vrn_row.hip: bc_channel12 / 22)
+// kernel BC:  out = relu( x + [ relu(conv1_2(t11)) | relu(conv2_3(relu(conv2_2(t21)))) ] )      (row_common.h: bc_channel12 / 22)
 // ---------------------------------------------------------------------------------------------------------------
-template <int P0, int P1, int P2, bool FRESH>
-__device__ __forceinline__ void bc_channel12(f32x4 (&acc)[3][TH][2], const f32x4 (&bias)[2], const float (&W)[14], int ci,
-                                             const f32x4 (&b0)[TH + 2], const f32x4 (&be)[TH + 2], bool v0, bool v1, bool v2) {
-  float x0[TH + 2], xm[TH + 2], xp[TH + 2];
-#pragma unroll
-  for (int r = 0; r < TH + 2; ++r) { x0[r] = comp(b0[r], ci); xm[r] = shr_edge(x0[r], comp(be[r], ci)); xp[r] = shl_edge(x0[r], comp(be[r], ci)); }
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;
-    if (vj[j]) {
-#pragma unroll
-      for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int jr = r - kh;
-          if (jr >= 0 && jr < TH) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const int t = (kd * 3 + kh) * 3 + kw;
-              const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
-#pragma unroll
-              for (int hf = 0; hf < 2; ++hf) {
-                const bool first = FRESH && j == 2 && kh == 0 && kw == 0;
-                acc[P[j]][jr][hf] = first ? mfa_new((t & 1) * 8 + ci * 2 + hf, W[t >> 1], xv, bias[hf])
-                                          : mfa((t & 1) * 8 + ci * 2 + hf, W[t >> 1], xv, acc[P[j]][jr][hf]);
-              }
-            }
-          }
-        }
-    }
-  }
-}
-
-template <int P0, int P1, int P2, bool FRESH>
-__device__ __forceinline__ void bc_channel22(f32x4 (&acc)[3][TH], const f32x4& bias, const float (&W)[7], int ci, const f32x4 (&b0)[TH + 2],
-                                             const f32x4 (&be)[TH + 2], bool v0, bool v1, bool v2) {
-  float x0[TH + 2], xm[TH + 2], xp[TH + 2];
-#pragma unroll
-  for (int r = 0; r < TH + 2; ++r) { x0[r] = comp(b0[r], ci); xm[r] = shr_edge(x0[r], comp(be[r], ci)); xp[r] = shl_edge(x0[r], comp(be[r], ci)); }
-  const bool vj[3] = {v0, v1, v2};
-  constexpr int P[3] = {P0, P1, P2};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int kd = 2 - j;
-    if (vj[j]) {
-#pragma unroll
-      for (int r = 0; r < TH + 2; ++r)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-          const int jr = r - kh;
-          if (jr >= 0 && jr < TH) {
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const int t = (kd * 3 + kh) * 3 + kw;
-              const float xv = kw == 0 ? xm[r] : (kw == 1 ? x0[r] : xp[r]);
-              const bool first = FRESH && j == 2 && kh == 0 && kw == 0;
-              acc[P[j]][jr] = first ? mfa_new((t & 3) * 4 + ci, W[t >> 2], xv, bias) : mfa((t & 3) * 4 + ci, W[t >> 2], xv, acc[P[j]][jr]);
-            }
-          }
-        }
-    }
-  }
-}
-
 template <bool NONNEG>
 __global__ void __launch_bounds__(256, 2) vrn16bc_seg_kernel(SegArgs a) {
   Slot sl;
@@ -361,9 +272,9 @@ __global__ void __launch_bounds__(256, 2) vrn16bc_seg_kernel(SegArgs a) {
   auto step = [&](int i, auto P0_, auto P1_, auto P2_) {
     constexpr int P0 = decltype(P0_)::value, P1 = decltype(P1_)::value, P2 = decltype(P2_)::value;
     const bool v0 = i >= 2, v1 = i >= 1 && i <= LD, v2 = i < LD;
-    bc_channel12<P0, P1, P2, true>(acc12, bi12, W12, 0, A0, Ae, v0, v1, v2);
+    bc_channel12<TH, P0, P1, P2, true>(acc12, bi12, W12, 0, edge_rows(A0, Ae), v0, v1, v2);
 #pragma unroll
-    for (int c = 1; c < 4; ++c) bc_channel12<P0, P1, P2, false>(acc12, bi12, W12, c, A0, Ae, v0, v1, v2);
+    for (int c = 1; c < 4; ++c) bc_channel12<TH, P0, P1, P2, false>(acc12, bi12, W12, c, edge_rows(A0, Ae), v0, v1, v2);
     if (i == 0 || i == LD) row_offsets(ro, sl, vb, baseT, baseE, i + 1);
     const int snext = (i + 1) * (kD * kRow2);
     load2<kRow2>(A0, Ae, rs, ro, snext);
@@ -375,9 +286,9 @@ __global__ void __launch_bounds__(256, 2) vrn16bc_seg_kernel(SegArgs a) {
     for (int r = 0; r < TH; ++r)
 #pragma unroll
       for (int q = 0; q < 4; ++q) res[r][q] = raw_load4(rs, (int)(done ? resb : kBad), obase + r * kRow4 + q * 1024, 0);
-    bc_channel22<P0, P1, P2, true>(acc22, bi22, W22, 0, B0, Be, v0, v1, v2);
+    bc_channel22<TH, P0, P1, P2, true>(acc22, bi22, W22, 0, edge_rows(B0, Be), v0, v1, v2);
 #pragma unroll
-    for (int c = 1; c < 4; ++c) bc_channel22<P0, P1, P2, false>(acc22, bi22, W22, c, B0, Be, v0, v1, v2);
+    for (int c = 1; c < 4; ++c) bc_channel22<TH, P0, P1, P2, false>(acc22, bi22, W22, c, edge_rows(B0, Be), v0, v1, v2);
     load2<kRow2>(B0, Be, rs, ro, snext + 1024);
     f32x4 t22[TH], q3[TH][2];
 #pragma unroll
@@ -400,17 +311,7 @@ __global__ void __launch_bounds__(256, 2) vrn16bc_seg_kernel(SegArgs a) {
       }
     }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-#pragma unroll 1
-  for (int i = 0; i <= LD + 1; i += 3) {
-    step(i, I0{}, I1{}, I2{});
-    if (i + 1 > LD + 1) break;
-    step(i + 1, I1{}, I2{}, I0{});
-    if (i + 2 > LD + 1) break;
-    step(i + 2, I2{}, I0{}, I1{});
-  }
+  PCGC_ROTATE3(0, <=, LD + 1, step, false)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -460,6 +361,7 @@ __global__ void __launch_bounds__(256, 2) conv_in_seg_kernel(ConvInSegArgs a) {
     float xm[TH + 2], xp[TH + 2];
 #pragma unroll
     for (int r = 0; r < TH + 2; ++r) { xm[r] = shr_edge(cur[r], cue[r]); xp[r] = shl_edge(cur[r], cue[r]); }
+    // (the tap walk of row_common.h, written out as in conv_in_row_kernel: a call to tap_walk from the kernel's own body gives it another schedule)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int kd = 2 - j;

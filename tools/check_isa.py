@@ -3,6 +3,7 @@ csrc/row_common.h: mfa_new) — the workaround is an addressing convention, so a
 silently undo it; this makes the object code itself the thing that is checked.
 
     python tools/check_isa.py            # every pcgcv1_amd/lib/obj/*.hip.o, exit 1 on a violation
+    python tools/check_isa.py --digest [DIR]   # SHA-256 of each code object's .text / .rodata / .note / .symtab (DIR: other objects)
 
 The hazard (round 2: one channel of lanes 12..15 of each row of 16 wrong, run to run different, only when two waves share
 a SIMD).  A `buffer_store_dwordx4` reads its four data registers over several cycles; an instruction right behind it that
@@ -24,6 +25,7 @@ The compiler version the objects were built with is printed with the result; tes
 tests/test_gpu_parity.py::test_every_row_kernel_is_slot_invariant_and_repeatable is the run-time side of it.
 """
 import glob
+import hashlib
 import os
 import re
 import shutil
@@ -40,19 +42,45 @@ _STORE = re.compile(r"^\s*buffer_store_dwordx4\s+v\[\d+:\d+\],\s*(\S+?),\s*s\[\d
 _VREG = re.compile(r"^v(\d+)$")
 
 
-def disassemble(obj):
-    """-> disassembly text of the gfx950 code object bundled in a hipcc host object"""
+def _with_code_object(obj, use):
+    """use(path of the gfx950 code object bundled in a hipcc host object, or None) -> its result"""
     d = tempfile.mkdtemp(prefix="pcgc_isa_")
     try:
         src = os.path.join(d, os.path.basename(obj))
         shutil.copy(obj, src)
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", src], check=True, capture_output=True)
         dev = [f for f in glob.glob(src + ".*") if "amdgcn" in f]
-        if not dev:
-            return ""
-        return subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", dev[0]], check=True, capture_output=True, text=True).stdout
+        return use(dev[0] if dev else None)
     finally:
         shutil.rmtree(d, ignore_errors=True)
+
+
+def disassemble(obj):
+    """-> disassembly text of the gfx950 code object bundled in a hipcc host object"""
+    def use(dev):
+        if not dev:
+            return ""
+        return subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", dev], check=True, capture_output=True, text=True).stdout
+    return _with_code_object(obj, use)
+
+
+DIGEST_SECTIONS = (".text", ".rodata", ".note", ".symtab")
+
+
+def digest(obj):
+    """-> {section: SHA-256 of its raw contents} of the code object: equal digests = the same instructions, kernel descriptors,
+    register / LDS / scratch numbers and symbols.  The sections left out hold the name of the compile-unit symbol
+    __hip_cuid_<hash>; build the two trees to compare at ONE path (profiles/row_tap_walk_isa.txt)."""
+    def use(dev):
+        if dev:                                              # one call, its rewritten copy thrown away: the input stays as hipcc made it
+            dump = [a for sec in DIGEST_SECTIONS for a in ("--dump-section", "%s=%s%s.bin" % (sec, dev, sec))]
+            subprocess.run([os.path.join(LLVM, "llvm-objcopy")] + dump + [dev, dev + ".copy"], capture_output=True)
+        out = {}
+        for sec in DIGEST_SECTIONS:                          # "-": no code object, or no such section in it
+            raw = (dev or "") + sec + ".bin"
+            out[sec] = hashlib.sha256(open(raw, "rb").read()).hexdigest() if dev and os.path.exists(raw) else "-"
+        return out
+    return _with_code_object(obj, use)
 
 
 def check_text(text):
@@ -90,10 +118,17 @@ def compiler_version():
 
 
 def main():
-    objs = sorted(glob.glob(os.path.join(OBJ, "*.hip.o")))
+    want_digest = "--digest" in sys.argv[1:]
+    obj_dir = ([a for a in sys.argv[1:] if not a.startswith("--")] + [OBJ])[0]
+    objs = sorted(glob.glob(os.path.join(obj_dir, "*.hip.o")))
     if not objs:
-        print("no objects under %s: run `python -m pcgcv1_amd.build` first" % OBJ)
+        print("no objects under %s: run `python -m pcgcv1_amd.build` first" % obj_dir)
         return 2
+    if want_digest:
+        for obj in objs:
+            for sec, h in digest(obj).items():
+                print("%-22s %-8s %s" % (os.path.basename(obj), sec, h))
+        return 0
     total_bad = []
     for obj in objs:
         n_mfma, n_store, bad, overlaps = check_text(disassemble(obj))

@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256, 2) seg_bc_kernel(Args a) {
   const int b = wv;
   if (b >= a.B) return;
   const int h0 = 4 * hq, w0 = 16 * s;
-  // weights as in vrn16bc_row_body: conv1_2 register tap >> 1, abid (tap & 1) * 8 + ci * 2 + half; conv2_2 register tap >> 2, abid
+  // weights as in bc_channel12 / bc_channel22 (csrc/row_common.h): conv1_2 register tap >> 1, abid (tap & 1) * 8 + ci * 2 + half; conv2_2 register tap >> 2, abid
   // (tap & 3) * 4 + ci; conv2_3 one register, abid ci * 2 + half
   float W12[14], W22[7];
 #pragma unroll
