@@ -434,7 +434,8 @@ __global__ void laplace_bwd_kernel(const float* yt, const float* loc, const floa
     float gy = 0.f, gl = 0.f, gb = 0.f;
     if (p >= bound && delta != 0.f) {
       const float sg = delta > 0.f ? 1.f : -1.f;
-      const float fu = eu / (2.f * b), fl = el / (2.f * b);          // Laplace density at the two edges
+      // Laplace density at the two edges; an edge exactly on loc has none: the gradient of tf.abs is sign(), 0 at 0
+      const float fu = au > 0.f ? eu / (2.f * b) : 0.f, fl = al > 0.f ? el / (2.f * b) : 0.f;
       const float gu = (up <= l ? 1.f : -1.f) * fu * au / b;          // d c / d scale
       const float gq = (lo <= l ? 1.f : -1.f) * fl * al / b;
       const float k = coef / p * sg;
