@@ -252,6 +252,32 @@ int pcgc_d2_transfer_normals(const int32_t* p, int64_t np, const float* normals_
 int pcgc_d2_mse(const int32_t* p, int64_t np, const int64_t* qkeys, int64_t nq, const float* normals_q, int res,
                 double* out2, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* D1 / D2 of pc_error between clouds that are NOT on the integer grid: float32 xyz, integral or not (a reconstruction
+ * scaled back by 1 / scale; any two clouds that were never voxelised).  All distances are float64 arithmetic on the
+ * coordinates as they are: d2(p, q) = (dx*dx + dy*dy) + dz*dz with dx = double(p.x) - double(q.x), in this association.
+ * The target cloud Q is bucketed into cubic cells of edge h, a power of two within [1, 2^20]:
+ *   cell = floor(q / h) - (ox, oy, oz), each component within [0, res), res <= 1024, |o| < 2^29,
+ * and is passed SORTED ascending by the cell key (cx*res + cy)*res + cz (any number of points per cell, in any order
+ * within one; that order is the order of the plane sums); per-point arrays of Q are in that order.  P may lie anywhere,
+ * also outside Q's grid, as long as |floor(p / h) - o| < 2^29.  best(p) = min over Q of d2; the search walks Chebyshev
+ * shells of cells around p's cell and stops after shell w once best + 1e-8 <= (w h)^2.  T(p) = EVERY q with
+ * |d2(p, q) - best(p)| < 1e-8 (pc_error's tie rule, absolute on squared distances; no cap on their number).
+ *   pcgc_offgrid_transfer_normals: normals_q[j] (double [nq,3]) = mean of normals_p[i] (float32) over every i with j in
+ *     T(p_i), as sum of llrint(n * 2^40) in int64 / 2^40 / count; zero where no point of P maps to j.
+ *   pcgc_offgrid_mse: out4 = (mean over p of best, max of best, mean over p of plane(p), max of plane) with plane(p) =
+ *     mean_{q in T(p)} ((p - q) . normals_q)^2, the dot product as (dx*nx + dy*ny) + dz*nz; normals_q double [nq,3] or
+ *     NULL: out4[2] = out4[3] = 0 then.  best double [np], plane double [np], n_ties int32 [np]: per point of P, all
+ *     three or all NULL.
+ * Deterministic (integer atomics / fixed-order double sums).  A Q that is not sorted or leaves the grid, or a coordinate
+ * outside the stated limits (a NaN included), touches no memory out of bounds and gives NaN in every output. */
+size_t pcgc_offgrid_workspace_bytes(int res, int64_t nq);
+int pcgc_offgrid_transfer_normals(const float* p, int64_t np, const float* normals_p, const float* q, int64_t nq, double h,
+                                  int ox, int oy, int oz, int res, double* normals_q, void* workspace,
+                                  size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, const double* normals_q, double h, int ox,
+                     int oy, int oz, int res, double* out4, double* best, double* plane, int32_t* n_ties,
+                     void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* Recolouring: the colours of the original cloud S (int32 xyz < res, unique, uint8 rgb per point) carried onto the decoded
  * geometry T, passed like the D2 target as its linear keys (x*res + y)*res + z, int64, SORTED ascending and unique;
  * target_colors uint8 [n_t,3] and backward_counts int32 [n_t] (may be NULL) are in that order.  With N_T(s) = all points

@@ -73,6 +73,11 @@ HIP_API = {
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),
     "pcgc_d2_transfer_normals": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_offgrid_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_offgrid_transfer_normals": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                              c_sz, c_vp]),
+    "pcgc_offgrid_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_double, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp, c_sz, c_vp]),
     "pcgc_recolor_workspace_bytes": (c_sz, [c_int, c_i64, c_i64]),
     "pcgc_recolor": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_color_mse_workspace_bytes": (c_sz, [c_int, c_i64]),

@@ -38,6 +38,7 @@ HIP_SOURCES = {
     "mesh.hip": ["-ffp-contract=off"],
     "pointnums.hip": ["-ffp-contract=off"],
     "color.hip": ["-ffp-contract=off"],
+    "offgrid.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

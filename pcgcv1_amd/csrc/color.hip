@@ -30,26 +30,7 @@ struct Grid {
 
 // index of the occupied cell idx among the set bits in key order
 __device__ __forceinline__ int64_t rank_of(const Grid& g, int64_t idx) {
-  const int64_t w = idx >> 5;
-  return (int64_t)g.rank[w] + __popc(g.bits[w] & ((1u << (idx & 31)) - 1u));
-}
-
-// rank[w] of every word, from the per-block offsets the scan of voxel_grid.h left
-__global__ void __launch_bounds__(kScanThreads) rank_write_kernel(const unsigned* bits, const int64_t* block_offset, unsigned* rank) {
-  unsigned w[kWordsPerThread];
-  const unsigned c = load_words(bits, blockIdx.x, w);
-  unsigned total;
-  unsigned o = (unsigned)block_offset[blockIdx.x] + block_scan(c, &total);
-  uint4* dst = reinterpret_cast<uint4*>(rank + (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
-#pragma unroll
-  for (int k = 0; k < kWordsPerThread / 4; ++k) {
-    uint4 r;
-    r.x = o; o += __popc(w[4 * k]);
-    r.y = o; o += __popc(w[4 * k + 1]);
-    r.z = o; o += __popc(w[4 * k + 2]);
-    r.w = o; o += __popc(w[4 * k + 3]);
-    dst[k] = r;
-  }
+  return rank_of(g.bits, g.rank, idx);
 }
 
 // the colours of a cloud in key order, one packed word (r | g << 8 | b << 16) per point
@@ -162,49 +143,6 @@ __global__ void color_mse_final_kernel(const double* partial, int nb, int64_t na
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct RankBuffers {
-  unsigned* bits;
-  unsigned* rank;
-  int64_t* block_count;
-  int64_t* n_set;
-  char* rest;                // what follows the rank structure in the workspace
-};
-
-size_t rank_bytes(int res) {
-  const int64_t nblk = scan_blocks((int64_t)res * res * res);
-  return 2 * align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) + 256;
-}
-
-RankBuffers rank_layout(int res, void* workspace) {
-  const int64_t nblk = scan_blocks((int64_t)res * res * res);
-  RankBuffers r;
-  char* w = static_cast<char*>(workspace);
-  r.bits = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(nblk));
-  r.rank = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(nblk));
-  r.block_count = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)nblk * sizeof(int64_t));
-  r.n_set = reinterpret_cast<int64_t*>(w);
-  r.rest = w + 256;
-  return r;
-}
-
-// bit set of a cloud given as points (keys == NULL) or as linear keys, and its rank structure
-int build_rank(const RankBuffers& r, int res, const int32_t* points, const int64_t* keys, int64_t n, hipStream_t s) {
-  const int64_t nblk = scan_blocks((int64_t)res * res * res);
-  PCGC_CHECK_HIP(hipMemsetAsync(r.bits, 0, padded_bits_bytes(nblk), s));
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  if (keys)
-    hipLaunchKernelGGL(bits_from_keys_kernel, dim3(grid), dim3(256), 0, s, keys, n, (int64_t)res * res * res, r.bits);
-  else
-    hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, r.bits);
-  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count);
-  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, r.block_count, nblk, r.n_set);
-  hipLaunchKernelGGL(rank_write_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count, r.rank);
-  return 0;
-}
-
 bool sizes_ok(int res, int64_t a, int64_t b) {
   return res > 0 && res <= 4096 && a > 0 && b > 0 && a <= 0x7FFFFFFF && b <= 0x7FFFFFFF;
 }

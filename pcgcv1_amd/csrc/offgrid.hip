@@ -1,0 +1,338 @@
+// D1 / D2 between clouds that are NOT on the integer grid (gfx950): pc_error's figures for a reconstruction scaled back by
+// 1 / scale, or for any two float32 clouds.  DESIGN.md "D1 / D2 off the grid" states the rule; tests/_offgrid_ref.py
+// restates it in numpy by brute force.
+//
+// The target cloud Q is bucketed into cubic cells of edge h (a power of two): cell = floor(q / h) - origin per axis, inside
+// a grid of res^3 cells.  Coordinates are never shifted or rescaled: every distance is float64 arithmetic on the float32
+// coordinates as they came, d2 = (dx*dx + dy*dy) + dz*dz with dx = double(p.x) - double(q.x) (the file is built with
+// -ffp-contract=off).  The cells are the occupancy bit set and rank table of voxel_grid.h; Q comes sorted by cell key, so
+// start[rank of a cell] .. start[rank + 1] are the points of that cell, any number of them.
+//
+// One thread per source point p, two passes:
+//   1. Chebyshev shells of cells around p's cell, clipped to the grid, keeping the minimal d2.  A point in an unvisited
+//      shell w' > w is farther than w h, so the walk ends after shell w once best + 1e-8 <= (w h)^2 — or when the grid is
+//      exhausted, which bounds the walk for a p outside Q's box.
+//   2. every point of the cube of those shells with |d2 - best| < 1e-8: pc_error's tie rule, no cap on their number.
+// Normal sums are 2^40 fixed-point int64 atomics (exact, order-free); the mse sums are float64 in a fixed order (per
+// thread, then a tree per workgroup, then the workgroups in index order).
+//
+// Input that breaks the contract (Q not sorted by cell or outside the grid, a coordinate whose cell no int holds, a NaN)
+// is met with no index out of bounds: it raises a flag in the workspace and the outputs come back as NaN.
+#include <algorithm>
+#include <cmath>
+#include "common.h"
+#include "voxel_grid.h"
+
+namespace pcgc {
+namespace {
+
+constexpr int kOffgridMaxRes = 1024;
+constexpr int kOffgridBlocks = 1024;
+constexpr double kTieEps = 1e-8;                    // on squared distances, absolute
+constexpr double kNormalFix = 1099511627776.0;      // 2^40 fixed point for the normal sums
+constexpr double kCellLimit = 536870912.0;          // 2^29: |cell - origin| and |origin| stay below it, so cell +- shell fits an int
+constexpr double kMinEdge = 1.0, kMaxEdge = 1048576.0;                  // 1 .. 2^20
+
+struct Cells {
+  double h;
+  int ox, oy, oz;            // the cell of the grid's corner
+  int res;
+};
+
+struct Target {
+  Cells c;
+  const unsigned* bits;
+  const unsigned* rank;
+  const int32_t* start;      // [occupied cells + 1]: first point of each occupied cell in key order, then nq
+  const float* q;            // [nq,3], sorted by cell key
+};
+
+// cell coordinate (relative to the grid's corner) of a coordinate; false when no int below 2^29 holds it, or for a NaN
+__device__ __forceinline__ bool cell_coord(float v, double h, int origin, int* c) {
+  const double f = floor((double)v / h) - (double)origin;
+  if (!(f > -kCellLimit && f < kCellLimit)) return false;
+  *c = (int)f;
+  return true;
+}
+
+__device__ __forceinline__ bool cell_of_point(const Cells& c, const float* p, int cell[3]) {
+  return cell_coord(p[0], c.h, c.ox, &cell[0]) && cell_coord(p[1], c.h, c.oy, &cell[1]) && cell_coord(p[2], c.h, c.oz, &cell[2]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the cells of Q
+// linear key of every point of Q, -1 (and the flag) for one outside the grid
+__global__ void __launch_bounds__(256) offgrid_keys_kernel(const float* q, int64_t nq, Cells c, int64_t* keys, int* bad) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nq) return;
+  int cell[3];
+  int64_t key = -1;
+  if (cell_of_point(c, q + j * 3, cell) && in_grid(c.res, cell[0], cell[1], cell[2])) key = cell_of(c.res, cell[0], cell[1], cell[2]);
+  if (key < 0) atomicOr(bad, 1);
+  keys[j] = key;
+}
+
+// start[r] = the first point of the r-th occupied cell, start[occupied cells] = nq.  Every occupied cell has a first point,
+// so every entry is written, with an index within [0, nq], whatever the order of Q; keys that descend raise the flag.
+__global__ void __launch_bounds__(256) offgrid_starts_kernel(const int64_t* keys, int64_t nq, const unsigned* bits, const unsigned* rank,
+                                                             const int64_t* n_set, int32_t* start, int* bad) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nq) return;
+  if (j == 0) start[*n_set] = (int32_t)nq;                  // n_set <= nq: the table has nq + 1 entries
+  const int64_t key = keys[j], prev = j ? keys[j - 1] : -1;
+  if (key < 0) return;
+  if (prev > key) atomicOr(bad, 1);
+  if (prev != key) start[rank_of(bits, rank, key)] = (int32_t)j;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- search
+__device__ __forceinline__ double dist2(const float* q, double px, double py, double pz) {
+  const double dx = px - (double)q[0], dy = py - (double)q[1], dz = pz - (double)q[2];
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// calls f(j) for every point j of the cell (x, y, z), which lies inside the grid
+template <typename F>
+__device__ __forceinline__ void for_each_in_cell(const Target& t, int x, int y, int z, F f) {
+  if (!bit_at(t.bits, t.c.res, x, y, z)) return;
+  const int64_t r = rank_of(t.bits, t.rank, cell_of(t.c.res, x, y, z));
+  for (int32_t j = t.start[r], end = t.start[r + 1]; j < end; ++j) f(j);
+}
+
+// Pass 1: the minimal d2 from p (in cell `cell`, which may lie outside the grid) to Q, and in *shell the last shell walked.
+// Shells before the first one that touches the grid hold nothing and are skipped; the last one that touches it ends the walk.
+__device__ __forceinline__ double nearest_offgrid(const Target& t, const int cell[3], double px, double py, double pz, int* shell) {
+  const int last = t.c.res - 1;
+  int w = 0, w_end = 0;
+  for (int a = 0; a < 3; ++a) {
+    w = max(w, max(-cell[a], cell[a] - last));
+    w_end = max(w_end, max(abs(cell[a]), abs(cell[a] - last)));
+  }
+  double best = INFINITY;
+  auto visit = [&](int x, int y, int z) {
+    for_each_in_cell(t, x, y, z, [&](int32_t j) { best = fmin(best, dist2(t.q + (int64_t)j * 3, px, py, pz)); });
+  };
+  for (;; ++w) {
+    for (int x = max(cell[0] - w, 0); x <= min(cell[0] + w, last); ++x)
+      for (int y = max(cell[1] - w, 0); y <= min(cell[1] + w, last); ++y) {
+        const int z0 = cell[2] - w, z1 = cell[2] + w;
+        if (abs(x - cell[0]) == w || abs(y - cell[1]) == w) {           // a side of the shell (all of shell 0): the whole column
+          for (int z = max(z0, 0); z <= min(z1, last); ++z) visit(x, y, z);
+        } else {                                                        // its two ends
+          if ((unsigned)z0 <= (unsigned)last) visit(x, y, z0);
+          if ((unsigned)z1 <= (unsigned)last) visit(x, y, z1);
+        }
+      }
+    const double reach = (double)w * t.c.h;
+    if (best + kTieEps <= reach * reach || w >= w_end) break;
+  }
+  *shell = w;
+  return best;
+}
+
+// Pass 2: f(j, dx, dy, dz) with d = p - q_j for every point of Q within 1e-8 of `best`, cells in x, y, z order, the points
+// of a cell in Q's order
+template <typename F>
+__device__ __forceinline__ void for_each_tied_offgrid(const Target& t, const int cell[3], double px, double py, double pz, double best,
+                                                      int shell, F f) {
+  const int last = t.c.res - 1;
+  for (int x = max(cell[0] - shell, 0); x <= min(cell[0] + shell, last); ++x)
+    for (int y = max(cell[1] - shell, 0); y <= min(cell[1] + shell, last); ++y)
+      for (int z = max(cell[2] - shell, 0); z <= min(cell[2] + shell, last); ++z)
+        for_each_in_cell(t, x, y, z, [&](int32_t j) {
+          const float* q = t.q + (int64_t)j * 3;
+          if (fabs(dist2(q, px, py, pz) - best) < kTieEps) f(j, px - (double)q[0], py - (double)q[1], pz - (double)q[2]);
+        });
+}
+
+// ---------------------------------------------------------------------------------------------------------------- normals
+__global__ void __launch_bounds__(256) offgrid_transfer_kernel(const float* p, int64_t np, const float* normals_p, Target t,
+                                                               long long* sums, int* counts, int* bad) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
+    int cell[3], shell;
+    if (!cell_of_point(t.c, p + i * 3, cell)) { atomicOr(bad, 1); continue; }
+    const double px = p[i * 3], py = p[i * 3 + 1], pz = p[i * 3 + 2];
+    const double best = nearest_offgrid(t, cell, px, py, pz, &shell);
+    long long fx[3];
+    for (int c = 0; c < 3; ++c) fx[c] = (long long)llrint((double)normals_p[i * 3 + c] * kNormalFix);
+    for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t j, double, double, double) {
+      for (int c = 0; c < 3; ++c) atomicAdd(reinterpret_cast<unsigned long long*>(&sums[(int64_t)j * 3 + c]), (unsigned long long)fx[c]);
+      atomicAdd(&counts[j], 1);
+    });
+  }
+}
+
+__global__ void __launch_bounds__(256) offgrid_normals_final_kernel(const long long* sums, const int* counts, int64_t nq, const int* bad,
+                                                                    double* normals_q) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= nq) return;
+  const int c = counts[j];
+  for (int k = 0; k < 3; ++k)
+    normals_q[j * 3 + k] = *bad ? (double)NAN : (c ? (double)sums[j * 3 + k] / kNormalFix / (double)c : 0.0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- mse
+// partial[k * kOffgridBlocks + b], k = sum of best, max of best, sum of plane, max of plane of workgroup b
+__global__ void __launch_bounds__(256) offgrid_mse_partial_kernel(const float* p, int64_t np, Target t, const double* normals_q,
+                                                                  double* partial, double* best_out, double* plane_out,
+                                                                  int32_t* ties_out, int* bad) {
+  __shared__ double sh[4][256];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
+    int cell[3], shell, ties = 0;
+    double best = NAN, plane = 0.0;
+    if (cell_of_point(t.c, p + i * 3, cell)) {
+      const double px = p[i * 3], py = p[i * 3 + 1], pz = p[i * 3 + 2];
+      best = nearest_offgrid(t, cell, px, py, pz, &shell);
+      double s = 0.0;
+      for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t j, double dx, double dy, double dz) {
+        if (normals_q) {
+          const double* n = normals_q + (int64_t)j * 3;
+          const double d = (dx * n[0] + dy * n[1]) + dz * n[2];
+          s += d * d;
+        }
+        ++ties;
+      });
+      if (ties) plane = s / (double)ties;
+    } else {
+      atomicOr(bad, 1);
+    }
+    if (best_out) { best_out[i] = best; plane_out[i] = plane; ties_out[i] = ties; }
+    acc[0] += best; acc[1] = fmax(acc[1], best);
+    acc[2] += plane; acc[3] = fmax(acc[3], plane);
+  }
+  for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] = acc[k];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+      sh[1][threadIdx.x] = fmax(sh[1][threadIdx.x], sh[1][threadIdx.x + o]);
+      sh[2][threadIdx.x] += sh[2][threadIdx.x + o];
+      sh[3][threadIdx.x] = fmax(sh[3][threadIdx.x], sh[3][threadIdx.x + o]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) partial[threadIdx.x * kOffgridBlocks + blockIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ void offgrid_mse_final_kernel(const double* partial, int nb, int64_t np, int with_plane, const int* bad, double* out4) {
+  if (threadIdx.x != 0) return;
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = 0; i < nb; ++i) {
+    v[0] += partial[i];
+    v[1] = fmax(v[1], partial[kOffgridBlocks + i]);
+    v[2] += partial[2 * kOffgridBlocks + i];
+    v[3] = fmax(v[3], partial[3 * kOffgridBlocks + i]);
+  }
+  v[0] /= (double)np;
+  v[2] /= (double)np;
+  for (int k = 0; k < 4; ++k) out4[k] = *bad ? (double)NAN : ((k < 2 || with_plane) ? v[k] : 0.0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+bool edge_ok(double h) {
+  int e;
+  return h >= kMinEdge && h <= kMaxEdge && std::frexp(h, &e) == 0.5;
+}
+
+bool grid_ok(double h, int ox, int oy, int oz, int res, int64_t np, int64_t nq) {
+  return edge_ok(h) && res >= 1 && res <= kOffgridMaxRes && std::abs((double)ox) < kCellLimit && std::abs((double)oy) < kCellLimit &&
+         std::abs((double)oz) < kCellLimit && np > 0 && nq > 0 && np <= 0x7FFFFFFF && nq < 0x7FFFFFFF;
+}
+
+struct OffgridBuffers {
+  RankBuffers r;
+  int64_t* keys;             // [nq]
+  int32_t* start;            // [nq + 1]
+  long long* sums;           // [nq,3]
+  int* counts;               // [nq]
+  double* partial;           // [4, kOffgridBlocks]
+  int* bad;
+};
+
+size_t offgrid_bytes(int res, int64_t nq) {
+  return rank_bytes(res) + align256((size_t)nq * sizeof(int64_t)) + align256((size_t)(nq + 1) * sizeof(int32_t)) +
+         align256((size_t)nq * 3 * sizeof(long long)) + align256((size_t)nq * sizeof(int)) +
+         align256(4 * kOffgridBlocks * sizeof(double)) + 256;
+}
+
+OffgridBuffers offgrid_layout(int res, int64_t nq, void* workspace) {
+  OffgridBuffers b;
+  b.r = rank_layout(res, workspace);
+  char* w = b.r.rest;
+  b.keys = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)nq * sizeof(int64_t));
+  b.start = reinterpret_cast<int32_t*>(w);
+  w += align256((size_t)(nq + 1) * sizeof(int32_t));
+  b.sums = reinterpret_cast<long long*>(w);
+  w += align256((size_t)nq * 3 * sizeof(long long));
+  b.counts = reinterpret_cast<int*>(w);
+  w += align256((size_t)nq * sizeof(int));
+  b.partial = reinterpret_cast<double*>(w);
+  w += align256(4 * kOffgridBlocks * sizeof(double));
+  b.bad = reinterpret_cast<int*>(w);
+  return b;
+}
+
+// the cells of Q: keys, bit set, rank table, cell starts; the flag starts at zero
+int build_target(const OffgridBuffers& b, const Cells& c, const float* q, int64_t nq, hipStream_t s, Target* t) {
+  const unsigned grid = (unsigned)((nq + 255) / 256);
+  PCGC_CHECK_HIP(hipMemsetAsync(b.bad, 0, sizeof(int), s));
+  hipLaunchKernelGGL(offgrid_keys_kernel, dim3(grid), dim3(256), 0, s, q, nq, c, b.keys, b.bad);
+  const int rc = build_rank(b.r, c.res, nullptr, b.keys, nq, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(offgrid_starts_kernel, dim3(grid), dim3(256), 0, s, b.keys, nq, b.r.bits, b.r.rank, b.r.n_set, b.start, b.bad);
+  *t = Target{c, b.r.bits, b.r.rank, b.start, q};
+  return 0;
+}
+
+}  // namespace
+}  // namespace pcgc
+
+using namespace pcgc;
+
+extern "C" {
+
+size_t pcgc_offgrid_workspace_bytes(int res, int64_t nq) {
+  if (res < 1 || res > kOffgridMaxRes || nq <= 0 || nq >= 0x7FFFFFFF) return 0;
+  return offgrid_bytes(res, nq);
+}
+
+int pcgc_offgrid_transfer_normals(const float* p, int64_t np, const float* normals_p, const float* q, int64_t nq, double h, int ox,
+                                  int oy, int oz, int res, double* normals_q, void* workspace, size_t workspace_bytes,
+                                  pcgc_stream_t stream) {
+  PCGC_REQUIRE(p && normals_p && q && normals_q && workspace && grid_ok(h, ox, oy, oz, res, np, nq),
+               "pcgc_offgrid_transfer_normals: bad arguments");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_offgrid_workspace_bytes(res, nq), "pcgc_offgrid_transfer_normals: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const OffgridBuffers b = offgrid_layout(res, nq, workspace);
+  Target t;
+  const int rc = build_target(b, Cells{h, ox, oy, oz, res}, q, nq, s, &t);
+  if (rc) return rc;
+  PCGC_CHECK_HIP(hipMemsetAsync(b.sums, 0, (size_t)nq * 3 * sizeof(long long), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.counts, 0, (size_t)nq * sizeof(int), s));
+  const int blocks = (int)std::min<int64_t>((np + 255) / 256, 4096);
+  hipLaunchKernelGGL(offgrid_transfer_kernel, dim3(blocks), dim3(256), 0, s, p, np, normals_p, t, b.sums, b.counts, b.bad);
+  hipLaunchKernelGGL(offgrid_normals_final_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, b.sums, b.counts, nq, b.bad,
+                     normals_q);
+  return launch_ok("off-grid normal transfer kernels");
+}
+
+int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, const double* normals_q, double h, int ox, int oy, int oz,
+                     int res, double* out4, double* best, double* plane, int32_t* n_ties, void* workspace, size_t workspace_bytes,
+                     pcgc_stream_t stream) {
+  PCGC_REQUIRE(p && q && out4 && workspace && grid_ok(h, ox, oy, oz, res, np, nq) && (best == nullptr) == (plane == nullptr) &&
+               (best == nullptr) == (n_ties == nullptr), "pcgc_offgrid_mse: bad arguments");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_offgrid_workspace_bytes(res, nq), "pcgc_offgrid_mse: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const OffgridBuffers b = offgrid_layout(res, nq, workspace);
+  Target t;
+  const int rc = build_target(b, Cells{h, ox, oy, oz, res}, q, nq, s, &t);
+  if (rc) return rc;
+  const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
+  hipLaunchKernelGGL(offgrid_mse_partial_kernel, dim3(blocks), dim3(256), 0, s, p, np, t, normals_q, b.partial, best, plane, n_ties,
+                     b.bad);
+  hipLaunchKernelGGL(offgrid_mse_final_kernel, dim3(1), dim3(64), 0, s, b.partial, blocks, np, normals_q ? 1 : 0, b.bad, out4);
+  return launch_ok("off-grid mse kernels");
+}
+
+}  // extern "C"

@@ -1,12 +1,13 @@
-// The voxel grid the D1 / D2 kernels (tail.hip), the colour kernels (color.hip) and the mesh kernels (mesh.hip) share:
+// The voxel grid the D1 / D2 kernels (tail.hip, offgrid.hip), the colour kernels (color.hip) and the mesh kernels (mesh.hip) share:
 // a cloud of integer points < res per axis as an occupancy bit set over res^3 cells, bit (x*res + y)*res + z of a flat
 // array of 32-bit words (the cell's linear key: ascending keys are np.unique's lexicographic order).  One copy each of
 //   * addressing: cell_of, in_grid, bit_at, and the two kernels that fill a zeroed bit set;
 //   * nearest_d2: the exact squared distance to the nearest occupied cell, by Chebyshev shells;
 //   * for_each_at_distance: every occupied cell at that distance, in a fixed order (the callers' float sums follow it);
 //   * the popcount scan that turns a bit set into per-block offsets of its set bits in key order;
+//   * the rank table over that scan: an occupied cell's index among the set bits (rank_of, build_rank);
 //   * find_sorted_key: lower bound in a sorted key list.
-// Everything here has internal linkage: the three objects link into one library.
+// Everything here has internal linkage: the objects link into one library.
 #pragma once
 #include <algorithm>
 #include "common.h"
@@ -171,12 +172,82 @@ __global__ void __launch_bounds__(1024) grid_block_scan_kernel(int64_t* block_co
   for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- rank table
+// rank[w] = number of set bits in words 0 .. w-1, one 32-bit entry per word of the padded bit set: the index of an occupied
+// cell among the set bits in key order is two loads, no search (color.hip's colours, offgrid.hip's cell starts).
+__device__ __forceinline__ int64_t rank_of(const unsigned* bits, const unsigned* rank, int64_t idx) {
+  const int64_t w = idx >> 5;
+  return (int64_t)rank[w] + __popc(bits[w] & ((1u << (idx & 31)) - 1u));
+}
+
+// rank[w] of every word, from the per-block offsets the scan above left
+__global__ void __launch_bounds__(kScanThreads) rank_write_kernel(const unsigned* bits, const int64_t* block_offset, unsigned* rank) {
+  unsigned w[kWordsPerThread];
+  const unsigned c = load_words(bits, blockIdx.x, w);
+  unsigned total;
+  unsigned o = (unsigned)block_offset[blockIdx.x] + block_scan(c, &total);
+  uint4* dst = reinterpret_cast<uint4*>(rank + (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread);
+#pragma unroll
+  for (int k = 0; k < kWordsPerThread / 4; ++k) {
+    uint4 r;
+    r.x = o; o += __popc(w[4 * k]);
+    r.y = o; o += __popc(w[4 * k + 1]);
+    r.z = o; o += __popc(w[4 * k + 2]);
+    r.w = o; o += __popc(w[4 * k + 3]);
+    dst[k] = r;
+  }
+}
+
 // host side: scan blocks of a grid of `cells` cells, bytes of its padded bit set, 256-byte rounding of a workspace part
 int64_t scan_blocks(int64_t cells) { return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32); }
 
 size_t padded_bits_bytes(int64_t nblk) { return (size_t)nblk * kScanWords * sizeof(unsigned); }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the rank structure at the head of a workspace, and what follows it
+struct RankBuffers {
+  unsigned* bits;
+  unsigned* rank;
+  int64_t* block_count;
+  int64_t* n_set;
+  char* rest;                // what follows the rank structure in the workspace
+};
+
+size_t rank_bytes(int res) {
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  return 2 * align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) + 256;
+}
+
+RankBuffers rank_layout(int res, void* workspace) {
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  RankBuffers r;
+  char* w = static_cast<char*>(workspace);
+  r.bits = reinterpret_cast<unsigned*>(w);
+  w += align256(padded_bits_bytes(nblk));
+  r.rank = reinterpret_cast<unsigned*>(w);
+  w += align256(padded_bits_bytes(nblk));
+  r.block_count = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)nblk * sizeof(int64_t));
+  r.n_set = reinterpret_cast<int64_t*>(w);
+  r.rest = w + 256;
+  return r;
+}
+
+// bit set of a cloud given as points (keys == NULL) or as linear keys, and its rank structure
+int build_rank(const RankBuffers& r, int res, const int32_t* points, const int64_t* keys, int64_t n, hipStream_t s) {
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  PCGC_CHECK_HIP(hipMemsetAsync(r.bits, 0, padded_bits_bytes(nblk), s));
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (keys)
+    hipLaunchKernelGGL(bits_from_keys_kernel, dim3(grid), dim3(256), 0, s, keys, n, (int64_t)res * res * res, r.bits);
+  else
+    hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, r.bits);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, r.block_count, nblk, r.n_set);
+  hipLaunchKernelGGL(rank_write_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count, r.rank);
+  return 0;
+}
 
 }  // namespace
 }  // namespace pcgc

@@ -24,15 +24,16 @@ from .recolor import recolored_metrics
 from .transform import compress_factorized, compress_hyper, compress_hyper_ahead, decompress_factorized, decompress_hyper
 
 
-def _d1_of(points, rec, resolution):
-    """mseF PSNR (p2point) of a reconstruction: on the device for a cloud on the integer grid, metrics.pc_error_off_grid for
-    one scaled back by 1 / scale (fractional coordinates, which pc_error measures as they are)."""
+def _d1_of(points, rec, resolution, offgrid="host"):
+    """mseF PSNR (p2point) of a reconstruction: on the device for a cloud on the integer grid; for one scaled back by
+    1 / scale (fractional coordinates, which pc_error measures as they are) metrics.pc_error_off_grid (offgrid="host") or
+    metrics.pc_error_float (offgrid="device")."""
     if metrics._off_grid(rec):
-        return metrics.pc_error(points, rec, None, resolution)["mseF,PSNR (p2point)"]
+        return metrics.pc_error(points, rec, None, resolution, off_grid=offgrid)["mseF,PSNR (p2point)"]
     return metrics.d1_psnr(points.astype(np.int32), np.rint(rec).astype(np.int32), resolution)
 
 
-def test_hyper(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64, rho=1.0, resolution=1023, rootdir=None):
+def test_hyper(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64, rho=1.0, resolution=1023, rootdir=None, offgrid="host"):
     points = np.asarray(points)
     cubes, cube_positions, points_numbers = preprocess_points(points, scale, cube_size, min_num)
     stream = compress_hyper(cubes, model, ckpt_dir)
@@ -48,7 +49,7 @@ def test_hyper(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64, rho
     names = ("strings", "strings_head", "strings_hyper", "pointnums", "cubepos")
     out = {"bpp": metrics.bpp(sum(sizes), n), "n_cubes": int(cubes.shape[0]), "n_points_in": int(n), "n_points_out": int(len(rec))}
     out.update({"bpp_" + k: metrics.bpp(v, n) for k, v in zip(names, sizes)})
-    out["d1_psnr"] = _d1_of(points, rec, resolution)
+    out["d1_psnr"] = _d1_of(points, rec, resolution, offgrid)
     if own_tmp:
         for k in names:
             os.remove(os.path.join(rootdir, "x." + k))
@@ -56,7 +57,8 @@ def test_hyper(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64, rho
     return out
 
 
-def test_factorized(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64, rho=1.0, resolution=1023, rootdir=None):
+def test_factorized(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64, rho=1.0, resolution=1023, rootdir=None,
+                    offgrid="host"):
     """eval.py:45-75: one rate point of --mode=factorized (analysis -> factorized prior on y -> three-file container ->
     synthesis); the bpp itemisation has no hyper / head terms (eval.py:69-70)."""
     points = np.asarray(points)
@@ -65,7 +67,7 @@ def test_factorized(points, model, ckpt_dir, scale=1.0, cube_size=64, min_num=64
     rec = postprocess_points(cubes_d, points_numbers, cube_positions, scale, cube_size, rho)
     out = {"bpp": bpps[0], "bpp_strings": bpps[1], "bpp_strings_hyper": bpps[2], "bpp_strings_head": bpps[3], "bpp_pointnums": bpps[4],
            "bpp_cubepos": bpps[5], "n_cubes": int(len(points_numbers)), "n_points_in": int(n), "n_points_out": int(len(rec))}
-    out["d1_psnr"] = _d1_of(points, rec, resolution)
+    out["d1_psnr"] = _d1_of(points, rec, resolution, offgrid)
     return out
 
 
@@ -240,7 +242,8 @@ def rate_point(points, model, ckpt_dir, scale, cube_size, min_num, rootdir=None,
 
 
 def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname="pcgcv1_amd.models.model_voxception",
-         fixed_thres=None, postfix="", estimate_normals=False, pointnums="count", color=False, color_qstep=None, color_coder="range"):
+         fixed_thres=None, postfix="", estimate_normals=False, pointnums="count", color=False, color_qstep=None, color_coder="range",
+         offgrid="host"):
     """eval.py:160-215.  The config .ini has DEFAULT {cube_size, min_num} and one section per rate with
     {scale, ckpt_dir, rho_d1, rho_d2} (eval.py:170-183).  Returns the list of result rows (dicts).
     estimate_normals=True: an input ply without normals gets them from metrics.estimate_normals(points, 10, 20) (the
@@ -255,7 +258,11 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
     color_qstep (with color=True): the recoloured rho = 1 reconstruction also goes through the RAHT colour codec (colorcodec.py) at
     that step; the row gains bpp_colors (the .colors bytes per input point) and "coded c[i],PSNRF", color_metrics of the original
     against the colour-decoded cloud.  scale must be 1 for such a rate.  color_coder: the entropy coder of that stream, "range"
-    (version 1) or "rans" (version 2, coded on the GPU); the decoded colours are the same, bpp_colors differs slightly."""
+    (version 1) or "rans" (version 2, coded on the GPU); the decoded colours are the same, bpp_colors differs slightly.
+    offgrid: where a rate section with scale != 1 (fractional reconstruction) is measured, "host" (metrics.pc_error_off_grid, scipy)
+    or "device" (metrics.pc_error_float, the HIP kernels: every tied neighbour counts, not the first 8)."""
+    if offgrid not in ("host", "device"):
+        raise ValueError("eval: offgrid must be 'host' or 'device' (got %r)" % (offgrid,))
     if mode not in ("hyper", "factorized"):
         raise ValueError("eval: mode must be 'hyper' or 'factorized' (got %r)" % (mode,))
     hyper = mode == "hyper"
@@ -308,7 +315,7 @@ def eval(input_file, rootdir, cfgdir, res, mode="hyper", cube_size=64, modelname
         def measure(rho):
             rec = reconstruct(rho)
             if metrics._off_grid(rec):                        # scale != 1: pc_error measures the float coordinates (process.py:76-77)
-                return metrics.pc_error(points, rec, normals, res - 1)
+                return metrics.pc_error(points, rec, normals, res - 1, off_grid=offgrid)
             rec = np.unique(np.rint(rec).astype(np.int32), axis=0)          # pc_error drops duplicate points (dropDuplicates 2)
             return metrics.pc_error(points, rec, normals, res - 1)
 
@@ -381,10 +388,13 @@ def main(argv=None):
                          "bpp_colors and the coded c[i],PSNRF")
     ap.add_argument("--color_coder", choices=("range", "rans"), default="range",
                     help="with --color_qstep: the entropy coder of the colour stream (range = version 1, rans = version 2, on the GPU)")
+    ap.add_argument("--offgrid", choices=("host", "device"), default="host",
+                    help="where a rate section with scale != 1 (fractional coordinates) gets its D1 / D2: scipy on the host, or the "
+                         "HIP kernels, which count every tied neighbour")
     a = ap.parse_args(argv)
     for input_file in sorted(a.input):
         for r in eval(input_file, a.rootdir, a.cfgdir, a.res, a.mode, a.cube_size, a.modelname, a.fixed_thres, a.postfix,
-                      a.estimate_normals, a.pointnums, a.color, a.color_qstep, a.color_coder):
+                      a.estimate_normals, a.pointnums, a.color, a.color_qstep, a.color_coder, a.offgrid):
             print(r)
 
 

@@ -164,9 +164,9 @@ def _off_grid(points):
 def pc_error_off_grid(points_a, points_b, normals_a=None, resolution=1023):
     """The same figures when the decoded cloud B is NOT on the integer grid: a rate point with scale != 1 (R1 = 5/8) is
     scaled back by 1 / scale as float32 and written as text (process.py:76-77), and pc_error measures those coordinates —
-    rounding them first moves D1 by a whole dB.  The device kernels search a voxel bitmap and cannot hold such a cloud, so
-    this path is a k-d tree on the host (scipy, float64 like pc_error): the eval harness' metric of ONE rate section, not
-    part of the codec.  Same definitions as d1_metrics / d2_metrics: T(p) = every target point at the minimal distance,
+    rounding them first moves D1 by a whole dB.  The kernels of d1_metrics / d2_metrics search a voxel bitmap and cannot
+    hold such a cloud; this path is a k-d tree on the host (scipy, float64 like pc_error, at most 8 ties per point), and
+    pc_error_float is the same rule on the device.  Same definitions as d1_metrics / d2_metrics: T(p) = every target point at the minimal distance,
     B's normals transferred from A as the plain mean over the points that chose it.  Pinned against the prebuilt pc_error_d
     on the config-3 frame's R1 section (tests/golden/oracle_a0.75b3_cloud2000_s0.625.npz)."""
     from scipy.spatial import cKDTree
@@ -218,15 +218,148 @@ def pc_error_off_grid(points_a, points_b, normals_a=None, resolution=1023):
     return out
 
 
-def pc_error(points_a, points_b, normals_a=None, resolution=1023, colors_a=None, colors_b=None):
+OFFGRID_MAX_CELLS = 1024          # cells per axis of the device search's grid (csrc/offgrid.hip)
+OFFGRID_MAX_EDGE = 2.0 ** 20      # its largest cell edge
+OFFGRID_MAX_CELL = 2 ** 28        # |floor(x / edge)| of every coordinate of either cloud stays below this (|cell - origin| < 2^29)
+
+
+def _offgrid_cells(target, source):
+    """-> (h, origin [3], res) of the grid pcgc_offgrid_* searches `target` (float32 [N,3]) in: the smallest power of two
+    h >= 1 with at most OFFGRID_MAX_CELLS cells of edge h per axis between the target's extremes; sized from the data."""
+    ends = [np.stack([x.min(0), x.max(0)]).astype(np.float64) for x in (target, source)]       # a NaN anywhere shows in them
+    if not all(np.isfinite(e).all() for e in ends):
+        raise ValueError("pc_error_float: coordinates must be finite")
+    lo, hi = ends[0]
+    h = 1.0
+    while int((np.floor(hi / h) - np.floor(lo / h)).max()) + 1 > OFFGRID_MAX_CELLS:
+        h *= 2.0
+        if h > OFFGRID_MAX_EDGE:
+            raise ValueError("pc_error_float: a cloud of extent %g needs cells wider than 2^20 to fit %d cells per axis; the "
+                             "device search supports a cell edge of at most 2^20" % (float((hi - lo).max()), OFFGRID_MAX_CELLS))
+    origin = np.floor(lo / h)
+    far = max(float(np.abs(np.floor(e / h)).max()) for e in ends)          # floor is monotone: the extremes bound every cell
+    if far >= OFFGRID_MAX_CELL:
+        raise ValueError("pc_error_float: coordinate / cell edge reaches %g; the device search supports less than 2^28 cells "
+                         "from zero (cell edge %g)" % (far, h))
+    return h, origin.astype(np.int64), int((np.floor(hi / h) - origin).max()) + 1
+
+
+class _OffgridTarget:
+    """a cloud as pcgc_offgrid_* searches it: its cell rule against one source cloud, and its points sorted by cell key"""
+
+    def __init__(self, target, source, dev):
+        self.h, origin, self.res = _offgrid_cells(target, source)
+        self.origin = [int(v) for v in origin]
+        q = torch.from_numpy(target).to(dev)
+        cell = torch.floor(q.to(torch.float64) / self.h).to(torch.int64) - torch.from_numpy(origin).to(dev)
+        keys = (cell[:, 0] * self.res + cell[:, 1]) * self.res + cell[:, 2]
+        self.order = torch.sort(keys, stable=True)[1]
+        self.points = q[self.order].contiguous()
+
+    def grid(self):
+        return (self.h, self.origin[0], self.origin[1], self.origin[2], self.res)
+
+
+def _offgrid_mse(p_d, target, normals_t, ws, per_point=False):
+    """pcgc_offgrid_mse of the device cloud p_d against an _OffgridTarget (normals_t: float64 device tensor in the target's
+    sorted order, or None) -> the four figures; per_point=True: also (best, plane, n_ties) numpy arrays per point of p_d"""
+    dev, n = p_d.device, p_d.shape[0]
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    best = torch.empty(n, dtype=torch.float64, device=dev) if per_point else None
+    plane = torch.empty(n, dtype=torch.float64, device=dev) if per_point else None
+    ties = torch.empty(n, dtype=torch.int32, device=dev) if per_point else None
+    _lib.check(_lib.hip().pcgc_offgrid_mse(_lib.dptr(p_d), n, _lib.dptr(target.points), target.points.shape[0], _lib.dptr(normals_t),
+                                           *target.grid(), _lib.dptr(out), _lib.dptr(best), _lib.dptr(plane), _lib.dptr(ties),
+                                           _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_offgrid_mse")
+    figures = [float(v) for v in out.cpu().numpy()]
+    if any(np.isnan(figures)):
+        raise RuntimeError("pcgc_offgrid_mse: the clouds break the cell rule (include/pcgc.h)")
+    if per_point:
+        return figures, (best.cpu().numpy(), plane.cpu().numpy(), ties.cpu().numpy())
+    return figures
+
+
+def _offgrid_transfer(p_d, normals_p, target, ws):
+    """pcgc_offgrid_transfer_normals: float64 device tensor [n_target, 3] in the target's sorted order"""
+    out = torch.empty((target.points.shape[0], 3), dtype=torch.float64, device=p_d.device)
+    _lib.check(_lib.hip().pcgc_offgrid_transfer_normals(_lib.dptr(p_d), p_d.shape[0], _lib.dptr(normals_p), _lib.dptr(target.points),
+                                                        target.points.shape[0], *target.grid(), _lib.dptr(out), _lib.dptr(ws),
+                                                        ws.numel(), _lib.stream()), "pcgc_offgrid_transfer_normals")
+    return out
+
+
+def _float32_cloud(points, what):
+    p = np.asarray(points)
+    p32 = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+    if len(p32) == 0 or not np.array_equal(p32.astype(np.float64), np.asarray(p, np.float64).reshape(-1, 3)):
+        raise ValueError("pc_error_float: %s must be a non-empty cloud of float32-representable coordinates" % what)
+    return p32
+
+
+def pc_error_float(points_a, points_b, normals_a=None, resolution=1023, per_point=False):
+    """pc_error_off_grid on the device (csrc/offgrid.hip; include/pcgc.h, pcgc_offgrid_*): the same keys and the same rule
+    for two clouds of any float32-representable coordinates, integral or not, neither of them voxelised.  B loses its
+    duplicate points (np.unique of the float32 rows, as the host path does), A is taken as it is.  Every tied nearest
+    neighbour counts (squared distances within 1e-8 of the minimum), however many there are; no scipy.
+    Raises ValueError when a cloud's extent / 1024 needs a cell edge above 2^20, the widest the search supports.
+    per_point=True: -> (dict, {"1": (best, plane, n_ties) per point of A, "2": the same per point of the deduplicated B in
+    np.unique's order, "normals_b": the normals B received, float64, in that order})."""
+    dev = _lib.require_gpu()
+    a = _float32_cloud(points_a, "cloud A")
+    b = np.unique(_float32_cloud(points_b, "cloud B"), axis=0)
+    tb, ta = _OffgridTarget(b, a, dev), _OffgridTarget(a, b, dev)
+    lib = _lib.hip()
+    ws = torch.empty(int(max(lib.pcgc_offgrid_workspace_bytes(tb.res, len(b)), lib.pcgc_offgrid_workspace_bytes(ta.res, len(a)))),
+                     dtype=torch.uint8, device=dev)
+    a_d, b_d = ta.points, tb.points                           # either order of a source cloud gives the same sums: use the sorted
+    nb_d = na_d = None
+    if normals_a is not None:
+        na = np.ascontiguousarray(normals_a, np.float32).reshape(-1, 3)
+        if len(na) != len(a):
+            raise ValueError("pc_error_float: %d normals for %d points" % (len(na), len(a)))
+        na32 = torch.from_numpy(na).to(dev)[ta.order].contiguous()
+        nb_d, na_d = _offgrid_transfer(a_d, na32, tb, ws), na32.to(torch.float64)
+    peak = float(resolution)
+
+    def psnr(m):
+        return float("inf") if m == 0 else 10.0 * np.log10(3.0 * peak * peak / m)
+    r1 = _offgrid_mse(a_d, tb, nb_d, ws, per_point)
+    r2 = _offgrid_mse(b_d, ta, na_d, ws, per_point)
+    (mse1, h1, m1, p1), (mse2, h2, m2, p2) = (r1[0], r2[0]) if per_point else (r1, r2)
+    out = {"mse1      (p2point)": mse1, "mse2      (p2point)": mse2, "mseF      (p2point)": max(mse1, mse2),
+           "mse1,PSNR (p2point)": psnr(mse1), "mse2,PSNR (p2point)": psnr(mse2), "mseF,PSNR (p2point)": psnr(max(mse1, mse2)),
+           "h.       1(p2point)": h1, "h.       2(p2point)": h2, "h.        (p2point)": max(h1, h2)}
+    if normals_a is not None:
+        out.update({"mse1      (p2plane)": m1, "mse2      (p2plane)": m2, "mseF      (p2plane)": max(m1, m2),
+                    "mse1,PSNR (p2plane)": psnr(m1), "mse2,PSNR (p2plane)": psnr(m2), "mseF,PSNR (p2plane)": psnr(max(m1, m2)),
+                    "h.       1(p2plane)": p1, "h.       2(p2plane)": p2, "h.        (p2plane)": max(p1, p2)})
+    if not per_point:
+        return out
+
+    def unsort(values, order):                                # per-point arrays back from the sorted order to the caller's
+        back = np.empty_like(values)
+        back[order.cpu().numpy()] = values
+        return back
+    detail = {"1": tuple(unsort(v, ta.order) for v in r1[1]), "2": tuple(unsort(v, tb.order) for v in r2[1])}
+    if normals_a is not None:
+        detail["normals_b"] = unsort(nb_d.cpu().numpy(), tb.order)
+    return out, detail
+
+
+def pc_error(points_a, points_b, normals_a=None, resolution=1023, colors_a=None, colors_b=None, off_grid="host"):
     """All figures of myutils/pc_error_wrapper.pc_error (26-75) as one dict: D1 always, D2 when normals are given.
-    points_b with fractional coordinates (a rate point with scale != 1): pc_error_off_grid.
+    points_b with fractional coordinates (a rate point with scale != 1): pc_error_off_grid (off_grid="host", a k-d tree in
+    scipy, at most 8 ties per point) or pc_error_float (off_grid="device", the HIP kernels, every tie).
     colors_a and colors_b (uint8 [N,3], both): the colour keys of `--color=1` as well (color_metrics; voxelised clouds only)."""
+    if off_grid not in ("host", "device"):
+        raise ValueError("pc_error: off_grid must be 'host' or 'device' (got %r)" % (off_grid,))
     if (colors_a is None) != (colors_b is None):
         raise ValueError("pc_error: colours of both clouds are needed for the colour figures")
     if _off_grid(points_b):
         if colors_a is not None:
             raise ValueError("pc_error: the colour figures need a cloud on the integer grid")
+        if off_grid == "device":
+            return pc_error_float(points_a, points_b, normals_a, resolution)
         return pc_error_off_grid(points_a, points_b, normals_a, resolution)
     out = d1_metrics(points_a, points_b, resolution)
     if normals_a is not None:
