@@ -10,6 +10,7 @@
 
 #include "../../include/pcgc.h"
 #include "net_plan.h"      // kSkipLaunches, kSkipLaunchesMid, kSegLaunches, kSegMaxChunk
+#include "dw_plan.h"       // DwKernel, conv_dw_tile_groups, conv_dw_pair_supported, bwd_weight_partial_floats
 
 namespace pcgc {
 
@@ -255,15 +256,13 @@ size_t vrn64_image_floats();
 int launch_vrn64_image(const float* const* w, float* dst, hipStream_t s);
 // pack TF-layout weights for the MFMA kernel of this shape; returns floats needed (count_only) or packs
 size_t mfma_packed_floats(int Cin, int Cout, int ksize, int mode);
-// train_dw.hip: tiled weight gradient of the stride-1 convs; partial = [groups][taps][Cin][Cout]
-int conv_dw_tile_groups(int B, int D);
-int conv_dw_tile_groups_s2(int B, int D);
+// train_dw.hip: the tiled weight-gradient kernels dw_plan.h chooses among; partial = [groups][taps][Cin][Cout] (+ bias sums).
+// 1 launched, 0 no tiled kernel for this shape (the caller runs the generic one), < 0 error.
 // *_q4: that operand is in the Q4 layout [d][h][C/4][w][4] instead of NDHWC (the training step's 64^3 stage)
 int launch_conv_dw_tile_s2(const float* fine, const float* coarse, float* partial, int B, int D, int Ca, int Cb, int with_bias,
                            hipStream_t s, int fine_q4 = 0);
 int launch_conv_dw_tile(const float* x, const float* dz, float* partial, int B, int D, int Cin, int Cout, int ksize,
                         int with_bias, hipStream_t s, int x_q4 = 0, int dz_q4 = 0);
-bool conv_dw_pair_supported(int D, int Cin, int Cout);
 int launch_conv_dw_pair(const float* x, const float* dz3, const float* dz1, float* partial3, float* partial1, int B, int D,
                         int Cin, int Cout, int with_bias, hipStream_t s, int x_q4 = 0);
 int pack_weights_mfma(const float* w_tf, float* packed, int Cin, int Cout, int ksize, int mode, hipStream_t s);
@@ -297,10 +296,10 @@ struct FinalJobs {
 // jobs of one launch — the deferred mode of the training plan (pcgc_train_plan_defer_small)
 constexpr int kDwBatchMax = 8;
 struct DwCall {
-  int kind;                          // 0 / 1 / 2: conv_dw_mfma_kernel<16 / 32 / 64, 1, 16>; 3 / 4: conv_dw_tile_kernel<16, 16 / 32, 1>
+  DwKernel kernel;                   // one whose DwChoice is batchable
   const float *x, *dz;
   float* partial;
-  int B, D, Cin, groups, with_bias;
+  int B, D, Cin, groups, chunks, with_bias;
 };
 void dw_capture_begin(std::vector<DwCall>* sink);
 void dw_capture_end();
@@ -311,7 +310,6 @@ int bwd_data_impl(const float* dz, const float* kernel, const float* wt_ready, c
                   const float* relu_mask, const float* add_to, int B, int D, int Cin, int Cout, int ksize, int stride, int transposed,
                   float* wt_scratch, float* packed_scratch, hipStream_t s, int x_q4 = 0, int dz_q4 = 0);   // x_q4: dx / mask / add_to
 int launch_hyper_row_conv(const ConvArgs& a, hipStream_t s);   // hyper_row.hip: 1 launched, 0 not an 8^3 hyper layer, < 0 error
-size_t bwd_weight_partial_floats(int B, int D, int Cin, int Cout, int ksize, int stride, int transposed, size_t* bias_floats);
 int bwd_weight_impl(const float* x, const float* dz, float* dkernel, float* dbias, int B, int D, int Cin, int Cout, int ksize,
                     int stride, int transposed, float* partial, float* bias_partial, std::vector<FinalJob>* sink, hipStream_t s,
                     int x_q4 = 0, int dz_q4 = 0);

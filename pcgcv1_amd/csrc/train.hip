@@ -127,8 +127,6 @@ __global__ void abs_max_bwd_kernel(const float* dscale, const float* s, float lb
 // dW[tap][ci][co] (conv) or dW[tap][co][ci] (tconv) = sum over (b, voxel) x[in(voxel, tap)][ci] * dz[voxel][co].
 // grid = (taps, NCHUNK); a block owns one tap and a contiguous range of output voxels (conv) / input voxels
 // (tconv), stages 64 voxels of x and dz in LDS at a time and keeps its Cin*Cout partial sums in registers.
-constexpr int kDwChunks = 128;
-constexpr int kDwPartials = 512;   // workspace slots per weight: max(kDwChunks, train_dw.hip's persistent groups)
 constexpr int kDwVox = 64;
 
 template <int MAXPAIRS>   // pairs per thread = ceil(Cin*Cout / 256) <= MAXPAIRS
@@ -781,14 +779,6 @@ int bwd_data_impl(const float* dz, const float* kernel, const float* wt_ready, c
   if (x_q4 || dz_q4) { set_error("bwd-data on Q4 tensors: no MFMA kernel for Cin=%d Cout=%d stride=%d transposed=%d", Cin, Cout, stride, transposed); return -1; }
   if ((rc = launch_hyper_row_conv(a, s)) != 0) return rc < 0 ? rc : 0;        // the 8^3 hyper layers: row kernels
   return launch_conv_direct(a, s);
-}
-
-// floats of partial sums one layer's weight gradient needs at (B, D): *bias_floats more for the bias-only partials
-size_t bwd_weight_partial_floats(int B, int D, int Cin, int Cout, int ksize, int stride, int transposed, size_t* bias_floats) {
-  const size_t wn = (size_t)ksize * ksize * ksize * Cin * Cout;
-  const int groups = transposed ? conv_dw_tile_groups_s2(B, D) : (stride == 2 ? conv_dw_tile_groups_s2(B, D / 2) : conv_dw_tile_groups(B, D));
-  *bias_floats = (size_t)1024 * Cout;
-  return (size_t)std::max(groups, kDwChunks) * (wn + Cout);
 }
 
 // Weight (and bias) gradient of one layer.  sink == nullptr: the final reductions are launched here; otherwise they

@@ -1,24 +1,37 @@
-// Weight gradient of the stride-1 3x3x3 convolutions (train_hyper.py:200-207, tf.GradientTape over the
-// model_voxception.py layers) as an LDS-tiled VALU kernel.
+// Weight gradients of the training step's convolutions (train_hyper.py:200-207, tf.GradientTape over the
+// model_voxception.py layers):
 //
 //   dW[tap][ci][co] = sum over (cube, voxel v)  x[v + tap - 1][ci] * dz[v][co]
 //
-// The reduction runs over millions of voxels and the result is tiny (27*Cin*Cout floats), so the tiling is the
-// transpose of the forward kernels': a workgroup walks 4 x 4 x 16-voxel tiles (x tile with halo and dz tile in
-// LDS, each global byte read once per channel chunk instead of once per tap) and every thread keeps a TI x TJ
-// register block of dW for one tap.  With T = 27 * (CIN/TI) * (COUT/TJ) such blocks per channel chunk,
-//   T <  256: S = 256 / T threads share a block and split the voxels of each tile (fixed-order LDS reduction),
-//   T >= 256: a thread owns ceil(T / 256) blocks.
-// Workgroups are persistent (grid.x of them, each summing a fixed, strided set of tiles in a fixed order) and
-// write one partial dW each; conv_dw_final_kernel (train.hip) adds the partials in index order.  No float
-// atomics anywhere: the result is bit-reproducible for a given (shape, grid).
-#include <cstdlib>
+// The reduction runs over millions of voxels and the result is tiny (27 * Cin * Cout floats), so every kernel here is
+// persistent: grid.x workgroups walk a fixed, strided set of voxel tiles in a fixed order with the sums in registers and
+// write one partial dW each (+ the bias sums of dz behind it); conv_dw_final_kernel (train.hip) adds the partials in index
+// order.  No float atomics anywhere: the result is bit-reproducible for a given (shape, grid).
+//
+// Which kernel a call takes is decided in dw_plan.h (dw_choose, dw_choose_s2, dw_choose_pair: the ladder and why it has the
+// order it has; tests/dw_plan_check.cpp checks it on the CPU); launch_dw below maps the choice to the instantiation:
+//   64^3 stage (C = 16 blocks, Q4 or NDHWC)
+//     conv_in 1 -> 16, deconv_out 16 -> 1             conv_dw_mfma_edge_kernel      the 27 taps fill the 1-channel side
+//     conv1_1 16 -> 4 + conv2_1 16 -> 4 (1^3)         conv_dw_mfma_16xn_kernel<4, true>   one pass over the block input
+//     conv1_2 4 -> 8, conv2_2 4 -> 4                  conv_dw_mfma_4xn_kernel       taps on both MFMA dimensions, whole rows
+//     conv2_3 4 -> 8 (1^3)                            conv_dw_1x1_kernel            sums in registers, operands read once
+//   32^3 stage (C = 32 blocks)
+//     conv1_1 32 -> 8 + conv2_1 32 -> 8 (1^3)         conv_dw_mfma_16xn_kernel<8, true>
+//     conv1_2 8 -> 16                                 conv_dw_mfma_kernel<16, 1, 8>   two taps per row block
+//     conv2_2 8 -> 8                                  conv_dw_slide_kernel<8, 8, 8>
+//     conv2_3 8 -> 16 (1^3)                           conv_dw_tile1_kernel<8, 16>
+//   16^3 stage (C = 64 blocks), conv_out, deconv_in, the hyper encoder's conv1
+//     3^3 with 16 | Cin and Cout 16 / 32 / 64         conv_dw_mfma_kernel<COUT, 1>
+//     conv2_1 64 -> 16, conv2_3 16 -> 32 (1^3)        conv_dw_tile1_kernel<16, 16 / 32>
+//     the pair kernel's shapes called one by one      conv_dw_mfma_16xn_kernel<4 / 8>, conv_dw_1x1_kernel<16, 4>, tile1<16, 8>
+//     4 -> 4 / 8 below 64^3 (a C = 16 block there)    conv_dw_slide_kernel<4, 4 / 8, 4>
+//   down_1, down_2, up_1, up_2 (stride 2)             conv_dw_mfma_kernel<Cb, 2>    16 | Ca, Cb 16 / 32 / 64, 16 | coarse D
+//   anything else (16 does not divide D: the hyperprior nets below 16^3; the 5^3 / 9^3 filters of the simple model; other
+//   channel counts)                                   conv_dw_partial_kernel (train.hip), any shape, not tuned
 #include <vector>
 #include "mfma_common.h"
 
 namespace pcgc {
-
-constexpr int kDwGroups = 512;     // persistent workgroups (x2 per CU) = partial sums per weight
 
 // Several weight gradients of the same shape in one launch (grid.z = job): the 16^3 stage of the training step has 30 of
 // them per step with 128-512 workgroups each, which leave most wave slots idle one at a time.  n = 0: the plain arguments.
@@ -34,26 +47,23 @@ static thread_local std::vector<DwCall>* t_dw_capture = nullptr;
 void dw_capture_begin(std::vector<DwCall>* sink) { t_dw_capture = sink; }
 void dw_capture_end() { t_dw_capture = nullptr; }
 
-// STRIDE 2 (k = 3): the first operand lives on the twice finer grid, x[2o + k] pairs with dz[o] — the stride-2 conv
-// (x = layer input, dz = output gradient, result [tap][ci][co]) and, with the operands swapped, the transposed conv
-// (first operand = dz on the fine grid, second = x, result [tap][co][ci] = the TF layout of its kernel).
-template <int CIN, int COUT, int KS, int STRIDE = 1>
-__global__ void __launch_bounds__(256) conv_dw_tile_kernel(const float* x, const float* dz, float* partial, int B, int D,
-                                                           int cin_total, int with_bias, DwBatch batch = DwBatch{}) {
-  static_assert(STRIDE == 1 || (STRIDE == 2 && KS == 3), "stride 2 is implemented for 3x3x3 (front padding 0)");
+// 1x1x1 layers with more than 64 (ci, co) pairs per chunk (conv2_1 / conv2_3 of the C = 32 and C = 64 blocks), LDS-tiled on
+// the VALU: a workgroup stages 4 x 4 x 16-voxel tiles of x and dz and every thread keeps a 4 x 4 register block of dW.
+// There are T = (CIN / 4) * (COUT / 4) <= 32 such blocks per channel chunk, so S = 256 / T threads share one and split the
+// voxels of each tile; their sums are added in a fixed order through LDS.  (conv_dw_1x1_kernel keeps all CIN x COUT sums of
+// a thread in registers and takes the layers with at most 64 pairs.)
+template <int CIN, int COUT>
+__global__ void __launch_bounds__(256) conv_dw_tile1_kernel(const float* x, const float* dz, float* partial, int B, int D,
+                                                            int cin_total, int with_bias, DwBatch batch) {
   if (batch.n) { x = batch.x[blockIdx.z]; dz = batch.dz[blockIdx.z]; partial = batch.partial[blockIdx.z]; }
-  constexpr int TD = STRIDE == 1 ? 4 : 2, TH = TD, TW = 16, PAD = STRIDE == 1 ? (KS - 1) / 2 : 0;
-  constexpr int ID = STRIDE * (TD - 1) + KS, IH = STRIDE * (TH - 1) + KS, IW = STRIDE * (TW - 1) + KS;
-  constexpr int TVOX = TD * TH * TW;
-  constexpr int TAPS = KS * KS * KS;
-  constexpr int TI = CIN < 4 ? CIN : 4, TJ = COUT < 4 ? COUT : 4;
-  constexpr int NIB = CIN / TI, NJB = COUT / TJ;
-  constexpr int T = TAPS * NIB * NJB;
-  constexpr int PASSES = (T + 255) / 256;
-  constexpr int S = T >= 256 ? 1 : 256 / T;
+  constexpr int TD = 4, TH = 4, TW = 16, TVOX = TD * TH * TW;
+  constexpr int NIB = CIN / 4, NJB = COUT / 4;
+  constexpr int T = NIB * NJB;
+  constexpr int S = 256 / T;
+  static_assert(CIN % 4 == 0 && COUT % 4 == 0 && 256 % T == 0 && S > 1, "shape");
   constexpr int XVS = CIN == 16 ? 20 : (CIN == 8 ? 12 : CIN);
   constexpr int ZVS = COUT;
-  __shared__ __attribute__((aligned(16))) float xt[ID * IH * IW * XVS];
+  __shared__ __attribute__((aligned(16))) float xt[TVOX * XVS];
   __shared__ __attribute__((aligned(16))) float zt[TVOX * ZVS];
   __shared__ float red[256];
 
@@ -61,33 +71,20 @@ __global__ void __launch_bounds__(256) conv_dw_tile_kernel(const float* x, const
   const int tw = D / TW, th = D / TH, td = D / TD;
   const int ntiles = B * td * th * tw;
 
-  // this thread's dW blocks
-  int xbase[PASSES], zbase[PASSES];
-  bool live[PASSES];
-  const int split = S > 1 ? threadIdx.x / T : 0;
-  const int t0 = S > 1 ? threadIdx.x - split * T : threadIdx.x;
-#pragma unroll
-  for (int p = 0; p < PASSES; ++p) {
-    const int tt = t0 + 256 * p;
-    live[p] = tt < T && split < S;
-    const int jb = tt % NJB, ib = (tt / NJB) % NIB, tap = tt / (NJB * NIB);
-    const int kw = tap % KS, kh = (tap / KS) % KS, kd = tap / (KS * KS);
-    xbase[p] = live[p] ? ((kd * IH + kh) * IW + kw) * XVS + ib * TI : 0;
-    zbase[p] = live[p] ? jb * TJ : 0;
-  }
+  // this thread's dW block and its share of a tile's voxels
+  const int split = threadIdx.x / T, t0 = threadIdx.x - split * T;
+  const int jb = t0 % NJB, ib = t0 / NJB;
   // bias gradient db[co] = sum of dz over voxels, from the dz tile that is in LDS anyway (channel chunk 0 only):
   // thread t owns channel t % COUT and every (256 / COUT)-th voxel of each tile
   constexpr int BL = 256 / COUT;
   const bool do_bias = with_bias && blockIdx.y == 0;
   const int bc = threadIdx.x % COUT, bl = threadIdx.x / COUT;
   float bsum = 0.f;
-  float acc[PASSES][TI][TJ];
+  float acc[4][4];
 #pragma unroll
-  for (int p = 0; p < PASSES; ++p)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) acc[p][i][j] = 0.f;
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     int bid = tile;
@@ -95,28 +92,11 @@ __global__ void __launch_bounds__(256) conv_dw_tile_kernel(const float* x, const
     const int ty = bid % th; bid /= th;
     const int tx = bid % td; bid /= td;
     const int b = bid, od0 = tx * TD, oh0 = ty * TH, ow0 = tz * TW;
-    const int DX = STRIDE * D;                           // grid of the first operand
-    const float* xb = x + (int64_t)b * DX * DX * DX * cin_total + chunk * CIN;
+    const float* xb = x + (int64_t)b * D * D * D * cin_total + chunk * CIN;
     const float* zb = dz + (int64_t)b * D * D * D * COUT;
     __syncthreads();
-    if constexpr (CIN >= 4) {
-      stage_tile<ID, IH, IW, CIN / 4, XVS>(xt, xb, DX, cin_total, STRIDE * od0 - PAD, STRIDE * oh0 - PAD, STRIDE * ow0 - PAD);
-    } else {
-      for (int v = threadIdx.x; v < ID * IH * IW; v += 256) {
-        const int zw = v % IW, zh = (v / IW) % IH, zd = v / (IW * IH);
-        const int gd = STRIDE * od0 - PAD + zd, gh = STRIDE * oh0 - PAD + zh, gw = STRIDE * ow0 - PAD + zw;
-        float val = 0.f;
-        if ((unsigned)gd < (unsigned)DX && (unsigned)gh < (unsigned)DX && (unsigned)gw < (unsigned)DX)
-          val = xb[(((int64_t)gd * DX + gh) * DX + gw) * cin_total];
-        xt[v] = val;
-      }
-    }
-    if constexpr (COUT >= 4) {
-      stage_tile<TD, TH, TW, COUT / 4, ZVS>(zt, zb, D, COUT, od0, oh0, ow0);
-    } else {
-      const int v = threadIdx.x, w = v & 15, h = (v >> 4) % TH, d = v / (16 * TH);
-      if (v < TVOX) zt[v] = zb[((int64_t)(od0 + d) * D + oh0 + h) * D + ow0 + w];
-    }
+    stage_tile<TD, TH, TW, CIN / 4, XVS>(xt, xb, D, cin_total, od0, oh0, ow0);
+    stage_tile<TD, TH, TW, COUT / 4, ZVS>(zt, zb, D, COUT, od0, oh0, ow0);
     __syncthreads();
     if (do_bias) {
 #pragma unroll 4
@@ -125,35 +105,18 @@ __global__ void __launch_bounds__(256) conv_dw_tile_kernel(const float* x, const
 
 #pragma unroll 2
     for (int v = split; v < TVOX; v += S) {
-      const int w = v & 15, h = (v >> 4) % TH, d = v / (16 * TH);
-      const int xo = ((STRIDE * d * IH + STRIDE * h) * IW + STRIDE * w) * XVS, zo = v * ZVS;
+      const float4 xq = *reinterpret_cast<const float4*>(&xt[v * XVS + ib * 4]);
+      const float4 zq = *reinterpret_cast<const float4*>(&zt[v * ZVS + jb * 4]);
+      const float xv[4] = {xq.x, xq.y, xq.z, xq.w}, zv[4] = {zq.x, zq.y, zq.z, zq.w};
 #pragma unroll
-      for (int p = 0; p < PASSES; ++p) {
-        float xv[TI], zv[TJ];
-        if constexpr (TI == 4) {
-          const float4 q = *reinterpret_cast<const float4*>(&xt[xo + xbase[p]]);
-          xv[0] = q.x; xv[1] = q.y; xv[2] = q.z; xv[3] = q.w;
-        } else {
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int i = 0; i < TI; ++i) xv[i] = xt[xo + xbase[p] + i];
-        }
-        if constexpr (TJ == 4) {
-          const float4 q = *reinterpret_cast<const float4*>(&zt[zo + zbase[p]]);
-          zv[0] = q.x; zv[1] = q.y; zv[2] = q.z; zv[3] = q.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < TJ; ++j) zv[j] = zt[zo + zbase[p] + j];
-        }
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int j = 0; j < TJ; ++j) acc[p][i][j] = fmaf(xv[i], zv[j], acc[p][i][j]);
-      }
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(xv[i], zv[j], acc[i][j]);
     }
   }
 
-  // partial[group][tap][ci][co] (+ [co] bias sums behind the weights when with_bias)
-  const size_t wn = (size_t)TAPS * cin_total * COUT;
+  // partial[group][ci][co] (+ [co] bias sums behind the weights when with_bias)
+  const size_t wn = (size_t)cin_total * COUT;
   float* out = partial + (size_t)blockIdx.x * (wn + (with_bias ? COUT : 0));
   if (do_bias) {                          // fixed-order sum over the BL voxel lanes of each channel
     __syncthreads();
@@ -166,30 +129,23 @@ __global__ void __launch_bounds__(256) conv_dw_tile_kernel(const float* x, const
     }
   }
 #pragma unroll
-  for (int p = 0; p < PASSES; ++p) {
-    const int tt = t0 + 256 * p;
-    const int jb = tt % NJB, ib = (tt / NJB) % NIB, tap = tt / (NJB * NIB);
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        float s = acc[p][i][j];
-        if constexpr (S > 1) {            // fixed-order sum over the S voxel splits
-          __syncthreads();
-          red[threadIdx.x] = s;
-          __syncthreads();
-          s = 0.f;
-          if (split == 0)
-            for (int l = 0; l < S; ++l) s += red[l * T + t0];
-        }
-        if (tt < T && split == 0) out[((size_t)tap * cin_total + chunk * CIN + ib * TI + i) * COUT + jb * TJ + j] = s;
+    for (int j = 0; j < 4; ++j) {         // fixed-order sum over the S voxel splits
+      __syncthreads();
+      red[threadIdx.x] = acc[i][j];
+      __syncthreads();
+      if (split == 0) {
+        float s = 0.f;
+        for (int l = 0; l < S; ++l) s += red[l * T + t0];
+        out[((size_t)chunk * CIN + ib * 4 + i) * COUT + jb * 4 + j] = s;
       }
-  }
+    }
 }
 
 // Stride-1 3x3x3, small channel counts: "sliding kw" variant.  A thread owns the three kw taps of one (kd, kh) for a
 // 4 x 4 (ci x co) block and walks WSEG consecutive voxels of a row, keeping the three x quads of the kw window in
-// registers: per voxel ONE new x quad and one dz quad are read from LDS for 48 FMAs (the kernel above reads two quads
+// registers: per voxel ONE new x quad and one dz quad are read from LDS for 48 FMAs (a thread that owns one tap reads two quads
 // per 16 FMAs and is LDS-bandwidth bound at about a quarter of the FMA rate).  T = 9 * (CIN/4) * (COUT/4) blocks,
 // S = 256 / T threads per block splitting the tile's 256 / WSEG row segments; partial sums are combined in a fixed order.
 template <int CIN, int COUT, int WSEG>
@@ -313,7 +269,7 @@ __global__ void __launch_bounds__(256) conv_dw_slide_kernel(const float* x, cons
 // = up to 28 accumulator quads; per four voxels it reads one B word per column block and one A word per tap from LDS.
 // Summation order per weight: tiles in the workgroup's fixed strided order, voxel groups ascending, the four voxels of
 // a group inside the instruction — bit-reproducible for a given (shape, grid), as above.  Same partial layout and bias sums
-// as conv_dw_tile_kernel<16, COUT, 3, STRIDE> (VALU: 16 x 16 34 us, 16 x 32 41 us, 16 x 64 64 us per launch at 16^3 / 32^3).
+// as every kernel here (an LDS-tiled VALU kernel took: 16 x 16 34 us, 16 x 32 41 us, 16 x 64 64 us per launch at 16^3 / 32^3).
 // CIN = 8 (conv1_2 / conv2_2 of the C = 32 blocks at 32^3): the 16 rows carry TWO taps — row i reads channel i % 8 of tap
 // 2 p + i / 8 — so 14 instructions cover the 27 taps (the last one half idle); COUT = 8 leaves half of the columns idle.
 // Float offset of channel quad q of voxel (d, h, w) in one cube of a [D^3] tensor with C channels: NDHWC, or — q4 — the Q4
@@ -436,7 +392,7 @@ __global__ void __launch_bounds__(256) conv_dw_mfma_kernel(const float* x, const
 //   D(kd, kh)[ci][kw * 4 + co] += sum over the 4 voxels v' of a group  x[v' + (kd - 1, kh - 1, 0)][ci] * dz[v' - (0, 0, kw - 1)][co]
 // 12 of 16 columns carry weights (75 % of the MFMA), one B read serves all nine (kd, kh) accumulators, x needs no w halo.
 // The four waves split the tile by depth slice (balanced: 9 accumulators do not divide by 4) and add their sums in wave
-// order through LDS after the last tile.  Same partial layout / bias sums as conv_dw_slide_kernel<16, 4, 8> (138 us per
+// order through LDS after the last tile.  Same partial layout / bias sums as conv_dw_slide_kernel (whose 16 -> 4 form took 138 us per
 // 8 cubes of 64^3).
 // PAIR: the 1x1x1 layer that reads the same input (conv2_1 next to conv1_1: x = the block input, dz1 = its own output
 // gradient) rides along — its weight gradient is one more accumulator fed by the centre row of the x tile already in LDS
@@ -626,7 +582,7 @@ __global__ void __launch_bounds__(256) conv_dw_mfma_16xn_kernel(const float* x, 
 // along w (as above), one accumulator per kd:
 //   D(kd)[kh * 4 + ci][kw * COUT + co] += sum over the 4 voxels v' of a group  x[v' + (kd - 1, kh - 1, 0)][ci] * dz[v' - (0, 0, kw - 1)][co]
 // 12 of 16 rows and 12 of 16 (COUT = 4) or 24 of 32 (COUT = 8, two column blocks) columns are weights: 56 % of the MFMA, but
-// 3 or 6 instructions per four voxels where the VALU kernels (conv_dw_slide_kernel<4, 4, 4> 79 us, <4, 8, 4> 90 us per 8 cubes,
+// 3 or 6 instructions per four voxels where the VALU kernels (conv_dw_slide_kernel<4, 4, 4> 79 us, <4, 8, 4> 90 us per 8 cubes of 64^3,
 // 23 and 40 TFLOP/s: bound by LDS reads) issue 108 / 216 FMAs per voxel.  Tiles are whole rows (4 x 4 x 64 voxels) so that a
 // tile carries enough MFMAs (192 / 384 per wave) to cover the register-double-buffered staging of the next one; a wave owns
 // one depth slice, the four waves' sums are added in wave order at the end.  x rows are 264 floats apart in LDS (the three kh
@@ -762,7 +718,7 @@ __global__ void __launch_bounds__(256) conv_dw_mfma_4xn_kernel(const float* x, c
 // shifted by tap - 1 (x tile with a halo), columns = co.  27 of 32 rows / columns carry weights, two instructions per four
 // voxels; a wave owns one depth slice of the 4 x 4 x 16 tile, the four waves' sums are added in wave order at the end.
 // Both kernels read their 16-channel operand once (134 MB per 8 cubes of 64^3) and run at the memory rate; the VALU tile
-// kernels they replace (conv_dw_tile_kernel<16, 1, 3> / <1, 16, 3>) took 162 / 154 us per 8 cubes.
+// kernel with one tap per thread took 162 / 154 us per 8 cubes.
 template <int MODE>
 __global__ void __launch_bounds__(256) conv_dw_mfma_edge_kernel(const float* x, const float* dz, float* partial, int B, int D,
                                                                 int with_bias, int wide_q4 = 0) {
@@ -867,104 +823,11 @@ __global__ void __launch_bounds__(256) conv_dw_mfma_edge_kernel(const float* x, 
   }
 }
 
-template <int COUT, int STRIDE, int CIN = 16>
-static int run_dw_mfma(const float* x, const float* dz, float* partial, int B, int D, int Cin, int groups, int with_bias,
-                       hipStream_t s, int x_q4 = 0) {
-  if (t_dw_capture && STRIDE == 1 && CIN == 16 && !x_q4) {
-    t_dw_capture->push_back(DwCall{COUT == 16 ? 0 : (COUT == 32 ? 1 : 2), x, dz, partial, B, D, Cin, groups, with_bias});
-    return 1;
-  }
-  hipLaunchKernelGGL((conv_dw_mfma_kernel<COUT, STRIDE, CIN>), dim3(groups, Cin / CIN), dim3(256), 0, s, x, dz, partial, B, D, Cin,
-                     with_bias, x_q4);
-  int rc = launch_ok("conv_dw_mfma_kernel");
-  return rc ? rc : 1;
-}
-static bool dw_mfma_enabled() {
-  static const bool on = !(getenv("PCGC_DW_MFMA") && atoi(getenv("PCGC_DW_MFMA")) == 0);          // experiment knob
-  return on;
-}
-
-static bool dw_edge_enabled() {
-  static const bool on = !(getenv("PCGC_DW_EDGE") && atoi(getenv("PCGC_DW_EDGE")) == 0);          // experiment knob: 1 <-> 16 channels
-  return on;
-}
-static bool dw_mfma32_enabled() {
-  static const bool on = !(getenv("PCGC_DW_MFMA32") && atoi(getenv("PCGC_DW_MFMA32")) == 0);      // experiment knob: 16 -> 8, 8 -> 16 / 8
-  return on;
-}
-
-template <int CIN, int COUT, int WSEG>
-static int run_dw_slide(const float* x, const float* dz, float* partial, int B, int D, int Cin, int groups, int with_bias,
-                        hipStream_t s) {
-  hipLaunchKernelGGL((conv_dw_slide_kernel<CIN, COUT, WSEG>), dim3(groups, Cin / CIN), dim3(256), 0, s, x, dz, partial, B, D, Cin,
-                     with_bias);
-  int rc = launch_ok("conv_dw_slide_kernel");
-  return rc ? rc : 1;
-}
-
-template <int CIN, int COUT, int KS>
-static int run_dw(const float* x, const float* dz, float* partial, int B, int D, int Cin, int groups, int with_bias,
-                  hipStream_t s) {
-  if (t_dw_capture && KS == 1 && CIN == 16 && (COUT == 16 || COUT == 32)) {
-    t_dw_capture->push_back(DwCall{COUT == 16 ? 3 : 4, x, dz, partial, B, D, Cin, groups, with_bias});
-    return 1;
-  }
-  hipLaunchKernelGGL((conv_dw_tile_kernel<CIN, COUT, KS>), dim3(groups, Cin / CIN), dim3(256), 0, s, x, dz, partial, B, D, Cin,
-                     with_bias);
-  int rc = launch_ok("conv_dw_tile_kernel");
-  return rc ? rc : 1;
-}
-
-// Tiles per workgroup of a launch with fewer tiles than 2 x kDwGroups (PCGC_DW_TPG / PCGC_DW_TPG_S2: experiment knobs).  Every
-// workgroup writes a partial sum of the WHOLE filter gradient, which the final reduction reads again: for down_2 / up_1 (27 x 32 x 64
-// weights) on a batch of 8 cubes that is 512 tiles of 2 x 2 x 16 coarse voxels -> 113 MB written and read per layer with one tile
-// per workgroup.  Two tiles each: the step 8.54 -> 8.47 ms (four: the same; the stride-1 layers of the 16^3 stage, 128 tiles:
-// 8.53 with two, 8.63 with four — left at one; 256 instead of 512 workgroups for the 1 024 tiles of the 32^3 stage: 8.36 against 8.34).
-static int dw_tiles_per_group(const char* name, int dflt) {
-  const char* e = getenv(name);
-  const int d = e ? atoi(e) : dflt;
-  return d < 1 ? 1 : d;
-}
-int conv_dw_tile_groups(int B, int D) {
-  static const int div = dw_tiles_per_group("PCGC_DW_TPG", 1);
-  const int ntiles = (B * (D / 4) * (D / 4) * (D / 16) + div - 1) / div;
-  return ntiles < kDwGroups ? ntiles : kDwGroups;
-}
-int conv_dw_tile_groups_s2(int B, int D) {          // D = coarse grid; tiles of 2 x 2 x 16
-  static const int div = dw_tiles_per_group("PCGC_DW_TPG_S2", 2);
-  const int ntiles = (B * (D / 2) * (D / 2) * (D / 16) + div - 1) / div;
-  return ntiles < kDwGroups ? ntiles : kDwGroups;
-}
-
-// Stride-2 pair, 3x3x3.  fine = operand on the 2D grid with Ca channels, coarse = operand on the D grid with Cb
-// channels; partial = [groups][27][Ca][Cb] (+ Cb sums of `coarse` when with_bias).  Returns 1 / 0 / <0 as below.
-int launch_conv_dw_tile_s2(const float* fine, const float* coarse, float* partial, int B, int D, int Ca, int Cb, int with_bias,
-                           hipStream_t s, int fine_q4) {
-  if (D % 16) return 0;
-  const int g = conv_dw_tile_groups_s2(B, D);
-  if (dw_mfma_enabled() && Ca % 16 == 0) {
-    if (Cb == 16) return run_dw_mfma<16, 2>(fine, coarse, partial, B, D, Ca, g, with_bias, s, fine_q4);
-    if (Cb == 32) return run_dw_mfma<32, 2>(fine, coarse, partial, B, D, Ca, g, with_bias, s, fine_q4);
-    if (Cb == 64) return run_dw_mfma<64, 2>(fine, coarse, partial, B, D, Ca, g, with_bias, s, fine_q4);
-  }
-  if (fine_q4) { set_error("weight gradient of a stride-2 layer: no kernel reads a Q4 operand for Ca=%d Cb=%d", Ca, Cb); return -1; }
-#define TRY2(cb)                                                                                                     \
-  if (Ca % 16 == 0 && Cb == cb) {                                                                                    \
-    hipLaunchKernelGGL((conv_dw_tile_kernel<16, cb, 3, 2>), dim3(g, Ca / 16), dim3(256), 0, s, fine, coarse, partial, B, D, Ca, \
-                       with_bias);                                                                                   \
-    int rc = launch_ok("conv_dw_tile_kernel (stride 2)");                                                           \
-    return rc ? rc : 1;                                                                                              \
-  }
-  TRY2(16) TRY2(32) TRY2(64)
-#undef TRY2
-  return 0;
-}
-
 // 1^3 layers with at most 64 (ci, co) pairs (conv2_1 16 -> 4 and conv2_3 4 -> 8 of the C = 16 blocks): the weight gradient
 // is one outer product per voxel summed over the voxels, i.e. a reduction that reads x and dz exactly once.  A thread walks
 // voxels tid, tid + stride, ... with the CIN x COUT sums in registers; then the 64 lanes of a wave are added by a
-// butterfly, the 4 waves through LDS in wave order: fixed order, partial = [groups][CIN*COUT (+ COUT bias sums)] like the
-// tile kernel (which staged 4 x 4 x 16-voxel tiles through LDS for these layers: 55 / 49 us per 8 cubes of 64^3).
+// butterfly, the 4 waves through LDS in wave order: fixed order, partial = [groups][CIN*COUT (+ COUT bias sums)] like
+// conv_dw_tile1_kernel (which stages 4 x 4 x 16-voxel tiles through LDS and took 55 / 49 us per 8 cubes of 64^3 for these layers).
 template <int CIN, int COUT>
 __global__ void __launch_bounds__(256) conv_dw_1x1_kernel(const float* x, const float* dz, float* partial, int64_t nvox, int with_bias,
                                                           int dz_q4_w = 0) {      // dz_q4_w = W of a Q4 dz tensor ([row][COUT / 4][w][4]), 0: NDHWC
@@ -984,7 +847,7 @@ __global__ void __launch_bounds__(256) conv_dw_1x1_kernel(const float* x, const 
   // kernel at 3.5 TB/s: 16 dependent iterations of ~2 us)
   constexpr int U = 4;                       // (8 for the 4 x 8 layer: 34 against 33 us per 8 cubes — the launch is at its floor of fixed cost + bytes)
   const int64_t step = (int64_t)gridDim.x * 256;
-  // Q4 dz: W divides 256 (launch_conv_dw_tile checks), so a thread keeps its w and its row advances by step / W per voxel —
+  // Q4 dz: W divides 256 (dw_choose checks), so a thread keeps its w and its row advances by step / W per voxel —
   // no 64-bit division per voxel
   const int64_t v_first = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int qw = dz_q4_w ? (int)(v_first % dz_q4_w) : 0;
@@ -1041,104 +904,97 @@ __global__ void __launch_bounds__(256) conv_dw_1x1_kernel(const float* x, const 
   if ((int)threadIdx.x < total) out[threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
 }
 
-// stride-1 convs (3x3x3 and 1x1x1).  Returns 1 launched (partial = [groups][taps*Cin*Cout (+ Cout bias sums)]),
-// 0 unsupported shape, <0 error.
+// One call's operands.  dz1 / partial1: the 1x1x1 layer of the pair kernels; x_q4 / dz_q4: that operand is a Q4 tensor.
+struct DwOperands {
+  const float *x, *dz;
+  float* partial;
+  int B, D, Cin, with_bias;
+  int x_q4 = 0, dz_q4 = 0;
+  const float* dz1 = nullptr;
+  float* partial1 = nullptr;
+};
+
+// The one place that names the instantiations: enum value -> launch.  grid = (groups, chunks[, jobs of `batch`]).
+static int launch_dw(DwKernel k, dim3 grid, const DwOperands& a, const DwBatch& batch, hipStream_t s) {
+  const dim3 block(256);
+  auto tile1 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, a.B, a.D, a.Cin, a.with_bias, batch); };
+  auto mfma = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, a.B, a.D, a.Cin, a.with_bias, a.x_q4, batch); };
+  auto slide = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, a.B, a.D, a.Cin, a.with_bias); };
+  auto mfma16 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, a.B, a.D, a.Cin, a.with_bias, a.dz1, a.partial1, a.x_q4); };
+  // (a workgroup of the whole-row kernel beyond its B * 16 * 16 tiles writes a partial of zeros)
+  auto mfma4 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, a.B, a.D, a.with_bias, a.dz_q4); };
+  auto edge = [&](auto kernel, int wide_q4) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, a.B, a.D, a.with_bias, wide_q4); };
+  auto one = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, a.x, a.dz, a.partial, (int64_t)a.B * a.D * a.D * a.D, a.with_bias, a.dz_q4 ? a.D : 0);
+  };
+  switch (k) {
+    case DwKernel::kOne_16x4: one(conv_dw_1x1_kernel<16, 4>); break;
+    case DwKernel::kOne_4x8: one(conv_dw_1x1_kernel<4, 8>); break;
+    case DwKernel::kMfma4_4: mfma4(conv_dw_mfma_4xn_kernel<4>); break;
+    case DwKernel::kMfma4_8: mfma4(conv_dw_mfma_4xn_kernel<8>); break;
+    case DwKernel::kMfma16_4: mfma16(conv_dw_mfma_16xn_kernel<4, false>); break;
+    case DwKernel::kMfma16_8: mfma16(conv_dw_mfma_16xn_kernel<8, false>); break;
+    case DwKernel::kMfma16Pair_4: mfma16(conv_dw_mfma_16xn_kernel<4, true>); break;
+    case DwKernel::kMfma16Pair_8: mfma16(conv_dw_mfma_16xn_kernel<8, true>); break;
+    case DwKernel::kMfma_8x16: mfma(conv_dw_mfma_kernel<16, 1, 8>); break;
+    case DwKernel::kMfma_16x16: mfma(conv_dw_mfma_kernel<16, 1, 16>); break;
+    case DwKernel::kMfma_16x32: mfma(conv_dw_mfma_kernel<32, 1, 16>); break;
+    case DwKernel::kMfma_16x64: mfma(conv_dw_mfma_kernel<64, 1, 16>); break;
+    case DwKernel::kMfmaS2_16x16: mfma(conv_dw_mfma_kernel<16, 2, 16>); break;
+    case DwKernel::kMfmaS2_16x32: mfma(conv_dw_mfma_kernel<32, 2, 16>); break;
+    case DwKernel::kMfmaS2_16x64: mfma(conv_dw_mfma_kernel<64, 2, 16>); break;
+    case DwKernel::kSlide_4x4: slide(conv_dw_slide_kernel<4, 4, 4>); break;
+    case DwKernel::kSlide_4x8: slide(conv_dw_slide_kernel<4, 8, 4>); break;
+    case DwKernel::kSlide_8x8: slide(conv_dw_slide_kernel<8, 8, 8>); break;
+    case DwKernel::kEdge_16x1: edge(conv_dw_mfma_edge_kernel<0>, a.x_q4); break;
+    case DwKernel::kEdge_1x16: edge(conv_dw_mfma_edge_kernel<1>, a.dz_q4); break;
+    case DwKernel::kTile1_16x8: tile1(conv_dw_tile1_kernel<16, 8>); break;
+    case DwKernel::kTile1_8x16: tile1(conv_dw_tile1_kernel<8, 16>); break;
+    case DwKernel::kTile1_16x16: tile1(conv_dw_tile1_kernel<16, 16>); break;
+    case DwKernel::kTile1_16x32: tile1(conv_dw_tile1_kernel<16, 32>); break;
+    case DwKernel::kGeneric:
+    case DwKernel::kCount: set_error("launch_dw: no tiled kernel to launch"); return -1;
+  }
+  const int rc = launch_ok(dw_kernel_name(k));
+  return rc ? rc : 1;
+}
+
+// Choose, then launch.  1 launched (or recorded), 0 no tiled kernel for this shape, < 0 error.
+static int run_dw_choice(const DwChoice& c, const DwOperands& a, int Cout, int ksize, int stride, hipStream_t s) {
+  if (c.refused) {
+    set_error("weight gradient: no kernel reads Q4 operands for Cin=%d Cout=%d k=%d stride=%d D=%d (x_q4=%d dz_q4=%d; the Q4 dz of a 1x1x1 layer "
+              "needs D dividing 256)", a.Cin, Cout, ksize, stride, a.D, a.x_q4, a.dz_q4);
+    return -1;
+  }
+  if (c.kernel == DwKernel::kGeneric) return 0;
+  if (t_dw_capture && c.batchable) {
+    t_dw_capture->push_back(DwCall{c.kernel, a.x, a.dz, a.partial, a.B, a.D, a.Cin, c.groups, c.chunks, a.with_bias});
+    return 1;
+  }
+  return launch_dw(c.kernel, dim3(c.groups, c.chunks), a, DwBatch{}, s);
+}
+
+// stride-1 convs (3x3x3 and 1x1x1): partial = [groups][taps*Cin*Cout (+ Cout bias sums)]
 int launch_conv_dw_tile(const float* x, const float* dz, float* partial, int B, int D, int Cin, int Cout, int ksize,
                         int with_bias, hipStream_t s, int x_q4, int dz_q4) {
-  if (D % 16) return 0;
-  const int g = conv_dw_tile_groups(B, D);
-  if (x_q4 || dz_q4) {
-    // Q4 operands (the training step's 64^3 stage): exactly the kernels of that stage read them — 1 <-> 16 channels (edge),
-    // 4 -> 8 (3^3 and 1^3: dz has 8 channels; x, 4 channels, is the same in both layouts); 16 -> 4 goes through
-    // launch_conv_dw_pair.  Anything else would silently read the wrong voxels: refused.
-    if (dw_mfma_enabled() && dw_edge_enabled() && ksize == 3 && Cin == 16 && Cout == 1 && x_q4) {
-      hipLaunchKernelGGL(conv_dw_mfma_edge_kernel<0>, dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias, 1);
-    } else if (dw_mfma_enabled() && dw_edge_enabled() && ksize == 3 && Cin == 1 && Cout == 16 && dz_q4) {
-      hipLaunchKernelGGL(conv_dw_mfma_edge_kernel<1>, dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias, 1);
-    } else if (dw_mfma_enabled() && ksize == 3 && Cin == 4 && Cout == 8 && D == 64 && dz_q4 && !x_q4) {
-      hipLaunchKernelGGL((conv_dw_mfma_4xn_kernel<8>), dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias, 1);
-    } else if (ksize == 1 && Cin == 4 && Cout == 8 && dz_q4 && !x_q4) {
-      if (256 % D) { set_error("weight gradient of a 1x1x1 layer on a Q4 operand: D=%d must divide 256", D); return -1; }
-      hipLaunchKernelGGL((conv_dw_1x1_kernel<4, 8>), dim3(g), dim3(256), 0, s, x, dz, partial, (int64_t)B * D * D * D, with_bias, D);
-    } else {
-      set_error("weight gradient: no kernel reads Q4 operands for Cin=%d Cout=%d k=%d D=%d (x_q4=%d dz_q4=%d)", Cin, Cout, ksize, D, x_q4, dz_q4);
-      return -1;
-    }
-    const int rc = launch_ok("conv_dw kernel (Q4 operand)");
-    return rc ? rc : 1;
-  }
-#define TRY(ck, co, ks)                                                                           \
-  if (ksize == ks && ((Cin >= 16 && ck == 16) || Cin == ck) && Cin % ck == 0 && Cout == co)      \
-    return run_dw<ck, co, ks>(x, dz, partial, B, D, Cin, g, with_bias, s);
-  static const bool dw1 = !(getenv("PCGC_DW_1X1") && atoi(getenv("PCGC_DW_1X1")) == 0);           // experiment knob
-  if (dw1 && ksize == 1 && ((Cin == 16 && Cout == 4) || (Cin == 4 && Cout == 8))) {
-    const int64_t nvox = (int64_t)B * D * D * D;
-    if (Cin == 16) hipLaunchKernelGGL((conv_dw_1x1_kernel<16, 4>), dim3(g), dim3(256), 0, s, x, dz, partial, nvox, with_bias);
-    else hipLaunchKernelGGL((conv_dw_1x1_kernel<4, 8>), dim3(g), dim3(256), 0, s, x, dz, partial, nvox, with_bias);
-    const int rc = launch_ok("conv_dw_1x1_kernel");
-    return rc ? rc : 1;
-  }
-  static const bool slide = !(getenv("PCGC_DW_SLIDE") && atoi(getenv("PCGC_DW_SLIDE")) == 0);     // experiment knob
-#define SLIDE(ck, co, wseg)                                                                       \
-  if (slide && ksize == 3 && ((Cin >= 16 && ck == 16) || Cin == ck) && Cin % ck == 0 && Cout == co) \
-    return run_dw_slide<ck, co, wseg>(x, dz, partial, B, D, Cin, g, with_bias, s);
-  if (dw_mfma_enabled() && ksize == 3 && Cin == 4 && (Cout == 4 || Cout == 8) && D == 64) {
-    // g workgroups (what the caller sized `partial` for) over B * 16 * 16 tiles of 4 x 4 x 64 voxels; a workgroup without a
-    // tile writes a partial of zeros
-    if (Cout == 4) hipLaunchKernelGGL((conv_dw_mfma_4xn_kernel<4>), dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias);
-    else hipLaunchKernelGGL((conv_dw_mfma_4xn_kernel<8>), dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias);
-    const int rc = launch_ok("conv_dw_mfma_4xn_kernel");
-    return rc ? rc : 1;
-  }
-  if (dw_mfma_enabled() && ksize == 3 && Cin % 16 == 0 && (Cout == 4 || (Cout == 8 && dw_mfma32_enabled()))) {
-    if (Cout == 4) hipLaunchKernelGGL(conv_dw_mfma_16xn_kernel<4>, dim3(g, Cin / 16), dim3(256), 0, s, x, dz, partial, B, D, Cin, with_bias);
-    else hipLaunchKernelGGL(conv_dw_mfma_16xn_kernel<8>, dim3(g, Cin / 16), dim3(256), 0, s, x, dz, partial, B, D, Cin, with_bias);
-    const int rc = launch_ok("conv_dw_mfma_16xn_kernel");
-    return rc ? rc : 1;
-  }
-  if (dw_mfma_enabled() && dw_mfma32_enabled() && ksize == 3 && Cin == 8) {
-    if (Cout == 16) return run_dw_mfma<16, 1, 8>(x, dz, partial, B, D, Cin, g, with_bias, s);
-    // (8 -> 8 with half of the columns idle: 25 us per 8 cubes of 32^3 against 23 us for the sliding VALU kernel — not used)
-  }
-  SLIDE(4, 4, 4) SLIDE(4, 8, 4) SLIDE(8, 4, 4) SLIDE(4, 16, 8) SLIDE(8, 8, 8) SLIDE(16, 4, 8) SLIDE(8, 16, 16) SLIDE(16, 8, 16)
-#undef SLIDE
-  if (dw_mfma_enabled() && ksize == 3 && Cin % 16 == 0) {
-    if (Cout == 16) return run_dw_mfma<16, 1>(x, dz, partial, B, D, Cin, g, with_bias, s);
-    if (Cout == 32) return run_dw_mfma<32, 1>(x, dz, partial, B, D, Cin, g, with_bias, s);
-    if (Cout == 64) return run_dw_mfma<64, 1>(x, dz, partial, B, D, Cin, g, with_bias, s);
-  }
-  if (dw_mfma_enabled() && dw_edge_enabled() && ksize == 3 && ((Cin == 16 && Cout == 1) || (Cin == 1 && Cout == 16))) {
-    if (Cout == 1) hipLaunchKernelGGL(conv_dw_mfma_edge_kernel<0>, dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias);
-    else hipLaunchKernelGGL(conv_dw_mfma_edge_kernel<1>, dim3(g), dim3(256), 0, s, x, dz, partial, B, D, with_bias);
-    const int rc = launch_ok("conv_dw_mfma_edge_kernel");
-    return rc ? rc : 1;
-  }
-  TRY(1, 16, 3) TRY(16, 1, 3)
-  TRY(4, 4, 3) TRY(4, 8, 3) TRY(4, 16, 3)
-  TRY(8, 4, 3) TRY(8, 8, 3) TRY(8, 16, 3) TRY(8, 32, 3)
-  TRY(16, 4, 3) TRY(16, 8, 3) TRY(16, 16, 3) TRY(16, 32, 3) TRY(16, 64, 3)
-  TRY(16, 4, 1) TRY(4, 8, 1) TRY(16, 8, 1) TRY(8, 16, 1) TRY(16, 16, 1) TRY(16, 32, 1)
-#undef TRY
-  return 0;
+  return run_dw_choice(dw_choose(ksize, Cin, Cout, D, B, x_q4, dz_q4), DwOperands{x, dz, partial, B, D, Cin, with_bias, x_q4, dz_q4}, Cout, ksize, 1, s);
+}
+
+// Stride-2 pair, 3x3x3: the first operand lives on the twice finer grid, fine[2o + k] pairs with coarse[o] — the stride-2
+// conv (fine = layer input, coarse = output gradient, result [tap][ci][co]) and, with the operands swapped, the transposed
+// conv (fine = dz, coarse = x, result [tap][co][ci] = the TF layout of its kernel).  partial = [groups][27][Ca][Cb] (+ Cb
+// sums of `coarse` when with_bias).
+int launch_conv_dw_tile_s2(const float* fine, const float* coarse, float* partial, int B, int D, int Ca, int Cb, int with_bias,
+                           hipStream_t s, int fine_q4) {
+  return run_dw_choice(dw_choose_s2(Ca, Cb, D, B, fine_q4), DwOperands{fine, coarse, partial, B, D, Ca, with_bias, fine_q4}, Cb, 3, 2, s);
 }
 
 // conv1_1 (3x3x3, Cin -> Cout) and conv2_1 (1x1x1, Cin -> Cout) of a VRN block read the same input: both weight
-// gradients in one pass over it (conv_dw_mfma_16xn_kernel<COUT, true>).  partial / partial1 as launch_conv_dw_tile would
-// lay them out for the two layers.  Returns 1 launched, 0 unsupported shape (the caller takes the layers one by one).
-bool conv_dw_pair_supported(int D, int Cin, int Cout) {
-  static const bool on = !(getenv("PCGC_DW_PAIR") && atoi(getenv("PCGC_DW_PAIR")) == 0);          // experiment knob
-  return on && dw_mfma_enabled() && D % 16 == 0 && Cin % 16 == 0 && (Cout == 4 || (Cout == 8 && dw_mfma32_enabled()));
-}
+// gradients in one pass over it.  partial3 / partial1 as launch_conv_dw_tile would lay them out for the two layers.
+// 0: unsupported shape (the caller takes the layers one by one).
 int launch_conv_dw_pair(const float* x, const float* dz3, const float* dz1, float* partial3, float* partial1, int B, int D,
                         int Cin, int Cout, int with_bias, hipStream_t s, int x_q4) {
-  if (!conv_dw_pair_supported(D, Cin, Cout)) return 0;
-  const int g = conv_dw_tile_groups(B, D);
-  if (Cout == 4)
-    hipLaunchKernelGGL((conv_dw_mfma_16xn_kernel<4, true>), dim3(g, Cin / 16), dim3(256), 0, s, x, dz3, partial3, B, D, Cin, with_bias, dz1, partial1, x_q4);
-  else
-    hipLaunchKernelGGL((conv_dw_mfma_16xn_kernel<8, true>), dim3(g, Cin / 16), dim3(256), 0, s, x, dz3, partial3, B, D, Cin, with_bias, dz1, partial1, x_q4);
-  const int rc = launch_ok("conv_dw_mfma_16xn_kernel<pair>");
-  return rc ? rc : 1;
+  return run_dw_choice(dw_choose_pair(Cin, Cout, D, B), DwOperands{x, dz3, partial3, B, D, Cin, with_bias, x_q4, 0, dz1, partial1}, Cout, 3, 1, s);
 }
 
 // The recorded calls, equal (kernel, shape) together as the jobs of one launch (at most kDwBatchMax per launch); a job's
@@ -1151,21 +1007,14 @@ int launch_dw_calls(const std::vector<DwCall>& calls, hipStream_t s) {
     DwBatch b;
     for (size_t k = i; k < calls.size() && b.n < kDwBatchMax; ++k) {
       const DwCall& o = calls[k];
-      if (done[k] || o.kind != c.kind || o.B != c.B || o.D != c.D || o.Cin != c.Cin || o.groups != c.groups || o.with_bias != c.with_bias) continue;
+      if (done[k] || o.kernel != c.kernel || o.B != c.B || o.D != c.D || o.Cin != c.Cin || o.groups != c.groups || o.with_bias != c.with_bias) continue;
       b.x[b.n] = o.x; b.dz[b.n] = o.dz; b.partial[b.n] = o.partial; ++b.n;
       done[k] = 1;
     }
-    const dim3 grid(c.groups, c.Cin / 16, b.n);
-    switch (c.kind) {
-      case 0: hipLaunchKernelGGL((conv_dw_mfma_kernel<16, 1, 16>), grid, dim3(256), 0, s, c.x, c.dz, c.partial, c.B, c.D, c.Cin, c.with_bias, 0, b); break;
-      case 1: hipLaunchKernelGGL((conv_dw_mfma_kernel<32, 1, 16>), grid, dim3(256), 0, s, c.x, c.dz, c.partial, c.B, c.D, c.Cin, c.with_bias, 0, b); break;
-      case 2: hipLaunchKernelGGL((conv_dw_mfma_kernel<64, 1, 16>), grid, dim3(256), 0, s, c.x, c.dz, c.partial, c.B, c.D, c.Cin, c.with_bias, 0, b); break;
-      case 3: hipLaunchKernelGGL((conv_dw_tile_kernel<16, 16, 1>), grid, dim3(256), 0, s, c.x, c.dz, c.partial, c.B, c.D, c.Cin, c.with_bias, b); break;
-      case 4: hipLaunchKernelGGL((conv_dw_tile_kernel<16, 32, 1>), grid, dim3(256), 0, s, c.x, c.dz, c.partial, c.B, c.D, c.Cin, c.with_bias, b); break;
-      default: set_error("launch_dw_calls: unknown kind %d", c.kind); return -1;
-    }
+    const int rc = launch_dw(c.kernel, dim3(c.groups, c.chunks, b.n), DwOperands{c.x, c.dz, c.partial, c.B, c.D, c.Cin, c.with_bias}, b, s);
+    if (rc < 0) return rc;
   }
-  return launch_ok("batched weight-gradient kernels");
+  return 0;
 }
 
 }  // namespace pcgc

@@ -293,6 +293,8 @@ _BWD_CASES = [  # (Cin, Cout, k, stride, transposed, D of the layer input): ever
     (64, 32, 3, 2, 1, 16), (32, 16, 3, 2, 1, 16), (16, 16, 3, 2, 1, 16),
     (16, 4, 3, 1, 0, 8), (16, 32, 3, 2, 0, 8), (32, 16, 3, 2, 1, 4),      # small cubes: generic kernel
     (1, 32, 9, 2, 0, 16), (32, 32, 5, 2, 0, 8), (32, 32, 5, 2, 1, 4), (32, 1, 9, 2, 1, 8),      # model_simple.py shapes
+    # shapes of no net at a D the tiled kernels take: the generic kernel (csrc/dw_plan.h has no row for them)
+    (8, 32, 3, 1, 0, 16), (8, 4, 3, 1, 0, 16), (4, 16, 3, 1, 0, 16), (32, 1, 3, 1, 0, 16), (32, 4, 1, 1, 0, 16),
 ]
 
 
