@@ -278,6 +278,40 @@ int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, con
                      int oy, int oz, int res, double* out4, double* best, double* plane, int32_t* n_ties,
                      void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- Rendering (pcgcv1_amd/render.py; DESIGN.md "Rendering"; tests/_render_ref.py is the rule in numpy) ---------------
+ * A cloud to an image: demo.ipynb:586,596,962,972 (o3d.visualization.draw_geometries), on a node without a display.
+ * Orthographic, all integers after one rounding, so an image is defined bit for bit.
+ *   points   float32 [n,3] (device), finite, |x| < 2^15; a point outside that (a NaN included) is dropped
+ *   rotation int32 [9] (HOST), Q14, rows right, up, toward the viewer, entries within [-16384, 16384]
+ *   window   u0, v1, w1 within (-2^31, 2^31); scale S within 1..2^30 = pixels per 1/16 voxel in Q16; |ox|, |oy| <= 2^20
+ *   q   = (int) rintf(p * 16.0f) per coordinate, round half to even (1/16-voxel units)
+ *   t_r = (rotation[3r] q0 + rotation[3r+1] q1 + rotation[3r+2] q2 + 8192) >> 14, r = 0, 1, 2, int64, arithmetic shift
+ *   px  = (((t0 - u0) * S) >> 16) + ox,  py = (((v1 - t1) * S) >> 16) + oy,  d = w1 - t2  (a smaller d is nearer)
+ * A point with d < 0 or d >= 2^31 is dropped.  Every other point i covers the point_size x point_size pixels centred on
+ * (px, py), the part outside the image dropped, with key = (uint64(d) << 32) | i.
+ *   pcgc_render_splat: workspace (uint64 [height, width], 8-byte aligned) = per pixel the smallest key of the points that
+ *     cover it, all ones where none does: one 64-bit atomic min per covered pixel, skipped where the stored key is
+ *     already smaller.  The minimum does not depend on arrival order; equal depths go to the lower index.  Rejects a
+ *     null pointer (points may be NULL when n = 0), width or height outside 1..8192, point_size not odd or outside
+ *     1..15, n outside [0, 2^32 - 1), a workspace smaller than pcgc_render_workspace_bytes (0 for a bad size).
+ *   pcgc_render_resolve: rgb uint8 [height, width, 3]; index int32 [height, width] (the winner, -1 for background) and
+ *     depth int32 [height, width] (its d, -1 for background) may be NULL.  An uncovered pixel takes `background`
+ *     (0xRRGGBB).  A covered pixel with winner i takes c = colors[i] (uint8 [n,3], device), or `foreground` when colors
+ *     is NULL or i >= n, shaded by eye-dome lighting of integer strength `shade` = k within 0..2^20 (0 = off):
+ *       obs = sum over the eight neighbouring pixels inside the image and covered of max(0, d - d_neighbour)
+ *       out = (c * ((255 k) / (k + obs)) + 127) / 255 per channel, integer divisions.
+ *   pcgc_colormap: out[i] (uint8 [n,3]) = lut[min(255, (int) floorf(values[i] * scale))] with values float32 [n], finite
+ *     and >= 0 (a NaN or a negative value takes entry 0), lut uint8 [256,3] (device), scale = float32(256 / vmax).
+ * Deterministic (integer atomic min; everything else one thread per output). */
+size_t pcgc_render_workspace_bytes(int width, int height);
+int pcgc_render_splat(const float* points, int64_t n, const int32_t* rotation, int64_t u0, int64_t v1, int64_t w1, int32_t scale,
+                      int32_t ox, int32_t oy, int width, int height, int point_size, void* workspace, size_t workspace_bytes,
+                      pcgc_stream_t stream);
+int pcgc_render_resolve(const void* workspace, size_t workspace_bytes, int width, int height, const uint8_t* colors, int64_t n,
+                        uint32_t background, uint32_t foreground, int shade, uint8_t* rgb, int32_t* index, int32_t* depth,
+                        pcgc_stream_t stream);
+int pcgc_colormap(const float* values, int64_t n, float scale, const uint8_t* lut, uint8_t* out, pcgc_stream_t stream);
+
 /* Recolouring: the colours of the original cloud S (int32 xyz < res, unique, uint8 rgb per point) carried onto the decoded
  * geometry T, passed like the D2 target as its linear keys (x*res + y)*res + z, int64, SORTED ascending and unique;
  * target_colors uint8 [n_t,3] and backward_counts int32 [n_t] (may be NULL) are in that order.  With N_T(s) = all points

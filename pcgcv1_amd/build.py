@@ -39,6 +39,7 @@ HIP_SOURCES = {
     "pointnums.hip": ["-ffp-contract=off"],
     "color.hip": ["-ffp-contract=off"],
     "offgrid.hip": ["-ffp-contract=off"],
+    "render.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

@@ -58,8 +58,10 @@ def parse_args(argv=None):
                            {"choices": ("range", "rans")} if name == "color_coder" else {}))
     ap.add_argument("--estimate_normals", action="store_true",
                     help="compress --pointnums=d2 with a ply that has no normals: estimate them (radius 10, 20 neighbours, as eval does)")
+    ap.add_argument("--render", default="", metavar="X.png",
+                    help="decompress only: also draw the cloud just written into this png (pcgcv1_amd/render.py, default view and size)")
     args = ap.parse_args(argv)
-    if args.color_target:                                  # with the other argument errors, before anything is loaded
+    if args.color_target:                                 # with the other argument errors, before anything is loaded
         from .colorcodec import parse_target
         try:
             parse_target(args.color_target)
@@ -198,6 +200,27 @@ def _self_launch(argv, n):
 
 def main(argv=None):
     args = parse_args(argv)
+    if not args.render:
+        return _main(args, argv)
+    if args.command != "decompress":
+        raise SystemExit("--render belongs to decompress: it draws the cloud decompress has just written")
+    if args.gpu > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--render runs on one GPU")
+    _main(args, argv)
+    _render_output(args)
+
+
+def _render_output(args):
+    """--render: the ply decompress has just written (args.output), default view and size, in its own colours if it has any"""
+    from .dataprocess.inout_points import load_ply_colors
+    from .render import render, write_png
+    t0 = time.time()
+    points, colors = load_ply_colors(args.output, as_float=True)
+    write_png(args.render, render(points, colors))
+    print("Render {} to {}: {}s ({} points)".format(args.output, args.render, round(time.time() - t0, 4), len(points)))
+
+
+def _main(args, argv):
     if args.gpu < 1:
         raise SystemExit("--gpu=0: this build runs the hot path on an MI355X only (no CPU fallback)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
