@@ -538,6 +538,38 @@ size_t pcgc_normals_workspace_bytes(int res, int64_t n, double radius);
 int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radius, int max_nn, float* normals, int64_t* cov,
                           int32_t* n_neighbours, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- raw scan -> voxel cloud with colours and normals (pcgcv1_amd/ingest.py; tests/_ingest_ref.py is
+ * the rule in numpy) ----
+ * A scan has float coordinates in its own units and any number of points per voxel.  A frame (origin[3], step, bits),
+ * 1 <= bits <= 12, puts it on the grid of res = 2^bits cells per axis, R = res - 1.  All position arithmetic is IEEE
+ * float64, one operation per step in the stated order, without contraction.
+ *   pcgc_ingest_bounds: out[0..2] = per-axis minimum, out[3..5] = per-axis maximum over the rows of points (double
+ *     [n,3], device) whose three coordinates are all finite; *n_dropped (DEVICE int64) = the number of the other rows.
+ *     When every row is dropped out = (+inf x 3, -inf x 3).  out: DEVICE double [6].  n >= 1.
+ *   pcgc_ingest_quantize: q_k = floor((p_k - origin_k) / step + 0.5) as sub, div, add, floor, then clamped to [0, R];
+ *     q int32 [n,3], keys int64 [n] = (q_x * res + q_y) * res + q_z.  A row with a non-finite coordinate gets q = -1,
+ *     -1, -1 and key -1.  origin: HOST double [3], finite; step finite and > 0.
+ *   pcgc_ingest_merge: one row per occupied voxel in ascending key (np.unique's order).  keys int64 [n]: a key outside
+ *     [0, res^3) contributes nothing.  colors uint8 [n,3] or NULL, normals float32 [n,3] or NULL (then the matching
+ *     output may be NULL too).  Per voxel:
+ *       out_points  int32 [cap,3]: the cell of the key;   out_counts int32 [cap]: its number of input rows;
+ *       out_colors  uint8 [cap,3]: (2 sum + count) / (2 count) in integers per channel: the exact mean, half rounded up;
+ *       out_normals float32 [cap,3]: each input component c -> double, non-finite -> 0, clamped to [-1, 1], then the int64
+ *         rint(c * 2^30) (half to even); v = the three int64 sums as double, len = sqrt((vx*vx + vy*vy) + vz*vz); the
+ *         output is float(v / len), or (0, 0, 0) when len == 0.
+ *     Everything summed is an integer (int32 / uint32 / int64 atomics), so no output depends on the order of the rows or
+ *     of the threads.  *n_out (DEVICE int64) = the number of rows; rows at and beyond cap are not written: cap >=
+ *     min(n, res^3) holds them all.  The colour sums are uint32: with colours n <= 16 843 009 (2^32 / 255), which no
+ *     voxel's sum can overflow.  1 <= n < 2^31.  workspace: pcgc_ingest_workspace_bytes(bits, n) (0 for a bad argument),
+ *     a bit set and a rank table over res^3 cells and the accumulators of n voxels. */
+int pcgc_ingest_bounds(const double* points, int64_t n, double* out, int64_t* n_dropped, pcgc_stream_t stream);
+int pcgc_ingest_quantize(const double* points, int64_t n, const double* origin, double step, int bits, int32_t* q,
+                         int64_t* keys, pcgc_stream_t stream);
+size_t pcgc_ingest_workspace_bytes(int bits, int64_t n);
+int pcgc_ingest_merge(const int64_t* keys, int64_t n, int bits, const uint8_t* colors, const float* normals,
+                      int32_t* out_points, int32_t* out_counts, uint8_t* out_colors, float* out_normals, int64_t cap,
+                      int64_t* n_out, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

@@ -68,6 +68,10 @@ HIP_API = {
     "pcgc_normals_table_size": (c_int, [ctypes.c_double]),
     "pcgc_normals_workspace_bytes": (c_sz, [c_int, c_i64, ctypes.c_double]),
     "pcgc_estimate_normals": (c_int, [c_vp, c_i64, c_int, ctypes.c_double, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_ingest_bounds": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pcgc_ingest_quantize": (c_int, [c_vp, c_i64, c_vp, ctypes.c_double, c_int, c_vp, c_vp, c_vp]),
+    "pcgc_ingest_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_ingest_merge": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d1_workspace_bytes": (c_sz, [c_int]),
     "pcgc_d1_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),

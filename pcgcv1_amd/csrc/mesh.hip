@@ -130,30 +130,16 @@ __global__ void __launch_bounds__(256) mesh_quantize_kernel(const double* p, int
 template <bool kCoords>
 __global__ void __launch_bounds__(kScanThreads) bits_compact_kernel(const unsigned* bits, const int64_t* block_offset, int64_t G,
                                                                     int64_t cap, int32_t* coords, int64_t* keys) {
-  unsigned w[kWordsPerThread];
-  const unsigned c = load_words(bits, blockIdx.x, w);
-  unsigned total;
-  int64_t o = block_offset[blockIdx.x] + block_scan(c, &total);
-  if (c == 0) return;
-  const int64_t word0 = (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread;
-  for (int k = 0; k < kWordsPerThread; ++k) {
-    unsigned x = w[k];
-    while (x) {
-      const int b = __ffs(x) - 1;
-      x &= x - 1;
-      const int64_t key = (word0 + k) * 32 + b;
-      if (o < cap) {
-        if (kCoords) {
-          coords[o * 3] = (int32_t)(key / (G * G));
-          coords[o * 3 + 1] = (int32_t)((key / G) % G);
-          coords[o * 3 + 2] = (int32_t)(key % G);
-        } else {
-          keys[o] = key;
-        }
-      }
-      ++o;
+  for_each_set_bit(bits, block_offset, [&](int64_t o, int64_t key) {
+    if (o >= cap) return;
+    if (kCoords) {
+      coords[o * 3] = (int32_t)(key / (G * G));
+      coords[o * 3 + 1] = (int32_t)((key / G) % G);
+      coords[o * 3 + 2] = (int32_t)(key % G);
+    } else {
+      keys[o] = key;
     }
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- normals

@@ -4,7 +4,8 @@
 //   * addressing: cell_of, in_grid, bit_at, and the two kernels that fill a zeroed bit set;
 //   * nearest_d2: the exact squared distance to the nearest occupied cell, by Chebyshev shells;
 //   * for_each_at_distance: every occupied cell at that distance, in a fixed order (the callers' float sums follow it);
-//   * the popcount scan that turns a bit set into per-block offsets of its set bits in key order;
+//   * the popcount scan that turns a bit set into per-block offsets of its set bits in key order, and for_each_set_bit,
+//     which lists them;
 //   * the rank table over that scan: an occupied cell's index among the set bits (rank_of, build_rank);
 //   * find_sorted_key: lower bound in a sorted key list.
 // Everything here has internal linkage: the objects link into one library.
@@ -170,6 +171,28 @@ __global__ void __launch_bounds__(1024) grid_block_scan_kernel(int64_t* block_co
   __syncthreads();
   int64_t acc = part[threadIdx.x];
   for (int64_t b = b0; b < b1; ++b) { const int64_t x = block_count[b]; block_count[b] = acc; acc += x; }
+}
+
+// f(o, key) for every set bit among the calling thread's words of scan block blockIdx.x, ascending: key = the cell, o = its
+// index among all set bits in key order.  A kernel over scan_blocks workgroups of kScanThreads threads, all of them calling,
+// lists a bit set this way (mesh.hip's cells and keys, ingest.hip's merged rows).
+template <typename F>
+__device__ __forceinline__ void for_each_set_bit(const unsigned* bits, const int64_t* block_offset, F f) {
+  unsigned w[kWordsPerThread];
+  const unsigned c = load_words(bits, blockIdx.x, w);
+  unsigned total;
+  int64_t o = block_offset[blockIdx.x] + block_scan(c, &total);
+  if (c == 0) return;
+  const int64_t word0 = (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread;
+  for (int k = 0; k < kWordsPerThread; ++k) {
+    unsigned x = w[k];
+    while (x) {
+      const int b = __ffs(x) - 1;
+      x &= x - 1;
+      f(o, (word0 + k) * 32 + b);
+      ++o;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- rank table

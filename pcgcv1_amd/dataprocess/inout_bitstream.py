@@ -125,9 +125,10 @@ def unpack_strings_head(buf):
 
 
 def write_binary_files_hyper(filename, y_strings, z_strings, points_numbers, cube_positions, y_min_vs, y_max_vs,
-                             y_shape, z_min_v, z_max_v, z_shape, rootdir='./', verbose=True, cubepos=None):
+                             y_shape, z_min_v, z_max_v, z_shape, rootdir='./', verbose=True, cubepos=None, frame=None):
     """cubepos: encode_cube_positions(cube_positions) when the caller already has it (test.py codes the positions on a
-    helper thread while the GPU encodes the cubes)."""
+    helper thread while the GPU encodes the cubes).  frame: the 40 bytes of <name>.frame (ingest.frame_bytes) of a cloud
+    that was voxelised from a scan: written with the others and counted in the printed total."""
     os.makedirs(rootdir, exist_ok=True)
     p = _paths(filename, rootdir)
     blobs = {
@@ -142,12 +143,27 @@ def write_binary_files_hyper(filename, y_strings, z_strings, points_numbers, cub
         with open(p[k], "wb") as f:
             f.write(v)
     sizes = tuple(len(blobs[k]) for k in ("strings", "strings_head", "strings_hyper", "pointnums", "cubepos"))
+    _write_frame(filename, rootdir, frame)
     if verbose:
         print('===== Write binary files =====')
-        print('Total file size (Bytes): {}'.format(sum(sizes)))
+        print('Total file size (Bytes): {}'.format(sum(sizes) + len(frame or b"")))
         for name, s in zip(('Strings', 'Strings head', 'Strings hyper', 'Numbers of points', 'Positions of cubes'), sizes):
             print('{} (Bytes): {}'.format(name, s))
+        if frame is not None:
+            print('Frame (Bytes): {}'.format(len(frame)))
     return sizes
+
+
+def _write_frame(filename, rootdir, frame):
+    """<name>.frame with the other files; a cloud written WITHOUT one takes an older <name>.frame away, or decompress would
+    apply another cloud's frame to it without any sign of it"""
+    name = os.path.join(rootdir, filename + ".frame")
+    if frame is not None:
+        with open(name, "wb") as f:
+            f.write(frame)
+    elif os.path.exists(name):
+        os.remove(name)
+        print("removed {}: it belonged to an earlier, voxelised cloud of this name".format(name))
 
 
 def read_binary_files_hyper(filename, rootdir='./'):
@@ -168,7 +184,7 @@ def read_binary_files_hyper(filename, rootdir='./'):
 
 # ------------------------------------------------------------------ factorized mode
 def write_binary_files_factorized(filename, strings, points_numbers, cube_positions, min_v, max_v, shape, rootdir='./',
-                                  verbose=True):
+                                  verbose=True, frame=None):
     os.makedirs(rootdir, exist_ok=True)
     p = _paths(filename, rootdir)
     blobs = {"strings": np.array(shape, dtype=np.int16).tobytes() + np.array((min_v, max_v), dtype=np.int8).tobytes()
@@ -179,9 +195,10 @@ def write_binary_files_factorized(filename, strings, points_numbers, cube_positi
         with open(p[k], "wb") as f:
             f.write(v)
     sizes = tuple(len(blobs[k]) for k in ("strings", "pointnums", "cubepos"))
+    _write_frame(filename, rootdir, frame)
     if verbose:
         print('===== Write binary files =====')
-        print('Total file size (Bytes): {}'.format(sum(sizes)))
+        print('Total file size (Bytes): {}'.format(sum(sizes) + len(frame or b"")))
     return sizes
 
 

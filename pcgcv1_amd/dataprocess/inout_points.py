@@ -3,7 +3,8 @@ dataprocess/inout_points.py, vectorised / on the device instead of per-point Pyt
 
   load_ply_data 8-28, write_ply_data 30-46, load_points 50-90 (partition), save_points 92-112
   (merge), points2voxels 116-132, voxels2points 134-143, select_voxels 147-168,
-  get_adaptive_thres 170-179.  load_ply_colors / write_ply_colors are the coloured forms of the first two.
+  get_adaptive_thres 170-179.  load_ply_colors / write_ply_colors are the coloured forms of the first two;
+  load_ply_scan reads a raw scan (float coordinates, colours, normals) without truncating it, for pcgcv1_amd/ingest.py.
 
 Bit-exact against the reference on the golden vectors (tests/golden/partition.npz, select.npz).
 Partition runs in libpcgc_host.so (`pcgc_partition`), voxelisation and the adaptive top-k
@@ -66,11 +67,10 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def _load_binary_ply(filename, with_colors=False):
-    """binary_little_endian / binary_big_endian ply (what MeshLab, Open3D and CloudCompare write by default) ->
-    (points int32 [N,3] truncated like the ASCII path, normals float32 [N,3] or None).  Vertex properties must be scalars
-    (x, y, z and anything else: colours, normals); elements after the vertices are ignored, elements before them refused.
-    with_colors=True appends a third value: colors uint8 [N,3] or None (load_ply_colors)."""
+def _binary_ply_vertices(filename):
+    """The vertex element of a binary_little_endian / binary_big_endian ply as a structured array, one field per property
+    in the file's byte order.  Vertex properties must be scalars (x, y, z and anything else: colours, normals); elements
+    after the vertices are ignored, elements before them refused."""
     with open(filename, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -96,11 +96,22 @@ def _load_binary_ply(filename, with_colors=False):
             fields.append((t[2], order + _PLY_TYPES[t[1]]))
     if n_vertex is None or before or not all(k in dict(fields) for k in "xyz"):
         raise ValueError("%s: binary ply needs a leading vertex element with x, y, z" % filename)
-    v = np.frombuffer(data, dtype=np.dtype(fields), count=n_vertex, offset=nl + 1)
-    pts = np.stack([v["x"], v["y"], v["z"]], -1).astype(np.float64).astype(np.int32)
-    nrm = None
+    return np.frombuffer(data, dtype=np.dtype(fields), count=n_vertex, offset=nl + 1)
+
+
+def _binary_ply_normals(v):
     if all(k in v.dtype.names for k in ("nx", "ny", "nz")):
-        nrm = np.stack([v["nx"], v["ny"], v["nz"]], -1).astype(np.float32)
+        return np.stack([v["nx"], v["ny"], v["nz"]], -1).astype(np.float32)
+    return None
+
+
+def _load_binary_ply(filename, with_colors=False):
+    """binary_little_endian / binary_big_endian ply (what MeshLab, Open3D and CloudCompare write by default) ->
+    (points int32 [N,3] truncated like the ASCII path, normals float32 [N,3] or None).  with_colors=True appends a third
+    value: colors uint8 [N,3] or None (load_ply_colors)."""
+    v = _binary_ply_vertices(filename)
+    pts = np.stack([v["x"], v["y"], v["z"]], -1).astype(np.float64).astype(np.int32)
+    nrm = _binary_ply_normals(v)
     if not with_colors:
         return pts, nrm
     names = _color_names(v.dtype.names)
@@ -135,40 +146,52 @@ def load_ply_colors(filename, as_float=False):
     normals and alpha; a file that declares none gives None.  ASCII bodies are parsed by libpcgc_host.so
     (pcgc_parse_ply_columns) on a few threads; binary files go through _load_binary_ply.  as_float=True keeps the
     positions of an ASCII file as float64 instead of truncating them (a scale != 1 reconstruction holds fractions)."""
-    import mmap
     with open(filename, "rb") as f:
         if _ply_is_binary(f, filename):
             pts, _, colors = _load_binary_ply(filename, with_colors=True)
             return pts, colors
-        f.seek(0)
-        head = f.read(4096)
-        while head.startswith(b"ply") and b"end_header" not in head:
-            more = f.read(65536)
-            if not more:
-                break
-            head += more
-        end = head.find(b"end_header")
-        if end < 0:
-            return load_ply_data(filename), None             # no header: nothing names a colour column
-        nl = head.find(b"\n", end)
-        start = nl + 1 if nl >= 0 else len(head)
-        props, n_vertex, element = [], -1, None
-        for ln in head[:end].decode("ascii", "replace").splitlines():
-            t = ln.split()
-            if len(t) >= 3 and t[0] == "element":
-                element = t[1]
-                if element == "vertex":
-                    n_vertex = int(t[2])
-            elif len(t) >= 3 and t[0] == "property" and element == "vertex":
-                props.append(t[-1])
-        if not all(k in props for k in "xyz"):
-            raise ValueError("%s: ply header declares no x, y, z vertex properties" % filename)
-        names = _color_names(props)
-        cols = np.array([props.index(k) for k in ("x", "y", "z") + (names or ())], np.int32)
-        size = os.fstat(f.fileno()).st_size
-        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size > start else None
+        table = _ascii_ply_columns(f, filename, (_COLOR_NAMES,))
+    if table is None:
+        return load_ply_data(filename), None                 # no header: nothing names a colour column
+    out, (names,) = table
+    pts = np.ascontiguousarray(out[:, :3]) if as_float else out[:, :3].astype(np.int32)
+    return pts, (_as_uint8_colors(out[:, 3:], filename) if names else None)
+
+
+def _ascii_ply_columns(f, filename, groups):
+    """The x y z columns of an open ASCII ply plus, for each entry of `groups` (alternative name triples, e.g. _COLOR_NAMES),
+    the first triple the header declares -> (float64 [n, 3 + 3 * found], [the triple found or None per group]); None for a
+    file without a header.  The body is parsed by libpcgc_host.so (pcgc_parse_ply_columns) on a few threads."""
+    import mmap
+    f.seek(0)
+    head = f.read(4096)
+    while head.startswith(b"ply") and b"end_header" not in head:
+        more = f.read(65536)
+        if not more:
+            break
+        head += more
+    end = head.find(b"end_header")
+    if end < 0:
+        return None
+    nl = head.find(b"\n", end)
+    start = nl + 1 if nl >= 0 else len(head)
+    props, n_vertex, element = [], -1, None
+    for ln in head[:end].decode("ascii", "replace").splitlines():
+        t = ln.split()
+        if len(t) >= 3 and t[0] == "element":
+            element = t[1]
+            if element == "vertex":
+                n_vertex = int(t[2])
+        elif len(t) >= 3 and t[0] == "property" and element == "vertex":
+            props.append(t[-1])
+    if not all(k in props for k in "xyz"):
+        raise ValueError("%s: ply header declares no x, y, z vertex properties" % filename)
+    found = [next((names for names in alternatives if all(k in props for k in names)), None) for alternatives in groups]
+    cols = np.array([props.index(k) for k in ("x", "y", "z") + tuple(k for names in found if names for k in names)], np.int32)
+    size = os.fstat(f.fileno()).st_size
+    mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size > start else None
     if mm is None:
-        return np.zeros((0, 3), np.int32), (np.zeros((0, 3), np.uint8) if names else None)
+        return np.zeros((0, len(cols)), np.float64), found
     try:
         buf = np.frombuffer(mm, np.uint8)[start:]
         cap = n_vertex if n_vertex >= 0 else buf.size // (2 * len(props)) + 1      # a row is at least "0 " per property
@@ -185,8 +208,31 @@ def load_ply_colors(filename, as_float=False):
     out = out[:int(n[0])]
     if n_vertex >= 0 and len(out) != n_vertex:
         raise ValueError("%s: header declares %d vertices, the body holds %d" % (filename, n_vertex, len(out)))
-    pts = np.ascontiguousarray(out[:, :3]) if as_float else out[:, :3].astype(np.int32)
-    return pts, (_as_uint8_colors(out[:, 3:], filename) if names else None)
+    return out, found
+
+
+def load_ply_scan(filename):
+    """A raw scan as it is: ply -> (points float64 [N,3], colors uint8 [N,3] or None, normals float32 [N,3] or None), nothing
+    truncated (fractions, negative coordinates, metres or millimetres: pcgcv1_amd/ingest.py puts it on a grid).  ASCII and
+    both binary byte orders; the property order is the header's."""
+    with open(filename, "rb") as f:
+        if _ply_is_binary(f, filename):
+            v = _binary_ply_vertices(filename)
+            pts = np.ascontiguousarray(np.stack([v["x"], v["y"], v["z"]], -1).astype(np.float64))
+            names = _color_names(v.dtype.names)
+            colors = _as_uint8_colors(np.stack([v[k] for k in names], -1), filename) if names else None
+            return pts, colors, _binary_ply_normals(v)
+        table = _ascii_ply_columns(f, filename, (_COLOR_NAMES, (("nx", "ny", "nz"),)))
+    if table is None:
+        raise ValueError("%s: a scan needs a ply header that names its columns" % filename)
+    out, (cnames, nnames) = table
+    at = 3
+    colors = normals = None
+    if cnames:
+        colors, at = _as_uint8_colors(out[:, at:at + 3], filename), at + 3
+    if nnames:
+        normals = np.ascontiguousarray(out[:, at:at + 3].astype(np.float32))
+    return np.ascontiguousarray(out[:, :3]), colors, normals
 
 
 def load_ply_normals(filename):

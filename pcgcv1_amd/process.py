@@ -34,12 +34,13 @@ def preprocess_points(points, scale, cube_size, min_num, device=True, block=None
     return cubes, pos, points_numbers
 
 
-def preprocess(input_file, scale, cube_size, min_num, device=True, verbose=True, block=None):
-    """-> (cubes [B,cs,cs,cs,1], cube_positions [B,3] in first-appearance order, points_numbers uint16 [B])."""
+def preprocess(input_file, scale, cube_size, min_num, device=True, verbose=True, block=None, points=None):
+    """-> (cubes [B,cs,cs,cs,1], cube_positions [B,3] in first-appearance order, points_numbers uint16 [B]).
+    points: the integer cloud when the caller already holds it (test.py --voxelize), instead of reading input_file."""
     if verbose:
         print('===== Preprocess =====')
     start = time.time()
-    pts = iop.load_ply_data(input_file)
+    pts = iop.load_ply_data(input_file) if points is None else points
     cubes, pos, nums = preprocess_points(pts, scale, cube_size, min_num, device, block)
     if verbose:
         print("Scaling + Partition + Voxelization: {}s".format(round(time.time() - start, 4)))

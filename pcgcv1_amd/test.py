@@ -8,7 +8,9 @@ decompress writes <name>_rec.ply.  compress --colors=raht --color_qstep=Q (a col
 of the decoded points (pcgcv1_amd/colorcodec.py); decompress finds that file and writes a coloured ply;
 --color_target=psnr:38 or bpp:0.6 instead of --color_qstep lets the encoder choose the step for a luma PSNR or a size.  --ckpt_dir additionally accepts "synthetic[:seed[:profile]]"
 (checkpoint.py).  --gpu=0 is rejected: this build has no CPU path; --gpu=N shards the cubes over N GPUs
-(one rank per GPU over RCCL, pcgcv1_amd/sharding.py; same files as one GPU).
+(one rank per GPU over RCCL, pcgcv1_amd/sharding.py; same files as one GPU).  compress --voxelize=BITS (or --voxel_size=S) takes a
+raw scan (float coordinates, several points per voxel; pcgcv1_amd/ingest.py) and adds <basename>.frame; decompress finds that
+file and writes the points in the scan's own coordinates.
 """
 import argparse
 import importlib
@@ -58,6 +60,12 @@ def parse_args(argv=None):
                            {"choices": ("range", "rans")} if name == "color_coder" else {}))
     ap.add_argument("--estimate_normals", action="store_true",
                     help="compress --pointnums=d2 with a ply that has no normals: estimate them (radius 10, 20 neighbours, as eval does)")
+    ap.add_argument("--voxelize", type=int, default=0, metavar="BITS",
+                    help="compress only: the input is a raw scan (float coordinates, any number of points per voxel); put it on a grid "
+                         "of 2^BITS cells per axis first (pcgcv1_amd/ingest.py), merged colours and normals feeding --colors=raht and "
+                         "--pointnums=d2, and write <name>.frame so that decompress returns the scan's own coordinates")
+    ap.add_argument("--voxel_size", type=float, default=0.0, metavar="S",
+                    help="compress only: as --voxelize, with voxels of edge S in the scan's units instead of a bit count")
     ap.add_argument("--render", default="", metavar="X.png",
                     help="decompress only: also draw the cloud just written into this png (pcgcv1_amd/render.py, default view and size)")
     args = ap.parse_args(argv)
@@ -75,7 +83,8 @@ def parse_args(argv=None):
         # with the other argument errors, before anything is loaded: d2 has nothing to measure against without normals
         ap.error("--pointnums=d2 needs normals: %s has no nx ny nz properties (or cannot be read); write them into the ply, or "
                  "pass --estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
-    print(args)
+    # the line every run prints: the ingest flags show up in it only when they are given
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size") or v}))
     return args
 
 
@@ -224,6 +233,23 @@ def _main(args, argv):
     if args.gpu < 1:
         raise SystemExit("--gpu=0: this build runs the hot path on an MI355X only (no CPU fallback)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.voxelize or args.voxel_size:
+        if args.voxelize and args.voxel_size:
+            raise SystemExit("--voxelize=%d and --voxel_size=%g both choose the grid of the scan: give one of them" % (args.voxelize, args.voxel_size))
+        if args.command != "compress":
+            raise SystemExit("--voxelize and --voxel_size belong to compress: decompress reads the frame from <name>.frame")
+        if args.scale != 1:
+            raise SystemExit("--voxelize and --voxel_size put the scan on the grid themselves: --scale must be 1 (got %g)" % args.scale)
+        if args.gpu > 1 or world > 1:
+            raise SystemExit("multi-GPU runs read a voxelised ply (--voxelize and --voxel_size run on one GPU)")
+        if not (1 <= args.voxelize <= 12 if args.voxelize else args.voxel_size > 0):
+            raise SystemExit("--voxelize takes 1..12 bits, --voxel_size a positive edge (got %s)" % (args.voxelize or args.voxel_size))
+    if args.command == "decompress" and args.input and os.path.exists(args.input + ".frame"):
+        why = "%s.frame maps the grid of the scale = 1 reconstruction back to the scan, on one GPU" % args.input
+        if args.scale != 1:
+            raise SystemExit("--scale=%g: %s" % (args.scale, why))
+        if args.gpu > 1 or world > 1:
+            raise SystemExit("--gpu=%d: %s" % (max(args.gpu, world), why))
     if (args.gpu > 1 or world > 1) and args.pointnums != "count":
         raise SystemExit("multi-GPU runs write --pointnums=count only (--pointnums=d1 and d2 run on one GPU)")
     if args.estimate_normals and (args.command != "compress" or args.pointnums != "d2"):
@@ -269,13 +295,17 @@ def _main(args, argv):
         if not args.output:
             args.output = os.path.split(args.input)[-1][:-4]
         coded_colors = args.colors == "raht"
-        if coded_colors:                          # before any GPU work: a ply without colours is refused by name
-            from .recolor import load_source
-            src_points, src_colors = load_source(args.input)
         optimised = args.pointnums != "count"
-        if args.pointnums == "d2":                # likewise: a ply without normals is refused before any GPU work
-            source = _load_normals(args)
-        cubes, cube_positions, points_numbers = preprocess(args.input, args.scale, args.cube_size, args.min_num)
+        points = frame = None
+        if args.voxelize or args.voxel_size:      # a raw scan: its merged points, colours and normals stand in for the file's
+            points, src_points, src_colors, source, frame = _voxelize_input(args, coded_colors)
+        else:
+            if coded_colors:                      # before any GPU work: a ply without colours is refused by name
+                from .recolor import load_source
+                src_points, src_colors = load_source(args.input)
+            if args.pointnums == "d2":            # likewise: a ply without normals is refused before any GPU work
+                source = _load_normals(args)
+        cubes, cube_positions, points_numbers = preprocess(args.input, args.scale, args.cube_size, args.min_num, points=points)
         logits = None
         if args.mode == "factorized":
             strings, min_v, max_v, shape = compress_factorized(cubes, model, args.ckpt_dir, verbose=True)
@@ -286,7 +316,7 @@ def _main(args, argv):
             elif args.pointnums == "d2":
                 points_numbers = _d2_counts(args, cubes, logits, points_numbers, cube_positions, source)
             bs.write_binary_files_factorized(args.output, strings, points_numbers, cube_positions, min_v, max_v, shape,
-                                             rootdir='./compressed')
+                                             rootdir='./compressed', frame=frame)
         else:
             # the batched, two-pipeline path bench.py times; PCGC_STAGE_TIMES=1 prints the reference's per-stage times
             # instead (transform.py:121-171), which serialises the stages
@@ -313,7 +343,7 @@ def _main(args, argv):
             _report(model, args.ckpt_dir, t0)
             bs.write_binary_files_hyper(args.output, y_strings, z_strings, points_numbers, cube_positions, y_min_vs,
                                         y_max_vs, y_shape, z_min_v, z_max_v, z_shape, rootdir='./compressed',
-                                        cubepos=cubepos.result())
+                                        cubepos=cubepos.result(), frame=frame)
         if coded_colors:
             _write_colors(args, logits, points_numbers, cube_positions, src_points, src_colors)
     else:
@@ -321,6 +351,10 @@ def _main(args, argv):
         if not args.output:
             args.output = filename + "_rec.ply"
         colors_file = args.input + ".colors" if os.path.exists(args.input + ".colors") else ""
+        frame = None
+        if os.path.exists(args.input + ".frame"):        # the cloud was voxelised from a scan: its own coordinates go out
+            from .ingest import read_frame
+            frame = read_frame(args.input + ".frame")
         if args.mode == "factorized":
             strings, points_numbers, cube_positions, min_v, max_v, shape = bs.read_binary_files_factorized(filename, rootdir)
             cubes = decompress_factorized(strings, min_v, max_v, shape, model, args.ckpt_dir, verbose=True)
@@ -331,7 +365,7 @@ def _main(args, argv):
             # the tail (top-k, points, text, file) follows the decoder slice by slice instead of waiting for the last cube;
             # PCGC_STREAM_TAIL=0 / --scale != 1 / PCGC_STAGE_TIMES=1: postprocess on the whole batch, as the reference does
             tail = None
-            if args.scale == 1 and not stage_times and os.environ.get("PCGC_STREAM_TAIL", "1") != "0" and not args.colors_from and not colors_file:
+            if args.scale == 1 and not stage_times and os.environ.get("PCGC_STREAM_TAIL", "1") != "0" and not args.colors_from and not colors_file and frame is None:
                 tail = StreamedPostprocess(args.output, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
             cubes = decompress_hyper(y_strings, y_min_vs, y_max_vs, y_shape, z_strings, z_min_v, z_max_v, z_shape, model,
                                      args.ckpt_dir, verbose=stage_times, on_slice=tail)
@@ -342,13 +376,61 @@ def _main(args, argv):
                 return
             _report(model, args.ckpt_dir, t0)
         if args.colors_from:
-            return _write_recolored(args, cubes, points_numbers, cube_positions)
+            return _write_recolored(args, cubes, points_numbers, cube_positions, frame)
         if colors_file:
-            return _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file)
+            return _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file, frame)
+        if frame is not None:
+            return _write_in_frame(args, cubes, points_numbers, cube_positions, frame)
         postprocess(args.output, cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
 
 
-def _write_recolored(args, cubes, points_numbers, cube_positions):
+def _voxelize_input(args, coded_colors):
+    """--voxelize / --voxel_size: the scan read as it is and put on its grid in memory (pcgcv1_amd/ingest.py) -> (points, colour
+    source points, colour source colours, (points, normals) for d2 or None, the 40 bytes of <name>.frame).  What the scan
+    lacks is refused by name before any GPU work."""
+    import numpy as np
+    from . import ingest
+    from .dataprocess.inout_points import load_ply_scan
+    t0 = time.time()
+    scan, colors, normals = load_ply_scan(args.input)
+    if coded_colors and colors is None:
+        raise SystemExit("%s has no colour properties (red green blue): nothing to transfer" % args.input)
+    if args.pointnums == "d2" and normals is None and not args.estimate_normals:
+        raise SystemExit("--pointnums=d2 needs normals: %s has no nx ny nz properties; write them into the ply, or pass "
+                         "--estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
+    try:
+        points, colors, normals, counts, frame, n_dropped = ingest.voxelize_scan(
+            scan, colors if coded_colors else None, normals if args.pointnums == "d2" else None,
+            bits=args.voxelize or None, voxel_size=args.voxel_size or None)
+    except ValueError as e:
+        raise SystemExit("%s: %s" % (args.input, e))
+    print(ingest.summary_line(len(scan), n_dropped, counts, frame))
+    print("Read and voxelise {}: {}s".format(args.input, round(time.time() - t0, 4)))
+    source = None
+    if args.pointnums == "d2":
+        if normals is None:
+            from .metrics import estimate_normals
+            normals = estimate_normals(points, 10, 20)
+        else:                                     # as the voxelised ply would hand them on: six decimals (write_ply_normals)
+            normals = np.round(normals.astype("float"), 6).astype(np.float32)
+        source = (points, normals)
+    return points, points, colors, source, ingest.frame_bytes(frame)
+
+
+def _write_in_frame(args, cubes, points_numbers, cube_positions, frame):
+    """<name>.frame is there: the decoded points (postprocess's, in its order) in the scan's own coordinates"""
+    from .dataprocess.inout_points import write_ply_data
+    from .ingest import apply_frame
+    from .process import postprocess_points
+    print('===== Post process =====')
+    t0 = time.time()
+    pts = postprocess_points(cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
+    write_ply_data(args.output, apply_frame(pts, frame))
+    print("Apply {}.frame and write {}: {}s ({} points, step {!r})".format(args.input, args.output, round(time.time() - t0, 4), len(pts),
+                                                                           frame.step))
+
+
+def _write_recolored(args, cubes, points_numbers, cube_positions, frame=None):
     """--colors_from: the decoded points (the ones postprocess would write, in its order) with the original's colours"""
     from .dataprocess.inout_points import write_ply_colors
     from .process import postprocess_points
@@ -358,7 +440,7 @@ def _write_recolored(args, cubes, points_numbers, cube_positions):
     src_points, src_colors = load_source(args.colors_from)
     pts = postprocess_points(cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
     colors, counts = recolor(src_points, src_colors, pts, return_counts=True)
-    write_ply_colors(args.output, pts, colors)
+    write_ply_colors(args.output, pts if frame is None else _in_frame(pts, frame), colors)
     print("Recolour from {} and write {}: {}s ({} of {} points coloured from their own nearest source points)".format(
         args.colors_from, args.output, round(time.time() - t0, 4), int((counts == 0).sum()), len(pts)))
 
@@ -392,7 +474,12 @@ def _write_colors(args, logits, points_numbers, cube_positions, src_points, src_
         round(time.time() - t0, 4)))
 
 
-def _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file):
+def _in_frame(pts, frame):
+    from .ingest import apply_frame
+    return apply_frame(pts, frame)
+
+
+def _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_file, frame=None):
     """<name>.colors is there: the decoded points (postprocess's, in its order) with the colours the stream holds"""
     import numpy as np
     from .colorcodec import decode_colors, read_colors_file
@@ -402,7 +489,7 @@ def _write_decoded_colors(args, cubes, points_numbers, cube_positions, colors_fi
     t0 = time.time()
     pts = postprocess_points(cubes, points_numbers, cube_positions, args.scale, args.cube_size, args.rho)
     colors = decode_colors(np.asarray(pts).astype(np.int32), read_colors_file(colors_file))
-    write_ply_colors(args.output, pts, colors)
+    write_ply_colors(args.output, pts if frame is None else _in_frame(pts, frame), colors)
     print("Decode {} and write {}: {}s ({} points)".format(colors_file, args.output, round(time.time() - t0, 4), len(pts)))
 
 
