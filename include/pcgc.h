@@ -570,6 +570,23 @@ int pcgc_ingest_merge(const int64_t* keys, int64_t n, int bits, const uint8_t* c
                       int32_t* out_points, int32_t* out_counts, uint8_t* out_colors, float* out_normals, int64_t cap,
                       int64_t* n_out, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- outlier voxels of a scan: neighbourhood statistics (pcgcv1_amd/clean.py; tests/_clean_ref.py is the
+ * rule in numpy) ----
+ * points int32 [n,3], distinct, on the grid of res = 2^bits cells per axis, 1 <= bits <= 12; 0 <= k <= 64; 1 <= radius
+ * R <= 32.  For a voxel p, N(p) = the multiset of squared distances d2(p, q) over the occupied q != p with d2 <= R * R (a
+ * Euclidean ball).  isqrt16(d) = floor(sqrt(d * 2^32)), from an exact integer table over d = 0 .. 1024.
+ *   cnt int32 [n]: |N(p)|;
+ *   S   int64 [n]: the sum of isqrt16 over the min(k, cnt) smallest members of N(p), plus (k - min(k, cnt)) * ((R + 1) <<
+ *     16): a neighbour the ball does not hold is charged as if it sat at distance R + 1.  Ties at the k-th distance do
+ *     not matter (equal distances, equal terms).
+ * All integer, independent of the order of the rows and of the threads; a ball that leaves the grid is clipped to it.  S
+ * or cnt may be NULL, not both; with k == 0, S must be NULL.  A point outside the grid sets no bit, is nobody's neighbour
+ * and gets S = k * ((R + 1) << 16), cnt = 0.  A bad argument returns an error before any memory is touched.  1 <= n <
+ * 2^31.  workspace: pcgc_clean_workspace_bytes(bits, n) (0 for a bad argument), the bit set over res^3 cells. */
+size_t pcgc_clean_workspace_bytes(int bits, int64_t n);
+int pcgc_clean_neighbors(const int32_t* points, int64_t n, int bits, int k, int radius, int64_t* S, int32_t* cnt,
+                         void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

@@ -41,6 +41,7 @@ HIP_SOURCES = {
     "offgrid.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "ingest.hip": ["-ffp-contract=off"],
+    "clean.hip": [],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

@@ -2,6 +2,7 @@
 -> one integer point per occupied voxel with merged attributes, and the frame that maps it back.
 
     python -m pcgcv1_amd.ingest --input scan.ply --output scan_vox10.ply --bits 10      # or --voxel_size 0.002
+                                [--clean stat:20:2.0]       # drop outlier voxels and refit the frame: voxelize_scan_clean
 
 writes the voxelised ply and scan_vox10.frame next to it.  The rule (include/pcgc.h, pcgc_ingest_*; DESIGN.md §7f;
 tests/_ingest_ref.py restates it in numpy), all position arithmetic in float64:
@@ -179,10 +180,15 @@ def merge_device(keys, bits, colors=None, normals=None):
     return pts, counts, oc, on, n_out
 
 
-def voxelize_scan(points, colors=None, normals=None, frame=None, bits=None, voxel_size=None):
+def voxelize_scan(points, colors=None, normals=None, frame=None, bits=None, voxel_size=None, clean=None):
     """A scan (float [N,3]; colors uint8 [N,3], normals float [N,3] or None) on the grid of `frame`, or of the frame fitted to it
     for `bits` or `voxel_size` -> (points int32 [M,3] in np.unique's order, colors uint8 [M,3] | None, normals float32
-    [M,3] | None, counts int32 [M], frame, n_dropped).  Points outside a given frame are clamped to its grid."""
+    [M,3] | None, counts int32 [M], frame, n_dropped).  Points outside a given frame are clamped to its grid.
+    clean (a --clean spec or a list of them, pcgcv1_amd/clean.py): voxelize_scan_clean's eight values instead."""
+    if clean:
+        if frame is not None:
+            raise ValueError("voxelize_scan: clean refits the frame to what it keeps: give bits or voxel_size, not a frame")
+        return voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)
     if frame is not None and (bits is not None or voxel_size is not None):
         raise ValueError("voxelize_scan: give a frame, or bits / voxel_size to fit one")
     p_d = _device_points(points)
@@ -192,6 +198,55 @@ def voxelize_scan(points, colors=None, normals=None, frame=None, bits=None, voxe
     _, keys = quantize(p_d, frame)
     pts, counts, c, nrm = merge(keys, frame.bits, colors, normals)
     return pts, c, nrm, counts, frame, n_dropped
+
+
+def voxelize_scan_clean(points, colors=None, normals=None, bits=None, voxel_size=None, clean=()):
+    """voxelize_scan with the outlier voxels of pcgcv1_amd/clean.py dropped and the frame fitted again to what is left ->
+    (points, colors, normals, counts, frame, n_dropped, n_removed_voxels, n_removed_points):
+      1. fit the frame, quantise, merge, and run the filters `clean` (a spec or a list, applied in order) on the voxels;
+      2. drop the input rows whose voxel was removed, as well as the non-finite ones;
+      3. bounds over the kept rows, the frame fitted again with the same bits / voxel_size;
+      4. quantise and merge again.
+    There is no second cleaning pass: the result is not filtered on its own, finer, grid.  With bits the resolution the
+    outliers took comes back; with voxel_size the origin stays a multiple of the step, so the result is the kept voxels of
+    pass 1 shifted by whole cells, in possibly fewer bits.  ValueError when the filters would leave nothing."""
+    return _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)[0]
+
+
+def _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean):
+    """-> (voxelize_scan_clean's values, the voxels of pass 1 as a device tensor: what the command lines report on)"""
+    import torch
+    from . import clean as cleaner
+    specs = cleaner.parse_specs(clean)
+    p_d = _device_points(points)
+    lo, hi, n_dropped = bounds(p_d)
+    frame = _frame_from_bounds(lo, hi, bits, voxel_size)
+    _, keys = quantize(p_d, frame)
+    vox, _, _, _, n_out = merge_device(keys, frame.bits)
+    vox = vox[:int(n_out.item())]
+    keep = torch.from_numpy(cleaner.keep_mask_all(vox, frame.bits, specs)).to(p_d.device)
+    # a row's voxel: the voxels are in ascending key, a dropped row (key -1) finds some voxel and is refused by its key
+    res = 1 << frame.bits
+    vox_keys = (vox[:, 0].long() * res + vox[:, 1].long()) * res + vox[:, 2].long()
+    row_keep = keep[torch.searchsorted(vox_keys, keys).clamp_(max=len(vox_keys) - 1)] & (keys >= 0)
+    n_removed_points = int(p_d.shape[0]) - n_dropped - int(row_keep.sum().item())
+
+    def rows(a, dtype):
+        if a is None:
+            return None
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        if tuple(t.shape) != (int(p_d.shape[0]), 3):
+            raise ValueError("ingest: %d points, attribute of shape %s" % (int(p_d.shape[0]), tuple(t.shape)))
+        if dtype == torch.uint8 and t.dtype != torch.uint8:
+            raise ValueError("ingest: colours must be uint8 (got %s)" % t.dtype)
+        return t.to(p_d.device, dtype)[row_keep]
+
+    kept = p_d[row_keep]
+    lo, hi, _ = bounds(kept)
+    frame = _frame_from_bounds(lo, hi, bits, voxel_size)
+    _, keys = quantize(kept, frame)
+    pts, counts, c, nrm = merge(keys, frame.bits, rows(colors, torch.uint8), rows(normals, torch.float32))
+    return (pts, c, nrm, counts, frame, n_dropped, int((~keep).sum().item()), n_removed_points), vox
 
 
 def apply_frame(points, frame):
@@ -235,13 +290,27 @@ def frame_path(ply_or_stem):
 
 
 # ---------------------------------------------------------------------------- command line
-def ingest_file(filename, bits=None, voxel_size=None):
-    """load_ply_scan + voxelize_scan -> (points, colors | None, normals | None, counts, frame, n_dropped, n_input)"""
+def voxelize_scan_report(points, colors=None, normals=None, bits=None, voxel_size=None, clean=None):
+    """what the command lines run -> (voxelize_scan's six values, the 'clean: ...' summary line, or None without clean)"""
+    if not clean:
+        return voxelize_scan(points, colors, normals, bits=bits, voxel_size=voxel_size), None
+    from . import clean as cleaner
+    import torch
+    out, vox = _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)
+    cube = vox >> 6                                             # 64^3 cubes of pass 1: at most 6 bits per axis are left
+    cubes = len(torch.unique((cube[:, 0] << 12) | (cube[:, 1] << 6) | cube[:, 2]))
+    return out[:6], cleaner.summary_line(clean, len(vox), out[6], cubes, cleaner.n_cubes(out[0]), out[7])
+
+
+def ingest_file(filename, bits=None, voxel_size=None, clean=None):
+    """load_ply_scan + voxelize_scan -> (points, colors | None, normals | None, counts, frame, n_dropped, n_input), and with
+    clean the 'clean: ...' summary line as an eighth value"""
     from .dataprocess.inout_points import load_ply_scan
     points, colors, normals = load_ply_scan(filename)
     if not len(points):
         raise ValueError("%s holds no points" % filename)
-    return voxelize_scan(points, colors, normals, bits=bits, voxel_size=voxel_size) + (len(points),)
+    out, line = voxelize_scan_report(points, colors, normals, bits, voxel_size, clean)
+    return out + (len(points),) + ((line,) if clean else ())
 
 
 def summary_line(n_input, n_dropped, counts, frame):
@@ -257,7 +326,10 @@ def parse_args(argv=None):
     ap.add_argument("--voxel_size", type=float, default=None, help="voxel edge in the scan's units; the grid grows to hold the scan")
     ap.add_argument("--attributes", choices=("colors", "normals"), default="colors",
                     help="which attribute the ply carries when the scan has both (it has room for one)")
+    from .clean import add_clean_argument, check_clean_argument
+    add_clean_argument(ap)
     args = ap.parse_args(argv)
+    check_clean_argument(ap, args)
     if (args.bits is None) == (args.voxel_size is None):
         ap.error("give --bits or --voxel_size, one of them")
     if args.bits is not None and not 1 <= args.bits <= MAX_BITS:
@@ -271,7 +343,8 @@ def main(argv=None):
     from .dataprocess.inout_points import write_ply_colors, write_ply_data, write_ply_normals
     args = parse_args(argv)
     try:
-        points, colors, normals, counts, frame, n_dropped, n_input = ingest_file(args.input, args.bits, args.voxel_size)
+        out = ingest_file(args.input, args.bits, args.voxel_size, args.clean)
+        points, colors, normals, counts, frame, n_dropped, n_input = out[:7]
     except ValueError as e:
         raise SystemExit("ingest: %s" % e)
     if colors is not None and (normals is None or args.attributes == "colors"):
@@ -282,6 +355,8 @@ def main(argv=None):
         write_ply_data(args.output, points)
     write_frame(frame_path(args.output), frame)
     print(summary_line(n_input, n_dropped, counts, frame))
+    if args.clean:
+        print(out[7])
     print("wrote {} and {}".format(args.output, frame_path(args.output)))
 
 

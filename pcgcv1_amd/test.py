@@ -66,9 +66,18 @@ def parse_args(argv=None):
                          "--pointnums=d2, and write <name>.frame so that decompress returns the scan's own coordinates")
     ap.add_argument("--voxel_size", type=float, default=0.0, metavar="S",
                     help="compress only: as --voxelize, with voxels of edge S in the scan's units instead of a bit count")
+    from .clean import add_clean_argument, check_clean_argument
+    add_clean_argument(ap)
     ap.add_argument("--render", default="", metavar="X.png",
                     help="decompress only: also draw the cloud just written into this png (pcgcv1_amd/render.py, default view and size)")
     args = ap.parse_args(argv)
+    check_clean_argument(ap, args)
+    if args.clean and args.command != "compress":
+        ap.error("--clean belongs to compress: decompress writes what the stream holds")
+    if args.clean and args.scale != 1:
+        ap.error("--clean filters the voxels of the grid as it is: --scale must be 1 (got %g)" % args.scale)
+    if args.clean and (args.gpu > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("multi-GPU runs read a cleaned ply (--clean runs on one GPU)")
     if args.color_target:                                 # with the other argument errors, before anything is loaded
         from .colorcodec import parse_target
         try:
@@ -84,7 +93,7 @@ def parse_args(argv=None):
         ap.error("--pointnums=d2 needs normals: %s has no nx ny nz properties (or cannot be read); write them into the ply, or "
                  "pass --estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
     # the line every run prints: the ingest flags show up in it only when they are given
-    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size") or v}))
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size", "clean") or v}))
     return args
 
 
@@ -305,6 +314,10 @@ def _main(args, argv):
                 src_points, src_colors = load_source(args.input)
             if args.pointnums == "d2":            # likewise: a ply without normals is refused before any GPU work
                 source = _load_normals(args)
+            if args.clean:                        # a voxelised ply: its outlier voxels go, with their colours and normals
+                points, src_points, src_colors, source = _clean_input(args, src_points if coded_colors else None,
+                                                                      src_colors if coded_colors else None,
+                                                                      source if args.pointnums == "d2" else None)
         cubes, cube_positions, points_numbers = preprocess(args.input, args.scale, args.cube_size, args.min_num, points=points)
         logits = None
         if args.mode == "factorized":
@@ -399,12 +412,14 @@ def _voxelize_input(args, coded_colors):
         raise SystemExit("--pointnums=d2 needs normals: %s has no nx ny nz properties; write them into the ply, or pass "
                          "--estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
     try:
-        points, colors, normals, counts, frame, n_dropped = ingest.voxelize_scan(
+        (points, colors, normals, counts, frame, n_dropped), cleaned = ingest.voxelize_scan_report(
             scan, colors if coded_colors else None, normals if args.pointnums == "d2" else None,
-            bits=args.voxelize or None, voxel_size=args.voxel_size or None)
+            bits=args.voxelize or None, voxel_size=args.voxel_size or None, clean=args.clean)
     except ValueError as e:
         raise SystemExit("%s: %s" % (args.input, e))
     print(ingest.summary_line(len(scan), n_dropped, counts, frame))
+    if cleaned:
+        print(cleaned)
     print("Read and voxelise {}: {}s".format(args.input, round(time.time() - t0, 4)))
     source = None
     if args.pointnums == "d2":
@@ -415,6 +430,29 @@ def _voxelize_input(args, coded_colors):
             normals = np.round(normals.astype("float"), 6).astype(np.float32)
         source = (points, normals)
     return points, points, colors, source, ingest.frame_bytes(frame)
+
+
+def _clean_input(args, src_points, src_colors, source):
+    """--clean on a voxelised ply (pcgcv1_amd/clean.py) -> (points, colour source points, colours, (points, normals) for d2):
+    the file's rows that the filters keep.  The colour and normal rows are the file's rows, so one mask serves them all."""
+    import numpy as np
+    from . import clean
+    from .dataprocess.inout_points import load_ply_data
+    t0 = time.time()
+    points = load_ply_data(args.input)
+    try:
+        if len(np.unique(points, axis=0)) != len(points):
+            raise ValueError("a voxel holds several points: --clean reads one point per voxel (--voxelize merges a raw scan)")
+        kept, _, _, _, mask = clean.clean_cloud(points, None, None, None, clean.bits_for(points), args.clean)
+    except ValueError as e:
+        raise SystemExit("%s: %s" % (args.input, e))
+    print(clean.summary_line(args.clean, len(points), len(points) - len(kept), clean.n_cubes(points), clean.n_cubes(kept)))
+    print("Read and clean {}: {}s".format(args.input, round(time.time() - t0, 4)))
+    if src_points is not None:
+        src_points, src_colors = src_points[mask], src_colors[mask]
+    if source is not None:
+        source = (source[0][mask], source[1][mask])
+    return kept, src_points, src_colors, source
 
 
 def _write_in_frame(args, cubes, points_numbers, cube_positions, frame):
