@@ -278,6 +278,43 @@ int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, con
                      int oy, int oz, int res, double* out4, double* best, double* plane, int32_t* n_ties,
                      void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* Rigid registration (ICP) of a float32 source cloud P against a target Q: one step = correspondences under a trial pose,
+ * reduced to the sums a point-to-point (Kabsch) or point-to-plane solve needs (pcgcv1_amd/register.py solves on the host;
+ * DESIGN.md §7h; tests/_register_ref.py is the rule in numpy).  Q, its cells (h, ox, oy, oz, res) and the search are those
+ * of pcgc_offgrid_* above; coordinates are in grid units (neighbouring surface points about 1 apart).
+ *   pcgc_register_workspace_bytes: the off-grid workspace followed by 45 x 1024 doubles; 0 for a bad size.
+ *   pcgc_register_prepare: the cells of Q (bit set, rank table, cell starts) into the workspace, once per target, and the
+ *     flag cleared.  The workspace then belongs to that (q, nq, cells) until the next prepare.
+ *   pcgc_register_step: R9 (row-major), t3, c3 are HOST doubles, taken by value.  All arithmetic is IEEE float64, one
+ *     operation per step in the order written.  Per point i of P:
+ *       p'   = float32(((R[3r] x + R[3r+1] y) + R[3r+2] z) + t[r]), r = 0, 1, 2, with x = double(P[i,0]) ...
+ *       best = min over Q of d2(p', q), T = every j with |d2(p', q_j) - best| < 1e-8, w = 1.0 / double(|T|)
+ *       used iff best <= max_dist * max_dist
+ *     and per used point and j in T:  a = double(p') - c,  b = double(Q[j]) - c,  n = double(normals_q[j]) (float32
+ *     [nq,3] in Q's order, taken as given, or NULL),
+ *       res = ((a0-b0) n0 + (a1-b1) n1) + (a2-b2) n2
+ *       J   = (a1 n2 - a2 n1, a2 n0 - a0 n2, a0 n1 - a1 n0, n0, n1, n2)
+ *     out45 (double, device):
+ *       [0]      number of used points (counted in integers)        [1]      sum of best, once per used point
+ *       [2..4]   sum of w a_r            [5..7]   sum of w b_r       [8..16]  sum of (w a_r) b_c, row-major
+ *       [17..37] sum of (w J_r) J_c for r <= c, the row-major upper triangle
+ *       [38..43] sum of (w J_r) res      [44]     sum of (w res) res;       [17..44] are 0 when normals_q is NULL.
+ *     The sums are float64 in a fixed order (per thread in grid-stride order, a fixed tree per workgroup, the workgroups
+ *     in index order; no float atomics): the same input gives the same bits.  best double [np] and n_ties int32 [np]
+ *     (0 for a point outside the gate) are optional, both or neither.
+ *   A coordinate of p' that is a NaN or that no cell holds raises the step's flag in the workspace: out45 of that step is
+ *   all NaN.  A Q that is not sorted or leaves the grid raises prepare's flag: every step is NaN until the next prepare.
+ *   Neither touches memory out of bounds.  A step on a workspace that was not prepared for this (q, nq, cells) is
+ *   undefined.  Rejects a null pointer, a max_dist that is not finite or <= 0, a pose or centre that is not finite, bad
+ *   cells and a workspace smaller than pcgc_register_workspace_bytes. */
+size_t pcgc_register_workspace_bytes(int res, int64_t nq);
+int pcgc_register_prepare(const float* q, int64_t nq, double h, int ox, int oy, int oz, int res, void* workspace,
+                          size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_register_step(const float* p, int64_t np, const float* q, int64_t nq, const float* normals_q, double h, int ox,
+                       int oy, int oz, int res, const double* R9, const double* t3, const double* c3, double max_dist,
+                       double* out45, double* best, int32_t* n_ties, void* workspace, size_t workspace_bytes,
+                       pcgc_stream_t stream);
+
 /* ---- Rendering (pcgcv1_amd/render.py; DESIGN.md "Rendering"; tests/_render_ref.py is the rule in numpy) ---------------
  * A cloud to an image: demo.ipynb:586,596,962,972 (o3d.visualization.draw_geometries), on a node without a display.
  * Orthographic, all integers after one rounding, so an image is defined bit for bit.

@@ -228,6 +228,100 @@ __global__ void offgrid_mse_final_kernel(const double* partial, int nb, int64_t 
   for (int k = 0; k < 4; ++k) out4[k] = *bad ? (double)NAN : ((k < 2 || with_plane) ? v[k] : 0.0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- registration
+// One ICP step (include/pcgc.h, pcgc_register_step; tests/_register_ref.py): the source under a trial pose, its tied nearest
+// neighbours, and the 45 sums of the point-to-point and point-to-plane normal equations.  The pose travels as a kernel argument.
+constexpr int kRegSums = 45;
+
+struct Pose {
+  double R[9], t[3], c[3];
+};
+
+// the terms of one pair (a, b, normal n, weight w) added to acc[2 ..]; without a normal acc[17 ..] is left alone
+__device__ __forceinline__ void add_pair_terms(double acc[kRegSums], const double a[3], const double b[3], const float* n, double w) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double wa = w * a[r];
+    acc[2 + r] += wa;
+    acc[5 + r] += w * b[r];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[8 + r * 3 + c] += wa * b[c];
+  }
+  if (!n) return;
+  const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
+  const double res = ((a[0] - b[0]) * n0 + (a[1] - b[1]) * n1) + (a[2] - b[2]) * n2;
+  const double J[6] = {a[1] * n2 - a[2] * n1, a[2] * n0 - a[0] * n2, a[0] * n1 - a[1] * n0, n0, n1, n2};
+  int k = 17;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double wj = w * J[r];
+#pragma unroll
+    for (int c = r; c < 6; ++c) acc[k++] += wj * J[c];
+    acc[38 + r] += wj * res;
+  }
+  acc[44] += (w * res) * res;
+}
+
+// partial[k * kOffgridBlocks + b] = sum k of workgroup b.  45 accumulators per thread stay in registers; the workgroup's
+// sum is a shuffle tree per wave, then the four waves in order (4 x 45 doubles of LDS, not 45 x 256).
+__global__ void __launch_bounds__(256) register_step_kernel(const float* p, int64_t np, Target t, const float* normals_q, Pose pose,
+                                                            double gate2, double* partial, double* best_out, int32_t* ties_out,
+                                                            int* bad) {
+  __shared__ double sh[4][kRegSums];
+  double acc[kRegSums];
+#pragma unroll
+  for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
+  long long n_used = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
+    const double x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+    float pf[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) pf[r] = (float)(((pose.R[3 * r] * x + pose.R[3 * r + 1] * y) + pose.R[3 * r + 2] * z) + pose.t[r]);
+    int cell[3], shell, ties = 0;
+    double best = NAN;
+    if (cell_of_point(t.c, pf, cell)) {
+      const double px = pf[0], py = pf[1], pz = pf[2];
+      best = nearest_offgrid(t, cell, px, py, pz, &shell);
+      if (best <= gate2) {
+        for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t, double, double, double) { ++ties; });
+        const double w = 1.0 / (double)ties;
+        const double a[3] = {px - pose.c[0], py - pose.c[1], pz - pose.c[2]};
+        for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t j, double, double, double) {
+          const float* q = t.q + (int64_t)j * 3;
+          const double b[3] = {(double)q[0] - pose.c[0], (double)q[1] - pose.c[1], (double)q[2] - pose.c[2]};
+          add_pair_terms(acc, a, b, normals_q ? normals_q + (int64_t)j * 3 : nullptr, w);
+        });
+        ++n_used;
+        acc[1] += best;
+      }
+    } else {
+      atomicOr(bad, 1);
+    }
+    if (best_out) { best_out[i] = best; ties_out[i] = ties; }
+  }
+  acc[0] = (double)n_used;                                    // below 2^31 per launch: exact, and so is every partial sum of them
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kRegSums; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) sh[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kRegSums)
+    partial[threadIdx.x * kOffgridBlocks + blockIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+// one wave: lane k adds sum k of the workgroups in index order; bad[0] is prepare's flag (the target), bad[1] this step's
+__global__ void __launch_bounds__(64) register_final_kernel(const double* partial, int nb, const int* bad, double* out45) {
+  const int k = threadIdx.x;
+  if (k >= kRegSums) return;
+  double v = 0.0;
+  for (int i = 0; i < nb; ++i) v += partial[k * kOffgridBlocks + i];
+  out45[k] = (bad[0] | bad[1]) ? (double)NAN : v;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host side
 bool edge_ok(double h) {
   int e;
@@ -333,6 +427,50 @@ int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, con
                      b.bad);
   hipLaunchKernelGGL(offgrid_mse_final_kernel, dim3(1), dim3(64), 0, s, b.partial, blocks, np, normals_q ? 1 : 0, b.bad, out4);
   return launch_ok("off-grid mse kernels");
+}
+
+// the off-grid layout as it is, then [45, kOffgridBlocks] doubles; the second word of the flag's 256 bytes is the step's flag
+size_t pcgc_register_workspace_bytes(int res, int64_t nq) {
+  const size_t base = pcgc_offgrid_workspace_bytes(res, nq);
+  return base ? base + align256((size_t)kRegSums * kOffgridBlocks * sizeof(double)) : 0;
+}
+
+int pcgc_register_prepare(const float* q, int64_t nq, double h, int ox, int oy, int oz, int res, void* workspace,
+                          size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(q && workspace && grid_ok(h, ox, oy, oz, res, 1, nq), "pcgc_register_prepare: bad arguments");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_register_workspace_bytes(res, nq), "pcgc_register_prepare: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const OffgridBuffers b = offgrid_layout(res, nq, workspace);
+  Target t;
+  const int rc = build_target(b, Cells{h, ox, oy, oz, res}, q, nq, s, &t);
+  if (rc) return rc;
+  return launch_ok("registration target kernels");
+}
+
+int pcgc_register_step(const float* p, int64_t np, const float* q, int64_t nq, const float* normals_q, double h, int ox, int oy, int oz,
+                       int res, const double* R9, const double* t3, const double* c3, double max_dist, double* out45, double* best,
+                       int32_t* n_ties, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(p && q && R9 && t3 && c3 && out45 && workspace && grid_ok(h, ox, oy, oz, res, np, nq) &&
+               (best == nullptr) == (n_ties == nullptr), "pcgc_register_step: bad arguments");
+  PCGC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0, "pcgc_register_step: max_dist must be finite and positive (got %g)", max_dist);
+  Pose pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R9[k];
+  for (int k = 0; k < 3; ++k) { pose.t[k] = t3[k]; pose.c[k] = c3[k]; }
+  bool finite = true;
+  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(pose.R[k]);
+  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(pose.t[k]) && std::isfinite(pose.c[k]);
+  PCGC_REQUIRE(finite, "pcgc_register_step: the pose and the centre must be finite");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_register_workspace_bytes(res, nq), "pcgc_register_step: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const OffgridBuffers b = offgrid_layout(res, nq, workspace);               // as pcgc_register_prepare left it
+  const Target t{Cells{h, ox, oy, oz, res}, b.r.bits, b.r.rank, b.start, q};
+  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + offgrid_bytes(res, nq));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.bad + 1, 0, sizeof(int), s));
+  const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
+  hipLaunchKernelGGL(register_step_kernel, dim3(blocks), dim3(256), 0, s, p, np, t, normals_q, pose, max_dist * max_dist, partial, best,
+                     n_ties, b.bad + 1);
+  hipLaunchKernelGGL(register_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, b.bad, out45);
+  return launch_ok("registration step kernels");
 }
 
 }  // extern "C"
