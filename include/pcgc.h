@@ -315,6 +315,47 @@ int pcgc_register_step(const float* p, int64_t np, const float* q, int64_t nq, c
                        double* out45, double* best, int32_t* n_ties, void* workspace, size_t workspace_bytes,
                        pcgc_stream_t stream);
 
+/* Global alignment: a start for the ICP above from any relative pose, by descriptor matching and RANSAC (pcgcv1_amd/
+ * register.py draws and solves on the host; tests/_global_ref.py is the rule in numpy).  Four device stages,
+ * every one with integer outputs that do not depend on the order of the work: the same input gives the same bytes, and
+ * they equal numpy's.  The float64 arithmetic is IEEE, one operation per step in the order written.  Coordinates are in
+ * grid units.  The keypoints K (float32 [n,3], n <= 2^24) are bucketed into the cells (h, ox, oy, oz, res) of pcgc_offgrid_*
+ * above and passed SORTED ascending by cell key; normals float32 [n,3] in that order, unit or zero, taken as given.  A normal
+ * is usable when its components are finite and not all zero.  d2 is that of pcgc_offgrid_*.
+ *   N(i) = every j != i with 0 < d2(K_i, K_j) <= radius * radius and both normals usable; empty when normal i is not.
+ *   pcgc_feature_pairs: per i and j in N(i), with d = double(K_i) - double(K_j), len = sqrt(d2), u = (dx/len, dy/len, dz/len),
+ *       f1 = |(ni.x u.x + ni.y u.y) + ni.z u.z|,  f2 = the same with nj,  f3 = |(ni.x nj.x + ni.y nj.y) + ni.z nj.z|
+ *       bin(f) = min(10, (int)floor(f * 11.0))
+ *     S (uint32 [n,33]) = the counts of bin(f1) in [0,11), of bin(f2) in [11,22), of bin(f3) in [22,33); k (int32 [n]) = |N(i)|.
+ *   pcgc_feature_combine: from S and k (as given), in uint64,
+ *       G_i[b] = k_i S_i[b] + sum over N(i) of S_j[b],   T_i = k_i k_i + sum over N(i) of k_j
+ *       feat_i[b] = (G_i[b] * 255 + T_i / 2) / T_i, integer division, 0 when T_i = 0 (at most 255 for S, k of pcgc_feature_pairs)
+ *     feat uint8 [n,36] = the 33 bins and three zero bytes; valid uint8 [n] = (T_i > 0).
+ *   Both build the cells in the workspace themselves.  radius must be positive and below 4 h.  Keypoints that are not
+ *   sorted or leave the grid, or a NaN coordinate, touch no memory out of bounds and raise the workspace's flag: then k is
+ *   -1 everywhere (pairs), valid 255 everywhere (combine).  The next call is not affected.
+ *   pcgc_feature_match: rows uint8 [n,36] / [m,36], 4-byte aligned, and their valid bytes.  Per source row with a non-zero
+ *     valid byte, over the target rows with one: dist (uint32) = the least sum over the 33 bins of (a - b)^2, j (int32) the
+ *     lowest target row that reaches it.  j = -1 and dist = 0xFFFFFFFF for every other source row, and when no target row
+ *     is valid.  The three bytes behind the bins are not read as data.  workspace: 8 n bytes, 8-byte aligned.
+ *   pcgc_ransac_score: poses double [K,12] (device; R row-major, then t), P, Q float32 [C,3].  counts (int32 [K]) = the
+ *     number of c with d2(p', Q_c) <= dist * dist, p' the moved point of pcgc_register_step, its float32 rounding included.
+ *     A pose with a NaN counts none.
+ *   All reject a null pointer, a size that is not positive or too large, bad cells, a radius or dist that is not finite
+ *   and positive, and a workspace smaller than the sizer's figure (0 for a bad size), before any memory is touched. */
+size_t pcgc_feature_workspace_bytes(int res, int64_t n);
+int pcgc_feature_pairs(const float* keypoints, const float* normals, int64_t n, double h, int ox, int oy, int oz, int res,
+                       double radius, uint32_t* S, int32_t* k, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_feature_combine(const float* keypoints, const float* normals, int64_t n, double h, int ox, int oy, int oz, int res,
+                         double radius, const uint32_t* S, const int32_t* k, uint8_t* feat, uint8_t* valid, void* workspace,
+                         size_t workspace_bytes, pcgc_stream_t stream);
+size_t pcgc_feature_match_workspace_bytes(int64_t n);
+int pcgc_feature_match(const uint8_t* source_rows, const uint8_t* source_valid, int64_t n, const uint8_t* target_rows,
+                       const uint8_t* target_valid, int64_t m, int32_t* j, uint32_t* dist, void* workspace,
+                       size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_ransac_score(const double* poses, int64_t n_poses, const float* P, const float* Q, int64_t C, double dist,
+                      int32_t* counts, pcgc_stream_t stream);
+
 /* ---- Rendering (pcgcv1_amd/render.py; DESIGN.md "Rendering"; tests/_render_ref.py is the rule in numpy) ---------------
  * A cloud to an image: demo.ipynb:586,596,962,972 (o3d.visualization.draw_geometries), on a node without a display.
  * Orthographic, all integers after one rounding, so an image is defined bit for bit.

@@ -88,6 +88,14 @@ HIP_API = {
     "pcgc_register_prepare": (c_int, [c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "pcgc_register_step": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_double, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                    ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_feature_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_feature_pairs": (c_int, [c_vp, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp, c_vp,
+                                   c_sz, c_vp]),
+    "pcgc_feature_combine": (c_int, [c_vp, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_feature_match_workspace_bytes": (c_sz, [c_i64]),
+    "pcgc_feature_match": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_ransac_score": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp]),
     "pcgc_render_workspace_bytes": (c_sz, [c_int, c_int]),
     "pcgc_render_splat": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_int, c_int,
                                   c_int, c_vp, c_sz, c_vp]),

@@ -39,6 +39,7 @@ HIP_SOURCES = {
     "pointnums.hip": ["-ffp-contract=off"],
     "color.hip": ["-ffp-contract=off"],
     "offgrid.hip": ["-ffp-contract=off"],
+    "global.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "ingest.hip": ["-ffp-contract=off"],
     "clean.hip": [],

@@ -4,6 +4,7 @@ of pcgcv1_amd/ingest.py.
     python -m pcgcv1_amd.register --input a.ply b.ply c.ply --output merged_vox10.ply --bits 10     # or --voxel_size S
                                   [--metric plane|point] [--max_dist 4,2,1] [--iters 50] [--tol 1e-3] [--estimate_normals]
                                   [--init poses.json] [--clean SPEC] [--min_fitness 0.3]
+                                  [--global_init [--feature_voxel 1] [--feature_radius 8] [--corr_dist 2] [--draws 100000] [--seed 0]]
 
 writes the voxelised ply and merged_vox10.frame as pcgcv1_amd.ingest would for the union of the aligned scans, and
 merged_vox10.poses.json: per input the 4x4 pose in the scan's own units and what the loop reports.
@@ -13,8 +14,15 @@ units, neighbouring surface points about 1 apart.  One step (csrc/offgrid.hip) m
 every tied nearest neighbour in the target with the off-grid search, keeps the points within max_dist and reduces them to 45
 float64 sums in a fixed order.  The solve is numpy float64 on the host: Kabsch for point-to-point, the 6x6 normal equations
 with an exact Rodrigues rotation for point-to-plane.  max_dist is a coarse-to-fine schedule: with one wide gate the points
-beyond the overlap pair with the target's rim and pull the pose.  A start further off than the first gate bridges is the
-caller's job (init): there is no global alignment here.
+beyond the overlap pair with the target's rim and pull the pose.  A start further off than the first gate bridges comes from
+init, or from the global alignment below (global_init / --global_init).
+
+Global alignment (include/pcgc.h, pcgc_feature_* and pcgc_ransac_score; tests/_global_ref.py restates it in
+numpy; csrc/global.hip).  Each cloud is reduced to one keypoint per cell of feature_voxel with a unit normal; every keypoint
+gets a sign-invariant integer descriptor of 33 bytes from the keypoints within `radius`; every source keypoint is paired with
+the target keypoint of the nearest descriptor.  On the host, seeded triples of those pairs whose triangles agree in size are
+solved by Kabsch (numpy float64), the device counts per pose the pairs it brings within corr_dist, and the pose with the most,
+solved again over its inliers, is the start ICP refines.  Every device stage gives integers that equal numpy's.
 """
 import argparse
 import json
@@ -29,6 +37,16 @@ N_SUMS = 45
 MIN_PAIRS = {"point": 3, "plane": 6}
 COND_LIMIT = 1e12
 DEFAULT_MAX_DIST = (4.0, 2.0, 1.0)
+# global alignment, grid units (neighbouring surface points about 1 apart): keypoints are the voxels ICP sees; a radius of 8
+# holds about 200 of them on a surface, enough for an 11-bin histogram and small enough to be local; a pair counts as an
+# inlier within 2, so the pose it votes for lands inside ICP's first gate of 4; triangles with a side under 6 fix a rotation
+# badly at that tolerance; 20 inliers are far more than the three a triple explains by itself
+DEFAULT_FEATURE_VOXEL, DEFAULT_FEATURE_RADIUS, DEFAULT_CORR_DIST, DEFAULT_MIN_EDGE, DEFAULT_MIN_INLIERS = 1.0, 8.0, 2.0, 6.0, 20
+DEFAULT_DRAWS = 100000
+DRAW_BATCH = 16384           # triples per call of the generator: part of the rule, the stream of draws depends on it
+EDGE_RATIO = 0.9
+FEATURE_BINS, FEATURE_ROW = 33, 36
+FEATURE_MAX_CELLS, FEATURE_MAX_EDGE = 1024, 2.0 ** 20
 
 
 # ---------------------------------------------------------------------------- the solves (host, float64)
@@ -252,6 +270,285 @@ def icp(source, target, target_normals=None, metric="plane", max_dist=DEFAULT_MA
             "plane_rmse": (math.sqrt(S[44] / n_used) if n_used else float("nan")) if plane else None}
 
 
+# ---------------------------------------------------------------------------- global alignment: the device stages
+def keypoints(points, normals, feature_voxel):
+    """points float32 [n,3] in grid units, normals [n,3] or None -> (keypoints float32 [m,3], unit normals float32 [m,3]):
+    one keypoint per occupied cell of edge feature_voxel (ingest's frame, quantise and merge), at the cell's position, rows
+    in ascending cell key; its normal is the merged normal, or without normals metrics.estimate_normals of those cells"""
+    from . import ingest, metrics
+    p = _float32_cloud(points, "global_align").astype(np.float64)
+    if not (np.isfinite(feature_voxel) and feature_voxel > 0):
+        raise ValueError("global_align: feature_voxel must be positive (got %r)" % (feature_voxel,))
+    try:
+        frame = ingest.fit_frame(p, voxel_size=float(feature_voxel))
+    except ValueError as e:
+        raise ValueError("global_align: %s" % e)
+    _, keys = ingest.quantize(p, frame)
+    vox, _, _, nrm = ingest.merge(keys, frame.bits, None, None if normals is None else np.asarray(normals, np.float32).reshape(-1, 3))
+    if normals is None:
+        nrm = metrics.estimate_normals(vox)
+    return ingest.apply_frame(vox, frame).astype(np.float32), _unit_normals(nrm, len(vox))
+
+
+def feature_cells(kp, radius):
+    """-> (h, ox, oy, oz, res): the cells pcgc_feature_* search keypoints in: the smallest power of two h >= max(1, radius)
+    with at most 1024 cells per axis between the extremes of the finite rows"""
+    p = np.asarray(kp, np.float64).reshape(-1, 3)
+    p = p[np.isfinite(p).all(1)]
+    if not len(p) or not (np.isfinite(radius) and radius > 0):
+        raise ValueError("global_align: the keypoints need a finite row and radius must be positive (got %r)" % (radius,))
+    lo, hi = p.min(0), p.max(0)
+    h = 1.0
+    while h < radius or int((np.floor(hi / h) - np.floor(lo / h)).max()) + 1 > FEATURE_MAX_CELLS:
+        h *= 2.0
+        if h > FEATURE_MAX_EDGE:
+            raise ValueError("global_align: keypoints of extent %g with radius %g need cells wider than 2^20" % (float((hi - lo).max()), radius))
+    origin = np.floor(lo / h)
+    if float(np.abs(np.stack([origin, np.floor(hi / h)])).max()) >= 2.0 ** 28:
+        raise ValueError("global_align: coordinate / cell edge reaches 2^28 (cell edge %g)" % h)
+    return (h, int(origin[0]), int(origin[1]), int(origin[2]), int((np.floor(hi / h) - origin).max()) + 1)
+
+
+class _FeatureCloud(object):
+    """keypoints and normals on the device, sorted by the cell key pcgc_feature_* want; rows come back in the caller's order"""
+
+    def __init__(self, kp, normals, radius, cells=None):
+        import torch
+        self.dev = _lib.require_gpu()
+        kp = _float32_cloud(kp, "keypoint")
+        nrm = np.ascontiguousarray(np.asarray(normals), np.float32).reshape(-1, 3)
+        if len(nrm) != len(kp):
+            raise ValueError("global_align: %d normals for %d keypoints" % (len(nrm), len(kp)))
+        self.n, self.radius = len(kp), float(radius)
+        self.cells = feature_cells(kp, radius) if cells is None else cells
+        h, ox, oy, oz, res = self.cells
+        with np.errstate(invalid="ignore"):
+            cell = np.floor(kp.astype(np.float64) / h) - np.array([ox, oy, oz], np.float64)
+        inside = np.isfinite(cell).all(1) & (cell >= 0).all(1) & (cell < res).all(1)
+        c = np.where(inside[:, None], cell, 0.0).astype(np.int64)
+        self.order = np.argsort(np.where(inside, (c[:, 0] * res + c[:, 1]) * res + c[:, 2], -1), kind="stable")
+        self.kp = torch.from_numpy(kp[self.order]).to(self.dev)
+        self.normals = torch.from_numpy(nrm[self.order]).to(self.dev)
+        self.ws = torch.empty(max(1, int(_lib.hip().pcgc_feature_workspace_bytes(res, self.n))), dtype=torch.uint8, device=self.dev)
+
+    def back(self, t):
+        out = np.empty_like(t.cpu().numpy())
+        out[self.order] = t.cpu().numpy()
+        return out
+
+    def pairs(self):
+        import torch
+        S = torch.empty((self.n, FEATURE_BINS), dtype=torch.int32, device=self.dev)          # uint32 on the device
+        k = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+        _lib.check(_lib.hip().pcgc_feature_pairs(_lib.dptr(self.kp), _lib.dptr(self.normals), self.n, *self.cells, self.radius, _lib.dptr(S),
+                                                 _lib.dptr(k), _lib.dptr(self.ws), self.ws.numel(), _lib.stream()), "pcgc_feature_pairs")
+        if int(k.min().item()) < 0:
+            raise RuntimeError("pcgc_feature_pairs: a keypoint coordinate is not finite or leaves the cells, or the keypoints are not "
+                               "sorted by cell (include/pcgc.h)")
+        return S, k
+
+    def combine(self, S, k):
+        import torch
+        feat = torch.empty((self.n, FEATURE_ROW), dtype=torch.uint8, device=self.dev)
+        valid = torch.empty(self.n, dtype=torch.uint8, device=self.dev)
+        _lib.check(_lib.hip().pcgc_feature_combine(_lib.dptr(self.kp), _lib.dptr(self.normals), self.n, *self.cells, self.radius, _lib.dptr(S),
+                                                   _lib.dptr(k), _lib.dptr(feat), _lib.dptr(valid), _lib.dptr(self.ws), self.ws.numel(),
+                                                   _lib.stream()), "pcgc_feature_combine")
+        if int(valid.max().item()) > 1:
+            raise RuntimeError("pcgc_feature_combine: a keypoint coordinate is not finite or leaves the cells, or the keypoints are "
+                               "not sorted by cell (include/pcgc.h)")
+        return feat, valid
+
+
+def feature_pairs(kp, normals, radius, cells=None):
+    """stage 1 (pcgc_feature_pairs) -> (S uint32 [n,33], k int32 [n]) in the caller's order.  RuntimeError for a NaN keypoint."""
+    c = _FeatureCloud(kp, normals, radius, cells)
+    S, k = c.pairs()
+    return c.back(S).view(np.uint32), c.back(k)
+
+
+def feature_combine(kp, normals, radius, S, k, cells=None):
+    """stage 2 (pcgc_feature_combine) from S uint32 [n,33] and k int32 [n] -> (feat uint8 [n,36], valid bool [n])"""
+    import torch
+    c = _FeatureCloud(kp, normals, radius, cells)
+    S = np.ascontiguousarray(np.asarray(S, np.uint32).reshape(c.n, FEATURE_BINS)[c.order]).view(np.int32)
+    k = np.ascontiguousarray(np.asarray(k, np.int32).reshape(c.n)[c.order])
+    feat, valid = c.combine(torch.from_numpy(S).to(c.dev), torch.from_numpy(k).to(c.dev))
+    return c.back(feat), c.back(valid).astype(bool)
+
+
+def features(kp, normals, radius):
+    """keypoints float32 [n,3] and their unit normals -> (descriptors uint8 [n,36], valid bool [n]): stages 1 and 2"""
+    c = _FeatureCloud(kp, normals, radius)
+    feat, valid = c.combine(*c.pairs())
+    return c.back(feat), c.back(valid).astype(bool)
+
+
+def match_features(fs, vs, ft, vt):
+    """stage 3 (pcgc_feature_match): per valid source row the valid target row of the nearest descriptor -> (j int32 [n],
+    dist uint32 [n]); -1 and 0xFFFFFFFF for an invalid source row"""
+    import torch
+    dev = _lib.require_gpu()
+    rows = [np.ascontiguousarray(np.asarray(f), np.uint8).reshape(-1, FEATURE_ROW) for f in (fs, ft)]
+    valid = [np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(-1) for v in (vs, vt)]
+    if not len(rows[0]) or not len(rows[1]) or len(valid[0]) != len(rows[0]) or len(valid[1]) != len(rows[1]):
+        raise ValueError("match_features: needs source and target rows, each with its valid flags")
+    fs_d, ft_d, vs_d, vt_d = (torch.from_numpy(a).to(dev) for a in (rows[0], rows[1], valid[0], valid[1]))
+    n, m = len(rows[0]), len(rows[1])
+    lib = _lib.hip()
+    ws = torch.empty(int(lib.pcgc_feature_match_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    j = torch.empty(n, dtype=torch.int32, device=dev)
+    dist = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(lib.pcgc_feature_match(_lib.dptr(fs_d), _lib.dptr(vs_d), n, _lib.dptr(ft_d), _lib.dptr(vt_d), m, _lib.dptr(j), _lib.dptr(dist),
+                                      _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_feature_match")
+    return j.cpu().numpy(), dist.cpu().numpy().view(np.uint32)
+
+
+class Scorer(object):
+    """stage 4 (pcgc_ransac_score): correspondences P -> Q (float32 [C,3]) on the device, and the inlier counts of poses"""
+
+    def __init__(self, P, Q, dist):
+        import torch
+        self.dev = _lib.require_gpu()
+        P, Q = _float32_cloud(P, "correspondence"), _float32_cloud(Q, "correspondence")
+        if len(P) != len(Q):
+            raise ValueError("global_align: %d source and %d target correspondences" % (len(P), len(Q)))
+        self.P, self.Q, self.C, self.dist = torch.from_numpy(P).to(self.dev), torch.from_numpy(Q).to(self.dev), len(P), float(dist)
+
+    def __call__(self, poses):
+        """poses float64 [K,12], R row-major then t -> int32 [K]"""
+        import torch
+        poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12))
+        poses_d = torch.from_numpy(poses).to(self.dev)
+        counts = torch.empty(len(poses), dtype=torch.int32, device=self.dev)
+        _lib.check(_lib.hip().pcgc_ransac_score(_lib.dptr(poses_d), len(poses), _lib.dptr(self.P), _lib.dptr(self.Q), self.C, self.dist,
+                                                _lib.dptr(counts), _lib.stream()), "pcgc_ransac_score")
+        return counts.cpu().numpy()
+
+
+def score_poses(poses, P, Q, dist):
+    return Scorer(P, Q, dist)(poses)
+
+
+# ---------------------------------------------------------------------------- global alignment: the draws and their solve (host, float64)
+def _edges(x, tri):
+    """float64 [K,3]: the lengths of the edges 0-1, 1-2, 2-0 of the triangles tri [K,3] of the points x (float64 [C,3])"""
+    a = x[tri]
+    d = a - a[:, (1, 2, 0), :]
+    return np.sqrt((d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2])
+
+
+def keep_triples(tri, P, Q, min_edge):
+    """bool [K]: distinct indices, every source edge at least min_edge, every source edge and its target edge within a factor
+    of 0.9 of each other.  P, Q float64 [C,3]."""
+    distinct = (tri[:, 0] != tri[:, 1]) & (tri[:, 1] != tri[:, 2]) & (tri[:, 2] != tri[:, 0])
+    es, et = _edges(P, tri), _edges(Q, tri)
+    return distinct & (es >= float(min_edge)).all(1) & (et >= EDGE_RATIO * es).all(1) & (es >= EDGE_RATIO * et).all(1)
+
+
+def kabsch(a, b):
+    """a, b float64 [K,M,3] -> (R [K,3,3], t [K,3]) with b ~ R a + t: solve_point's rule (the determinant fix included), batched"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    m = float(a.shape[1])
+    mu_a, mu_b = a.sum(1) / m, b.sum(1) / m
+    H = np.einsum("kmi,kmj->kij", a - mu_a[:, None, :], b - mu_b[:, None, :])
+    U, _, Vt = np.linalg.svd(H)
+    V, Ut = np.swapaxes(Vt, 1, 2), np.swapaxes(U, 1, 2)
+    D = np.zeros_like(H)
+    D[:, 0, 0] = D[:, 1, 1] = 1.0
+    D[:, 2, 2] = np.sign(np.linalg.det(V @ Ut))
+    R = V @ D @ Ut
+    return R, mu_b - np.einsum("kij,kj->ki", R, mu_a)
+
+
+def draw_hypotheses(P, Q, min_edge, draws, seed):
+    """The seeded triples of correspondence indices, DRAW_BATCH per call of np.random.default_rng(seed).integers, and the
+    poses of the kept ones -> (poses float64 [K,12], draw index int64 [K]) in draw order; a pose that is not finite is dropped"""
+    rng = np.random.default_rng(seed)
+    P64, Q64 = np.asarray(P, np.float32).astype(np.float64), np.asarray(Q, np.float32).astype(np.float64)
+    poses, index = [], []
+    for d0 in range(0, int(draws), DRAW_BATCH):
+        tri = rng.integers(0, len(P64), size=(min(DRAW_BATCH, int(draws) - d0), 3))
+        kept = np.nonzero(keep_triples(tri, P64, Q64, min_edge))[0]
+        if not len(kept):
+            continue
+        R, t = kabsch(P64[tri[kept]], Q64[tri[kept]])
+        pose = np.concatenate([R.reshape(-1, 9), t], 1)
+        fine = np.isfinite(pose).all(1)
+        poses.append(pose[fine])
+        index.append(kept[fine] + d0)
+    if not poses:
+        return np.zeros((0, 12)), np.zeros(0, np.int64)
+    return np.concatenate(poses), np.concatenate(index)
+
+
+def inlier_mask(pose, P, Q, dist):
+    """pcgc_ransac_score's rule for one pose on the host -> bool [C]"""
+    pose = np.asarray(pose, np.float64).reshape(12)
+    p = np.asarray(P, np.float32).astype(np.float64)
+    q = np.asarray(Q, np.float32).astype(np.float64)
+    d = []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(3):
+            moved = (((pose[3 * r] * p[:, 0] + pose[3 * r + 1] * p[:, 1]) + pose[3 * r + 2] * p[:, 2]) + pose[9 + r]).astype(np.float32)
+            d.append(moved.astype(np.float64) - q[:, r])
+        return ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) <= float(dist) * float(dist)
+
+
+def ransac(P, Q, corr_dist=DEFAULT_CORR_DIST, min_edge=DEFAULT_MIN_EDGE, draws=DEFAULT_DRAWS, seed=0, min_inliers=DEFAULT_MIN_INLIERS,
+           scorer=None):
+    """correspondences P -> Q (float32 [C,3]) -> dict R, t (Q ~ R P + t), inliers, correspondences, hypotheses, draw, draws.
+    The pose with the most inliers among the kept draws (the lowest draw among equals), solved once more over its inliers.
+    scorer: poses [K,12] -> counts, in place of the device's Scorer (the tests of the host rule run without a device)."""
+    if not (np.isfinite(corr_dist) and corr_dist > 0 and np.isfinite(min_edge) and min_edge >= 0 and int(draws) >= 1):
+        raise ValueError("global_align: corr_dist must be positive, min_edge not negative, draws at least 1 (got %r, %r, %r)"
+                         % (corr_dist, min_edge, draws))
+    if len(P) < 3:
+        raise ValueError("global_align: fewer than 3 valid correspondences (%d): the clouds have too few keypoints with neighbours within "
+                         "the feature radius; use a smaller feature_voxel or a larger radius" % len(P))
+    poses, draw = draw_hypotheses(P, Q, min_edge, draws, seed)
+    if not len(poses):
+        raise ValueError("global_align: no triple kept: none of %d draws among %d correspondences has three distinct pairs with source "
+                         "edges of at least %g that match their target edges within a factor of %g; lower min_edge or draw more"
+                         % (int(draws), len(P), min_edge, EDGE_RATIO))
+    scorer = Scorer(P, Q, corr_dist) if scorer is None else scorer
+    counts = np.asarray(scorer(poses))
+    w = int(np.argmax(counts))                                 # the first of equals: the lowest draw
+    inl = inlier_mask(poses[w], P, Q, corr_dist)
+    P64, Q64 = np.asarray(P, np.float32).astype(np.float64), np.asarray(Q, np.float32).astype(np.float64)
+    R, t = kabsch(P64[inl][None], Q64[inl][None])
+    refined = np.concatenate([R.reshape(9), t.reshape(3)])
+    n_in = int(scorer(refined[None])[0]) if np.isfinite(refined).all() else 0
+    if n_in < min_inliers:
+        raise ValueError("global_align: the best of %d poses has %d inliers of %d correspondences, below min_inliers = %d: the scans may "
+                         "not overlap, or their shape gives the descriptors nothing to hold on to"
+                         % (len(poses), n_in, len(P), min_inliers))
+    return {"R": R[0], "t": t[0], "inliers": n_in, "correspondences": len(P), "hypotheses": len(poses), "draw": int(draw[w]),
+            "draws": int(draws), "raw_inliers": int(counts[w])}
+
+
+def correspondences(source_kp, fs, vs, target_kp, ft, vt):
+    """-> (P float32 [C,3], Q float32 [C,3], source rows, target rows): every valid source keypoint and its match"""
+    j, _ = match_features(fs, vs, ft, vt)
+    rows = np.nonzero(j >= 0)[0]
+    return np.asarray(source_kp, np.float32)[rows], np.asarray(target_kp, np.float32)[j[rows]], rows, j[rows].astype(np.int64)
+
+
+def global_align(source, target, source_normals=None, target_normals=None, feature_voxel=DEFAULT_FEATURE_VOXEL,
+                 radius=DEFAULT_FEATURE_RADIUS, corr_dist=DEFAULT_CORR_DIST, min_edge=DEFAULT_MIN_EDGE, draws=DEFAULT_DRAWS, seed=0,
+                 min_inliers=DEFAULT_MIN_INLIERS):
+    """A start for icp from any relative pose.  source, target float32 [n,3] / [m,3] in grid units, their normals (of either
+    sign) or None: estimated on the keypoint cells -> dict: R, t (target ~ R source + t), inliers, correspondences, hypotheses
+    (kept draws), draw (the winner's index) and draws.  The pose is coarse: within about corr_dist, which icp's first gate must
+    bridge.  ValueError: fewer than 3 valid correspondences, no triple kept, a winner below min_inliers."""
+    ks, ns = keypoints(source, source_normals, feature_voxel)
+    kt, nt = keypoints(target, target_normals, feature_voxel)
+    fs, vs = features(ks, ns, radius)
+    ft, vt = features(kt, nt, radius)
+    P, Q, _, _ = correspondences(ks, fs, vs, kt, ft, vt) if vt.any() and vs.any() else (ks[:0], kt[:0], None, None)
+    return ransac(P, Q, corr_dist, min_edge, draws, seed, min_inliers)
+
+
 # ---------------------------------------------------------------------------- several scans
 def to_grid(points, frame):
     """g = (p - origin) / step in float64, then float32: the grid units ICP runs in (may leave [0, R])"""
@@ -287,11 +584,13 @@ def _finite_scan(k, scan):
 
 
 def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=DEFAULT_MAX_DIST, iters=50, tol=1e-3, init=None,
-                   estimate_normals=False, clean=None, names=None):
+                   estimate_normals=False, clean=None, names=None, global_init=False, global_options=None):
     """scans: list of (points float64 [n,3] in the scanner's units, colors uint8 [n,3] | None, normals [n,3] | None).  Scan 0
     defines the coordinates; scan k >= 1 is registered against the union of scan 0 and the aligned scans before it, on the
     grid of the ingest.Frame fitted to that union with bits / voxel_size.  init: per scan None or (R, t) in scan units;
-    names: what to call the scans in an error.
+    names: what to call the scans in an error.  global_init: a scan k >= 1 without an init starts from global_align against
+    the union before it (global_options: its keyword arguments), normals a scan lacks estimated on its voxels; icp then runs
+    unchanged, and the scan's pose entry gains "global": inliers, correspondences, hypotheses, draw.
     -> dict: merged = ingest.voxelize_scan(union, ..., clean=clean) as it returns it, poses = per scan the icp result with
     R, t in scan units and "pose" the 4x4 matrix (scan 0: the identity), aligned = the union's (points, colors, normals)."""
     from . import ingest
@@ -314,10 +613,21 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
         if metric == "plane":
             tn = np.concatenate(nrms) if all(n is not None for n in nrms) else estimated_target_normals(target, frame)
         start = None if init is None or init[k] is None else pose_from_scan_units(init[k][0], init[k][1], frame)
+        coarse = None
         try:
+            if global_init and start is None:
+                # normals for the descriptors: the scans' own, else estimated on the voxels of the registration grid, as the
+                # plane metric's are (the keypoint cells may be finer than the points lie, and estimate nothing there)
+                given = tn if tn is not None else (np.concatenate(nrms) if all(n is not None for n in nrms) else
+                                                   estimated_target_normals(target, frame))
+                own = nrm if nrm is not None else estimated_target_normals(p, ingest.fit_frame(p, voxel_size=frame.step))
+                coarse = global_align(to_grid(p, frame), to_grid(target, frame), own, given, **(global_options or {}))
+                start = (coarse["R"], coarse["t"])
             r = icp(to_grid(p, frame), to_grid(target, frame), tn, metric, gates, iters, tol, start)
         except ValueError as e:
             raise ValueError("%s: %s" % (names[k] if names else "scan %d" % k, e))
+        if coarse is not None:
+            r["global"] = {key: coarse[key] for key in ("inliers", "correspondences", "hypotheses", "draw")}
         r["R"], r["t"] = pose_to_scan_units(r["R"], r["t"], frame)
         r["pose"] = pose_matrix(r["R"], r["t"])
         poses.append(r)
@@ -341,6 +651,9 @@ def write_poses(filename, names, poses):
                 "iterations": [int(i) for i in r["iterations"]], "converged": bool(r["converged"]), "fitness": float(r["fitness"]),
                 "rmse": float(r["rmse"]), "plane_rmse": None if r["plane_rmse"] is None else float(r["plane_rmse"])}
                for name, r in zip(names, poses)]
+    for e, r in zip(entries, poses):
+        if "global" in r:                                      # the coarse start the scan's icp began from (--global_init)
+            e["global"] = {key: int(v) for key, v in r["global"].items()}
     with open(filename, "w") as f:
         json.dump(entries, f, indent=1)
 
@@ -381,6 +694,24 @@ def parse_args(argv=None):
                     help="--metric=plane with scans that have no normals: estimate the target's on its voxels (radius 10, 20 neighbours)")
     ap.add_argument("--init", default=None, help="a poses.json with the start pose of every scan, scan units")
     ap.add_argument("--min_fitness", type=float, default=0.3, help="fail when less of a scan lies within the last gate")
+    ap.add_argument("--global_init", action="store_true",
+                    help="start every scan from a global alignment against the scans before it (descriptor matching and RANSAC), so "
+                         "that any relative pose will do; not with --init.  A scan without normals gets them estimated on its "
+                         "voxels.  The pose it finds is coarse, within about --corr_dist: the first gate of --max_dist must "
+                         "bridge that, as the default 4 does for the default 2")
+    ap.add_argument("--feature_voxel", type=float, default=DEFAULT_FEATURE_VOXEL,
+                    help="--global_init: edge of the cells that give one keypoint each, in voxels (default %(default)g: the voxels "
+                         "the registration itself sees)")
+    ap.add_argument("--feature_radius", type=float, default=DEFAULT_FEATURE_RADIUS,
+                    help="--global_init: the neighbourhood a descriptor describes, in voxels (default %(default)g: about 200 "
+                         "keypoints of a surface, enough to fill the histograms and still local)")
+    ap.add_argument("--corr_dist", type=float, default=DEFAULT_CORR_DIST,
+                    help="--global_init: a matched pair counts for a pose that brings it within this many voxels (default "
+                         "%(default)g: half the first gate, so the winner lands inside it)")
+    ap.add_argument("--draws", type=int, default=DEFAULT_DRAWS,
+                    help="--global_init: triples of matched pairs drawn (default %(default)d: about one in 70 passes the edge "
+                         "checks, and of those about one in 100 is near the truth)")
+    ap.add_argument("--seed", type=int, default=0, help="--global_init: seed of the draws (default %(default)d); the same seed, the same pose")
     ap.add_argument("--attributes", choices=("colors", "normals"), default="colors",
                     help="which attribute the ply carries when the union has both")
     from .clean import add_clean_argument, check_clean_argument
@@ -408,6 +739,13 @@ def parse_args(argv=None):
             if not _ply_has_normals(name):
                 ap.error("--metric=plane needs normals: %s has no nx ny nz properties (or cannot be read); pass --estimate_normals "
                          "to estimate them, or --metric=point" % name)
+    if args.global_init and args.init is not None:
+        ap.error("--global_init finds the start itself: not together with --init")
+    for name in ("feature_voxel", "feature_radius", "corr_dist"):
+        if not (np.isfinite(getattr(args, name)) and getattr(args, name) > 0):
+            ap.error("--%s must be positive (got %r)" % (name, getattr(args, name)))
+    if args.draws < 1 or args.seed < 0:
+        ap.error("--draws must be at least 1 and --seed not negative")
     if args.init is not None:
         try:
             args.init_poses = read_poses(args.init)
@@ -432,12 +770,18 @@ def main(argv=None):
     if args.init is not None:
         init = [(e["pose"][:3, :3], e["pose"][:3, 3]) for e in args.init_poses]
     try:
+        options = {"feature_voxel": args.feature_voxel, "radius": args.feature_radius, "corr_dist": args.corr_dist, "draws": args.draws,
+                   "seed": args.seed}
         out = register_scans(scans, args.bits, args.voxel_size, args.metric, args.max_dist, args.iters, args.tol, init,
-                             args.estimate_normals, args.clean, names=args.input)
+                             args.estimate_normals, args.clean, names=args.input, global_init=args.global_init,
+                             global_options=options)
     except ValueError as e:
         raise SystemExit("register: %s" % e)
     failed = []
     for name, r in list(zip(args.input, out["poses"]))[1:]:
+        if "global" in r:
+            print("register: {}: global start from draw {} of {} kept, {} inliers of {} matches".format(
+                name, r["global"]["draw"], r["global"]["hypotheses"], r["global"]["inliers"], r["global"]["correspondences"]))
         print(summary_line(name, r))
         if not r["converged"]:
             failed.append("%s did not converge within %d steps per stage (steps %s)" % (name, args.iters, r["iterations"]))
