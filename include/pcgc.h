@@ -665,6 +665,25 @@ size_t pcgc_clean_workspace_bytes(int bits, int64_t n);
 int pcgc_clean_neighbors(const int32_t* points, int64_t n, int bits, int k, int radius, int64_t* S, int32_t* cnt,
                          void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- islands of a scan: connected components (pcgcv1_amd/clean.py; tests/_components_ref.py is the rule in
+ * numpy) ----
+ * points int32 [n,3], distinct, on the grid of res = 2^bits cells per axis, 1 <= bits <= 12; the gap G, 1 <= G <= 8.  Two
+ * voxels p != q are linked when max(|dx|, |dy|, |dz|) <= G (G = 1: 26-connectivity); the window is clipped to the grid and
+ * nothing wraps from the end of a row, a plane or the grid into the next.  The components are the classes of the transitive
+ * closure of the link.
+ *   label int64 [n]: the smallest linear key (x * res + y) * res + z over p's component, so ascending labels follow
+ *     np.unique's order;
+ *   size  int32 [n]: the number of voxels of p's component (may be NULL);
+ *   n_components int64 [1]: the number of distinct labels (may be NULL).
+ * All integer, independent of the order of the rows and of the threads; two calls give the same bytes.  A point outside
+ * the grid sets no bit, belongs to no component, is not counted and gets label = -1, size = 0.  A bad argument returns an
+ * error before any memory is touched.  1 <= n < 2^31.  The number of launches is fixed and nothing is read back.
+ * workspace: pcgc_clean_components_workspace_bytes(bits, n) (0 for a bad argument): the bit set and its rank table over
+ * res^3 cells, then 16 bytes per point. */
+size_t pcgc_clean_components_workspace_bytes(int bits, int64_t n);
+int pcgc_clean_components(const int32_t* points, int64_t n, int bits, int gap, int64_t* label, int32_t* size,
+                          int64_t* n_components, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

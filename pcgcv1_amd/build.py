@@ -43,6 +43,7 @@ HIP_SOURCES = {
     "render.hip": ["-ffp-contract=off"],
     "ingest.hip": ["-ffp-contract=off"],
     "clean.hip": [],
+    "components.hip": [],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

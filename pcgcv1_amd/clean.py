@@ -14,6 +14,19 @@ pcgc_clean_neighbors; tests/_clean_ref.py restates it in numpy),
 
 The statistic runs in csrc/clean.hip; mean and std are numpy's float64 reductions over the int64 array read back from the
 device, so the mask is exact as well.
+
+Both judge a voxel by its own neighbourhood, so a small dense island (a clump of flying pixels, a piece of the turntable, a
+second object) passes them.  Connected components (include/pcgc.h, pcgc_clean_components; csrc/components.hip;
+tests/_components_ref.py): two voxels are linked when max(|dx|, |dy|, |dz|) <= G, the gap; label(p) = the smallest key
+(x * res + y) * res + z of p's component, size(p) = its number of voxels.
+
+  component:MIN[:G]  keep p when size(p) >= MIN                                      1 <= MIN <= 2^31 - 1, 1 <= G <= 8, G = 1 when left out
+  largest[:G]        keep p when label(p) is the label of the largest component, the smallest label among equals
+
+    python -m pcgcv1_amd.clean --input vox.ply --output vox_clean.ply --clean stat:20:2.0 --clean largest:2
+
+The command lines print one more line per such filter: the number of components and the sizes of the three largest, as that
+filter saw them.
 """
 import argparse
 import math
@@ -23,19 +36,21 @@ import numpy as np
 from . import _lib
 
 MAX_BITS, MAX_K, MAX_RADIUS, DEFAULT_RADIUS = 12, 64, 32, 8
+MAX_GAP, DEFAULT_GAP, MAX_MIN_SIZE = 8, 1, 2 ** 31 - 1
 
 
 class Spec(object):
-    """one --clean filter: kind 'radius' (radius, min_count) or 'stat' (k, ratio, radius); text = the spec as given"""
+    """one --clean filter: kind 'radius' (radius, min_count), 'stat' (k, ratio, radius), 'component' (min_count, gap) or 'largest'
+    (gap); text = the spec as given"""
 
-    def __init__(self, kind, radius, k=0, ratio=0.0, min_count=0, text=""):
-        self.kind, self.radius, self.k, self.ratio, self.min_count, self.text = kind, radius, k, ratio, min_count, text
+    def __init__(self, kind, radius=0, k=0, ratio=0.0, min_count=0, text="", gap=DEFAULT_GAP):
+        self.kind, self.radius, self.k, self.ratio, self.min_count, self.text, self.gap = kind, radius, k, ratio, min_count, text, gap
 
     def __eq__(self, other):
         return isinstance(other, Spec) and self._key() == other._key()
 
     def _key(self):
-        return self.kind, self.radius, self.k, self.ratio, self.min_count
+        return self.kind, self.radius, self.k, self.ratio, self.min_count, self.gap
 
     def __repr__(self):
         return "Spec(%r)" % self.text
@@ -52,7 +67,7 @@ def _int_field(text, name, value, lo, hi):
 
 
 def parse_spec(text):
-    """'radius:R:MIN' or 'stat:K:RATIO[:R]' -> Spec; ValueError names the field that is wrong"""
+    """'radius:R:MIN', 'stat:K:RATIO[:R]', 'component:MIN[:G]' or 'largest[:G]' -> Spec; ValueError names the field that is wrong"""
     if isinstance(text, Spec):
         return text
     fields = str(text).split(":")
@@ -74,7 +89,17 @@ def parse_spec(text):
             raise ValueError("--clean %s: RATIO = %r must be finite and >= 0" % (text, fields[2]))
         radius = _int_field(text, "R", fields[3], 1, MAX_RADIUS) if len(fields) == 4 else DEFAULT_RADIUS
         return Spec("stat", radius, k=k, ratio=ratio, text=str(text))
-    raise ValueError("--clean %s: the filter %r is neither 'radius' nor 'stat'" % (text, kind))
+    if kind == "component":
+        if len(fields) not in (2, 3):
+            raise ValueError("--clean %s: the component filter is component:MIN[:G] (%d fields given)" % (text, len(fields)))
+        min_count = _int_field(text, "MIN", fields[1], 1, MAX_MIN_SIZE)
+        gap = _int_field(text, "G", fields[2], 1, MAX_GAP) if len(fields) == 3 else DEFAULT_GAP
+        return Spec("component", min_count=min_count, gap=gap, text=str(text))
+    if kind == "largest":
+        if len(fields) not in (1, 2):
+            raise ValueError("--clean %s: the largest-component filter is largest[:G] (%d fields given)" % (text, len(fields)))
+        return Spec("largest", gap=_int_field(text, "G", fields[1], 1, MAX_GAP) if len(fields) == 2 else DEFAULT_GAP, text=str(text))
+    raise ValueError("--clean %s: the filter %r is neither 'radius', 'stat', 'component' nor 'largest'" % (text, kind))
 
 
 def parse_specs(specs):
@@ -132,6 +157,27 @@ def neighbor_statistics(points, bits, k, radius, want_counts=True):
     return S, cnt
 
 
+def components(points, bits, gap=DEFAULT_GAP):
+    """points int32 [n,3] (distinct voxels; numpy or a tensor) -> device tensors (label int64 [n], size int32 [n], n_components
+    int64 [1]): pcgc_clean_components.  A point outside the grid gets label -1 and size 0."""
+    import torch
+    p_d = _device_voxels(points)
+    n = int(p_d.shape[0])
+    if n == 0:
+        raise ValueError("clean: the cloud has no points")
+    lib = _lib.hip()
+    size = int(lib.pcgc_clean_components_workspace_bytes(bits, n))
+    if size == 0:
+        raise ValueError("clean: bits = %r outside 1..%d, or %d points too many" % (bits, MAX_BITS, n))
+    ws = torch.empty(size, dtype=torch.uint8, device=p_d.device)
+    label = torch.empty(n, dtype=torch.int64, device=p_d.device)
+    sizes = torch.empty(n, dtype=torch.int32, device=p_d.device)
+    n_components = torch.empty(1, dtype=torch.int64, device=p_d.device)
+    _lib.check(lib.pcgc_clean_components(_lib.dptr(p_d), n, bits, gap, _lib.dptr(label), _lib.dptr(sizes), _lib.dptr(n_components),
+                                         _lib.dptr(ws), ws.numel(), _lib.stream()), "pcgc_clean_components")
+    return label, sizes, n_components
+
+
 def _download(t):
     """a device vector to the host through page-locked memory, as ingest.merge reads its rows back"""
     import torch
@@ -141,38 +187,54 @@ def _download(t):
     return host.numpy()
 
 
-def keep_mask(points, bits, spec):
-    """-> host bool [n]: the voxels one filter keeps"""
+def components_line(spec, label, size):
+    """components: largest:2 saw 28 components, the largest of 3002 125 5 voxels (label, size: host arrays, one row per voxel)"""
+    first = np.unique(label[label >= 0], return_index=True)[1]           # one row of every component
+    top = np.sort(size[label >= 0][first])[::-1][:3]
+    return "components: {} saw {} components, the largest of {} voxels".format(spec.text, len(first), " ".join(str(int(s)) for s in top))
+
+
+def keep_mask(points, bits, spec, report=None):
+    """-> host bool [n]: the voxels one filter keeps.  report (a list): a component filter appends its components_line"""
     spec = parse_spec(spec)
+    if spec.kind in ("component", "largest"):
+        label, size, _ = components(points, bits, spec.gap)
+        label, size = _download(label), _download(size)
+        if report is not None:
+            report.append(components_line(spec, label, size))
+        if spec.kind == "component":
+            return size >= spec.min_count
+        return label == label[size == size.max()].min()                  # the largest; the smallest label among equals
     if spec.kind == "radius":
         return _download(neighbor_statistics(points, bits, 0, spec.radius)[1]) >= spec.min_count
     S = _download(neighbor_statistics(points, bits, spec.k, spec.radius, want_counts=False)[0])
     return S <= threshold(S, spec.ratio)
 
 
-def keep_mask_all(points, bits, specs):
+def keep_mask_all(points, bits, specs, report=None):
     """-> host bool [n]: what the filters keep, applied in order, each on what the one before kept.  ValueError when nothing
-    would remain."""
+    would remain.  report: as keep_mask"""
     import torch
     specs = parse_specs(specs)
     p_d = _device_voxels(points)
     mask = None
     for spec in specs:
         if mask is None:
-            mask = keep_mask(p_d, bits, spec)
+            mask = keep_mask(p_d, bits, spec, report)
         else:
             alive = np.flatnonzero(mask)
-            mask[alive[~keep_mask(p_d[torch.from_numpy(alive).to(p_d.device)], bits, spec)]] = False
+            mask[alive[~keep_mask(p_d[torch.from_numpy(alive).to(p_d.device)], bits, spec, report)]] = False
         if not mask.any():
             raise ValueError("--clean %s removes every voxel that was left" % spec.text)
     return mask if mask is not None else np.ones(int(p_d.shape[0]), bool)
 
 
-def clean_cloud(points, colors, normals, counts, bits, specs):
+def clean_cloud(points, colors, normals, counts, bits, specs, report=None):
     """A voxelised cloud (points int32 [n,3], distinct; colors, normals, counts [n, ...] or None) through the filters in order
-    -> (points, colors, normals, counts, mask bool [n]), the kept rows in their order.  ValueError when nothing would remain."""
+    -> (points, colors, normals, counts, mask bool [n]), the kept rows in their order.  ValueError when nothing would remain.
+    report: as keep_mask"""
     points = np.asarray(points)
-    mask = keep_mask_all(points, bits, specs)
+    mask = keep_mask_all(points, bits, specs, report)
     pick = lambda a: None if a is None else np.asarray(a)[mask]
     return points[mask], pick(colors), pick(normals), pick(counts), mask
 
@@ -195,7 +257,9 @@ def add_clean_argument(ap):
     ap.add_argument("--clean", action="append", default=None, metavar="SPEC",
                     help="drop outlier voxels (pcgcv1_amd/clean.py): radius:R:MIN keeps a voxel with at least MIN occupied voxels within "
                          "R cells; stat:K:RATIO[:R] keeps one whose summed distance to its K nearest voxels within R (default 8) cells "
-                         "is at most mean + RATIO * std over the cloud.  Repeatable: applied in order")
+                         "is at most mean + RATIO * std over the cloud; component:MIN[:G] keeps a voxel whose connected component "
+                         "(voxels at most G cells apart per axis are linked, default 1) has at least MIN voxels; largest[:G] keeps the "
+                         "largest component.  Repeatable: applied in order")
 
 
 def check_clean_argument(ap, args):
@@ -231,7 +295,8 @@ def main(argv=None):
         points = scan.astype(np.int32)
         if len(np.unique(points, axis=0)) != len(points):
             raise ValueError("not a voxelised ply: a voxel holds several points (python -m pcgcv1_amd.ingest merges them)")
-        kept, colors, normals, _, mask = clean_cloud(points, colors, normals, None, bits_for(points), args.clean)
+        report = []
+        kept, colors, normals, _, mask = clean_cloud(points, colors, normals, None, bits_for(points), args.clean, report)
     except ValueError as e:
         raise SystemExit("clean: %s: %s" % (args.input, e))
     if colors is not None:
@@ -240,7 +305,7 @@ def main(argv=None):
         write_ply_normals(args.output, kept, normals)
     else:
         write_ply_data(args.output, kept)
-    print(summary_line(args.clean, len(points), len(points) - len(kept), n_cubes(points), n_cubes(kept)))
+    print("\n".join([summary_line(args.clean, len(points), len(points) - len(kept), n_cubes(points), n_cubes(kept))] + report))
     print("wrote {}".format(args.output))
 
 

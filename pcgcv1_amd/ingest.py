@@ -213,8 +213,9 @@ def voxelize_scan_clean(points, colors=None, normals=None, bits=None, voxel_size
     return _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)[0]
 
 
-def _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean):
-    """-> (voxelize_scan_clean's values, the voxels of pass 1 as a device tensor: what the command lines report on)"""
+def _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean, report=None):
+    """-> (voxelize_scan_clean's values, the voxels of pass 1 as a device tensor: what the command lines report on); report:
+    as clean.keep_mask"""
     import torch
     from . import clean as cleaner
     specs = cleaner.parse_specs(clean)
@@ -224,7 +225,7 @@ def _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean):
     _, keys = quantize(p_d, frame)
     vox, _, _, _, n_out = merge_device(keys, frame.bits)
     vox = vox[:int(n_out.item())]
-    keep = torch.from_numpy(cleaner.keep_mask_all(vox, frame.bits, specs)).to(p_d.device)
+    keep = torch.from_numpy(cleaner.keep_mask_all(vox, frame.bits, specs, report)).to(p_d.device)
     # a row's voxel: the voxels are in ascending key, a dropped row (key -1) finds some voxel and is refused by its key
     res = 1 << frame.bits
     vox_keys = (vox[:, 0].long() * res + vox[:, 1].long()) * res + vox[:, 2].long()
@@ -291,20 +292,22 @@ def frame_path(ply_or_stem):
 
 # ---------------------------------------------------------------------------- command line
 def voxelize_scan_report(points, colors=None, normals=None, bits=None, voxel_size=None, clean=None):
-    """what the command lines run -> (voxelize_scan's six values, the 'clean: ...' summary line, or None without clean)"""
+    """what the command lines run -> (voxelize_scan's six values, the 'clean: ...' summary line, or None without clean; a
+    component filter adds a line of its own: clean.components_line)"""
     if not clean:
         return voxelize_scan(points, colors, normals, bits=bits, voxel_size=voxel_size), None
     from . import clean as cleaner
     import torch
-    out, vox = _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)
+    report = []
+    out, vox = _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean, report)
     cube = vox >> 6                                             # 64^3 cubes of pass 1: at most 6 bits per axis are left
     cubes = len(torch.unique((cube[:, 0] << 12) | (cube[:, 1] << 6) | cube[:, 2]))
-    return out[:6], cleaner.summary_line(clean, len(vox), out[6], cubes, cleaner.n_cubes(out[0]), out[7])
+    return out[:6], "\n".join([cleaner.summary_line(clean, len(vox), out[6], cubes, cleaner.n_cubes(out[0]), out[7])] + report)
 
 
 def ingest_file(filename, bits=None, voxel_size=None, clean=None):
     """load_ply_scan + voxelize_scan -> (points, colors | None, normals | None, counts, frame, n_dropped, n_input), and with
-    clean the 'clean: ...' summary line as an eighth value"""
+    clean the 'clean: ...' summary line (and a component filter's line below it) as an eighth value"""
     from .dataprocess.inout_points import load_ply_scan
     points, colors, normals = load_ply_scan(filename)
     if not len(points):

@@ -443,10 +443,13 @@ def _clean_input(args, src_points, src_colors, source):
     try:
         if len(np.unique(points, axis=0)) != len(points):
             raise ValueError("a voxel holds several points: --clean reads one point per voxel (--voxelize merges a raw scan)")
-        kept, _, _, _, mask = clean.clean_cloud(points, None, None, None, clean.bits_for(points), args.clean)
+        report = []
+        kept, _, _, _, mask = clean.clean_cloud(points, None, None, None, clean.bits_for(points), args.clean, report)
     except ValueError as e:
         raise SystemExit("%s: %s" % (args.input, e))
     print(clean.summary_line(args.clean, len(points), len(points) - len(kept), clean.n_cubes(points), clean.n_cubes(kept)))
+    for line in report:                           # a component filter's own line (clean.components_line)
+        print(line)
     print("Read and clean {}: {}s".format(args.input, round(time.time() - t0, 4)))
     if src_points is not None:
         src_points, src_colors = src_points[mask], src_colors[mask]
