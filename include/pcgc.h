@@ -684,6 +684,29 @@ size_t pcgc_clean_components_workspace_bytes(int bits, int64_t n);
 int pcgc_clean_components(const int32_t* points, int64_t n, int bits, int gap, int64_t* label, int32_t* size,
                           int64_t* n_components, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- the floor or table of a scan: plane scoring and selection (pcgcv1_amd/clean.py; tests/_plane_ref.py is
+ * the rule in numpy) ----
+ * points int32 [n,3] on the grid of res = 2^bits cells per axis, 1 <= bits <= 12.  A plane is five int64 numbers (a, b, c,
+ * d, T); a voxel (x, y, z) is an inlier when |a x + b y + c z - d| <= T in exact integers.  T < 0 matches nothing, and a
+ * point with a coordinate outside the grid is never an inlier.  The caller makes the planes (clean.draw_planes,
+ * clean.refit_plane): for a normal (a, b, c) through p0 and a distance of D2 half cells, d = (a, b, c) . p0 and T =
+ * isqrt(D2^2 (a^2 + b^2 + c^2)) / 2, which is exactly 2 |s| <= D2 |(a, b, c)|.
+ *   pcgc_plane_count: planes int64 [K,5], 1 <= K <= 65536 -> counts int32 [K], the number of inliers of every plane.  Meant
+ *     for draws, the cross products of three voxels: |a|, |b|, |c| < 2^26, T < 2^31, |s| < 2^40 at 12 bits; a plane whose
+ *     a, b, c do not fit int32 is counted through 64-bit products, chosen per plane on the device.
+ *   pcgc_plane_select: plane int64 [5] -> mask uint8 [n], 1 = inlier, and sums int64 [10] (may be NULL) over the inliers: N,
+ *     sum x, sum y, sum z, sum x^2, sum y^2, sum z^2, sum xy, sum xz, sum yz.  Meant for any plane up to the refit's:
+ *     |a|, |b|, |c| < 2^47, T < 2^54, |s| < 2^62.
+ * The arithmetic is modulo 2^64: beyond those bounds a count or a mask is unspecified and nothing out of bounds is touched.
+ * All integer, independent of the order of the rows and of the threads; two calls give the same bytes.  counts and sums are
+ * zeroed by the call itself.  A bad argument (a null pointer other than sums, n outside 1 .. 2^31 - 1, K outside 1 ..
+ * 65536, bits outside 1 .. 12) returns an error before any memory is touched.  No workspace, a fixed number of launches and
+ * nothing is read back. */
+int pcgc_plane_count(const int32_t* points, int64_t n, int bits, const int64_t* planes, int64_t K, int32_t* counts,
+                     pcgc_stream_t stream);
+int pcgc_plane_select(const int32_t* points, int64_t n, int bits, const int64_t* plane, uint8_t* mask, int64_t* sums,
+                      pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

@@ -76,6 +76,8 @@ HIP_API = {
     "pcgc_clean_neighbors": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_clean_components_workspace_bytes": (c_sz, [c_int, c_i64]),
     "pcgc_clean_components": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_plane_count": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp]),
+    "pcgc_plane_select": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "pcgc_d1_workspace_bytes": (c_sz, [c_int]),
     "pcgc_d1_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),

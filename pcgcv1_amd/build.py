@@ -44,6 +44,7 @@ HIP_SOURCES = {
     "ingest.hip": ["-ffp-contract=off"],
     "clean.hip": [],
     "components.hip": [],
+    "plane.hip": [],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

@@ -27,6 +27,29 @@ tests/_components_ref.py): two voxels are linked when max(|dx|, |dy|, |dz|) <= G
 
 The command lines print one more line per such filter: the number of components and the sizes of the three largest, as that
 filter saw them.
+
+`largest` drops a piece of the turntable only when that piece is already detached.  The surface a scanned object stands on is
+dense and touches the object, so all four filters above keep it; the plane filter finds it and takes it away, after which the
+object is an island and `largest` finishes the job (include/pcgc.h, pcgc_plane_count and pcgc_plane_select; csrc/plane.hip;
+tests/_plane_ref.py).  A plane is five int64 numbers (a, b, c, d, T) and a voxel is an inlier when |a x + b y + c z - d| <= T:
+
+  plane:D[:FRAC[:DRAWS[:SEED]]]   drop the voxels within D cells of the dominant plane when they are at least FRAC of the cloud
+                                  D a multiple of 0.5 in 0.5 .. 32 (D2 = 2 D), 0 < FRAC <= 1 (0.05), 1 <= DRAWS <= 65536 (1024),
+                                  0 <= SEED <= 2^31 - 1 (0)
+
+  1. draws: np.random.default_rng(SEED).integers(0, n, (DRAWS, 3)) names three rows p0, p1, p2 per draw; (a, b, c) = cross(p1 - p0,
+     p2 - p0), d = (a, b, c) . p0, T = isqrt(D2^2 (a^2 + b^2 + c^2)) // 2 in Python integers (exactly 2 |s| <= D2 |(a, b, c)|), T = -1
+     for a repeated or collinear triple.  The host needs only those 3 DRAWS rows of the cloud.
+  2. score: the device counts every draw's inliers; the best draw has the most, the lowest index among equals.  All counts 0: no
+     plane.
+  3. refit: the device sums 1, x, y, z, x^2, y^2, z^2, xy, xz, yz over the best draw's inliers (int64); the host forms the float64
+     covariance, takes np.linalg.eigh's eigenvector v of the smallest eigenvalue, nq = rint(2^16 v), and the plane (N nq, nq . sum p,
+     isqrt(D2^2 N^2 |nq|^2) // 2).  The final plane is the one of the two with more inliers, the refit among equals.
+  4. decision: final count >= FRAC * n drops the final inliers, anything less keeps every voxel.
+
+    python -m pcgcv1_amd.clean --input vox.ply --output vox_clean.ply --clean stat:20:2.0 --clean plane:1.5 --clean largest:2
+
+It prints a line of its own as well: the unit normal, the offset along it, the final count, the best draw's and the draws.
 """
 import argparse
 import math
@@ -37,20 +60,24 @@ from . import _lib
 
 MAX_BITS, MAX_K, MAX_RADIUS, DEFAULT_RADIUS = 12, 64, 32, 8
 MAX_GAP, DEFAULT_GAP, MAX_MIN_SIZE = 8, 1, 2 ** 31 - 1
+MAX_DIST2, DEFAULT_FRAC, MAX_DRAWS, DEFAULT_DRAWS, MAX_SEED = 64, 0.05, 65536, 1024, 2 ** 31 - 1
+NORMAL_BITS = 16
 
 
 class Spec(object):
-    """one --clean filter: kind 'radius' (radius, min_count), 'stat' (k, ratio, radius), 'component' (min_count, gap) or 'largest'
-    (gap); text = the spec as given"""
+    """one --clean filter: kind 'radius' (radius, min_count), 'stat' (k, ratio, radius), 'component' (min_count, gap), 'largest'
+    (gap) or 'plane' (dist2 = twice the distance in cells, frac, draws, seed); text = the spec as given"""
 
-    def __init__(self, kind, radius=0, k=0, ratio=0.0, min_count=0, text="", gap=DEFAULT_GAP):
+    def __init__(self, kind, radius=0, k=0, ratio=0.0, min_count=0, text="", gap=DEFAULT_GAP, dist2=0, frac=DEFAULT_FRAC,
+                 draws=DEFAULT_DRAWS, seed=0):
         self.kind, self.radius, self.k, self.ratio, self.min_count, self.text, self.gap = kind, radius, k, ratio, min_count, text, gap
+        self.dist2, self.frac, self.draws, self.seed = dist2, frac, draws, seed
 
     def __eq__(self, other):
         return isinstance(other, Spec) and self._key() == other._key()
 
     def _key(self):
-        return self.kind, self.radius, self.k, self.ratio, self.min_count, self.gap
+        return self.kind, self.radius, self.k, self.ratio, self.min_count, self.gap, self.dist2, self.frac, self.draws, self.seed
 
     def __repr__(self):
         return "Spec(%r)" % self.text
@@ -67,7 +94,8 @@ def _int_field(text, name, value, lo, hi):
 
 
 def parse_spec(text):
-    """'radius:R:MIN', 'stat:K:RATIO[:R]', 'component:MIN[:G]' or 'largest[:G]' -> Spec; ValueError names the field that is wrong"""
+    """'radius:R:MIN', 'stat:K:RATIO[:R]', 'component:MIN[:G]', 'largest[:G]' or 'plane:D[:FRAC[:DRAWS[:SEED]]]' -> Spec; ValueError
+    names the field that is wrong"""
     if isinstance(text, Spec):
         return text
     fields = str(text).split(":")
@@ -99,7 +127,27 @@ def parse_spec(text):
         if len(fields) not in (1, 2):
             raise ValueError("--clean %s: the largest-component filter is largest[:G] (%d fields given)" % (text, len(fields)))
         return Spec("largest", gap=_int_field(text, "G", fields[1], 1, MAX_GAP) if len(fields) == 2 else DEFAULT_GAP, text=str(text))
-    raise ValueError("--clean %s: the filter %r is neither 'radius', 'stat', 'component' nor 'largest'" % (text, kind))
+    if kind == "plane":
+        if len(fields) not in (2, 3, 4, 5):
+            raise ValueError("--clean %s: the plane filter is plane:D[:FRAC[:DRAWS[:SEED]]] (%d fields given)" % (text, len(fields)))
+        try:
+            dist2 = 2 * float(fields[1])
+        except ValueError:
+            raise ValueError("--clean %s: D = %r is not a number" % (text, fields[1]))
+        if not (math.isfinite(dist2) and dist2 == math.floor(dist2) and 1 <= dist2 <= MAX_DIST2):
+            raise ValueError("--clean %s: D = %r must be a multiple of 0.5 in 0.5..%d" % (text, fields[1], MAX_DIST2 // 2))
+        frac = DEFAULT_FRAC
+        if len(fields) > 2:
+            try:
+                frac = float(fields[2])
+            except ValueError:
+                raise ValueError("--clean %s: FRAC = %r is not a number" % (text, fields[2]))
+            if not 0 < frac <= 1:                                            # a nan fails both
+                raise ValueError("--clean %s: FRAC = %r must be above 0 and at most 1" % (text, fields[2]))
+        draws = _int_field(text, "DRAWS", fields[3], 1, MAX_DRAWS) if len(fields) > 3 else DEFAULT_DRAWS
+        seed = _int_field(text, "SEED", fields[4], 0, MAX_SEED) if len(fields) > 4 else 0
+        return Spec("plane", text=str(text), dist2=int(dist2), frac=frac, draws=draws, seed=seed)
+    raise ValueError("--clean %s: the filter %r is neither 'radius', 'stat', 'component', 'largest' nor 'plane'" % (text, kind))
 
 
 def parse_specs(specs):
@@ -178,6 +226,107 @@ def components(points, bits, gap=DEFAULT_GAP):
     return label, sizes, n_components
 
 
+def plane_counts(points, bits, planes):
+    """points int32 [n,3] (numpy or a tensor), planes int64 [K,5] (a, b, c, d, T) -> device tensor int32 [K], the inliers of every
+    plane: pcgc_plane_count"""
+    import torch
+    p_d = _device_voxels(points)
+    planes = planes if torch.is_tensor(planes) else torch.from_numpy(np.ascontiguousarray(np.asarray(planes, np.int64).reshape(-1, 5)))
+    planes = planes.to(p_d.device, torch.int64).reshape(-1, 5).contiguous()
+    counts = torch.empty(int(planes.shape[0]), dtype=torch.int32, device=p_d.device)
+    _lib.check(_lib.hip().pcgc_plane_count(_lib.dptr(p_d), int(p_d.shape[0]), bits, _lib.dptr(planes), int(planes.shape[0]),
+                                           _lib.dptr(counts), _lib.stream()), "pcgc_plane_count")
+    return counts
+
+
+def plane_select(points, bits, plane, want_sums=True):
+    """points int32 [n,3], plane int64 [5] -> device tensors (mask uint8 [n], 1 = inlier; sums int64 [10] over the inliers: N, x,
+    y, z, x^2, y^2, z^2, xy, xz, yz | None when not wanted): pcgc_plane_select"""
+    import torch
+    p_d = _device_voxels(points)
+    plane = plane if torch.is_tensor(plane) else torch.from_numpy(np.ascontiguousarray(np.asarray(plane, np.int64).reshape(5)))
+    plane = plane.to(p_d.device, torch.int64).reshape(5).contiguous()
+    mask = torch.empty(int(p_d.shape[0]), dtype=torch.uint8, device=p_d.device)
+    sums = torch.empty(10, dtype=torch.int64, device=p_d.device) if want_sums else None
+    _lib.check(_lib.hip().pcgc_plane_select(_lib.dptr(p_d), int(p_d.shape[0]), bits, _lib.dptr(plane), _lib.dptr(mask), _lib.dptr(sums),
+                                            _lib.stream()), "pcgc_plane_select")
+    return mask, sums
+
+
+def plane_threshold(D2, nn):
+    """T of a plane whose normal has the squared length nn (a Python integer): |s| <= T is exactly 2 |s| <= D2 sqrt(nn)"""
+    return math.isqrt(D2 * D2 * int(nn)) // 2
+
+
+def draw_planes(points_at, D2, draws, seed, n):
+    """step 1 of the plane rule on the host -> int64 [draws,5].  points_at(rows int64 [m]) -> the voxels of those rows [m,3]: the
+    3 * draws rows the triples name are all it reads of the cloud"""
+    tri = np.random.default_rng(seed).integers(0, n, (draws, 3))
+    p = np.asarray(points_at(tri.reshape(-1)), np.int64).reshape(draws, 3, 3)
+    normal = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    nn = (normal * normal).sum(1)
+    planes = np.empty((draws, 5), np.int64)
+    planes[:, :3] = normal
+    planes[:, 3] = (normal * p[:, 0]).sum(1)
+    planes[:, 4] = [plane_threshold(D2, v) if v else -1 for v in nn.tolist()]     # a repeated or collinear triple matches nothing
+    return planes
+
+
+def refit_plane(sums, D2):
+    """step 3 of the plane rule on the host: the ten int64 sums over a plane's inliers -> the least-squares plane int64 [5]"""
+    N, sx, sy, sz, xx, yy, zz, xy, xz, yz = [int(v) for v in sums]
+    mu = np.array([sx, sy, sz], np.float64) / N
+    cov = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], np.float64) / N - np.outer(mu, mu)
+    v = np.linalg.eigh(cov)[1][:, 0]                                          # ascending eigenvalues
+    nq = [int(c) for c in np.rint(v * 2.0 ** NORMAL_BITS).astype(np.int64)]
+    return np.array([N * nq[0], N * nq[1], N * nq[2], nq[0] * sx + nq[1] * sy + nq[2] * sz,
+                     plane_threshold(D2, N * N * (nq[0] * nq[0] + nq[1] * nq[1] + nq[2] * nq[2]))], np.int64)
+
+
+def segment_plane(points, bits, spec):
+    """The plane rule for one spec -> (plane int64 [5] | None when no draw has an inlier, mask: device uint8 [n], 1 = within D of
+    that plane, info: n, draws, best_count (the best draw's inliers), count (the final plane's), dropped (count >= FRAC * n))"""
+    import torch
+    spec = parse_spec(spec)
+    p_d = _device_voxels(points)
+    n = int(p_d.shape[0])
+    if n == 0:
+        raise ValueError("clean: the cloud has no points")
+    planes = draw_planes(lambda rows: _download(p_d[torch.from_numpy(rows).to(p_d.device)]), spec.dist2, spec.draws, spec.seed, n)
+    counts = _download(plane_counts(p_d, bits, planes))
+    best = int(np.argmax(counts))                                         # the lowest index among equals
+    info = dict(n=n, draws=spec.draws, best_count=int(counts[best]), count=0, dropped=False)
+    if info["best_count"] == 0:
+        return None, torch.zeros(n, dtype=torch.uint8, device=p_d.device), info
+    plane = planes[best]
+    mask, sums = plane_select(p_d, bits, plane)
+    refit = refit_plane(_download(sums), spec.dist2)
+    refit_mask, refit_sums = plane_select(p_d, bits, refit)
+    info["count"] = int(_download(refit_sums)[0])
+    if info["count"] >= info["best_count"]:
+        plane, mask = refit, refit_mask
+    else:
+        info["count"] = info["best_count"]
+    info["dropped"] = info["count"] >= spec.frac * n
+    return plane, mask, info
+
+
+def plane_line(spec, plane, info):
+    """plane: plane:1.5 dropped normal (-0.1261 0.2032 0.9710) offset 41.77: 26987 of 41014 voxels (best of 1024 draws: 26069), or
+    plane: plane:4:0.9 no plane holds 0.9 of the voxels: the best has normal ...; plane = None: no draw had an inlier"""
+    if plane is None:
+        return "plane: {} no plane holds {:g} of the voxels: none of {} draws spans a plane".format(spec.text, spec.frac, info["draws"])
+    a, b, c, d = [int(v) for v in plane[:4]]
+    length = math.sqrt(a * a + b * b + c * c)
+    if max((a, b, c), key=abs) < 0:                                      # the same plane: its largest component points up
+        a, b, c, d = -a, -b, -c, -d
+    found = "normal ({:.4f} {:.4f} {:.4f}) offset {:.2f}: {} of {} voxels (best of {} draws: {})".format(
+        a / length, b / length, c / length, d / length, info["count"], info["n"], info["draws"], info["best_count"])
+    if info["dropped"]:
+        return "plane: {} dropped {}".format(spec.text, found)
+    return "plane: {} no plane holds {:g} of the voxels: the best has {}".format(spec.text, spec.frac, found)
+
+
 def _download(t):
     """a device vector to the host through page-locked memory, as ingest.merge reads its rows back"""
     import torch
@@ -195,8 +344,14 @@ def components_line(spec, label, size):
 
 
 def keep_mask(points, bits, spec, report=None):
-    """-> host bool [n]: the voxels one filter keeps.  report (a list): a component filter appends its components_line"""
+    """-> host bool [n]: the voxels one filter keeps.  report (a list): a component filter appends its components_line, a plane
+    filter its plane_line"""
     spec = parse_spec(spec)
+    if spec.kind == "plane":
+        plane, mask, info = segment_plane(points, bits, spec)
+        if report is not None:
+            report.append(plane_line(spec, plane, info))
+        return _download(mask) == 0 if info["dropped"] else np.ones(info["n"], bool)
     if spec.kind in ("component", "largest"):
         label, size, _ = components(points, bits, spec.gap)
         label, size = _download(label), _download(size)
@@ -259,7 +414,10 @@ def add_clean_argument(ap):
                          "R cells; stat:K:RATIO[:R] keeps one whose summed distance to its K nearest voxels within R (default 8) cells "
                          "is at most mean + RATIO * std over the cloud; component:MIN[:G] keeps a voxel whose connected component "
                          "(voxels at most G cells apart per axis are linked, default 1) has at least MIN voxels; largest[:G] keeps the "
-                         "largest component.  Repeatable: applied in order")
+                         "largest component; plane:D[:FRAC[:DRAWS[:SEED]]] drops the voxels within D cells (a multiple of 0.5) of the "
+                         "dominant plane, found by DRAWS seeded RANSAC draws (default 1024, seed 0) and refitted by least squares, "
+                         "when they are at least FRAC of the cloud (default 0.05): the floor or the table.  Repeatable: applied in "
+                         "order")
 
 
 def check_clean_argument(ap, args):
