@@ -356,6 +356,38 @@ int pcgc_feature_match(const uint8_t* source_rows, const uint8_t* source_valid, 
 int pcgc_ransac_score(const double* poses, int64_t n_poses, const float* P, const float* Q, int64_t C, double dist,
                       int32_t* counts, pcgc_stream_t stream);
 
+/* Smoothing of a float cloud before it is voxelised: every point is projected onto the plane fitted to the points within
+ * `radius` of it (pcgcv1_amd/smooth.py chains the passes; tests/_smooth_ref.py is the rule in numpy).  The
+ * moments are exact integers and everything behind them is IEEE float64, one operation per step in the order written, so
+ * nothing depends on the order of the points or of the threads: the same input gives the same bytes, and they equal numpy's.
+ * points g (float32 [n,3], grid units) are bucketed into the cells (h, ox, oy, oz, res) of pcgc_offgrid_* above and passed
+ * SORTED ascending by cell key; radius r within (0, 16] and r <= h, so a neighbourhood lies in a cell and its 26
+ * neighbours; kmin within [3, 2^22].  d2 is that of pcgc_offgrid_*.
+ *   N(i) = every j with d2(g_i, g_j) <= r * r: i itself and coincident points included.  K = |N(i)|.
+ *   o_j  = llrint((double(g_j) - double(g_i)) * 65536.0) per component (sub, mul, round half to even), int64
+ *   S = sum over N(i) of o_j (3 x int64);  Q = sum of o_j o_j^T (6 x int64: c00 c01 c02 c11 c12 c22, as pcgc_estimate_normals)
+ *     |o| <= 2^20, so a term is below 2^41 and K <= 2^22 keeps every sum inside int64.
+ *   K < kmin: out[i] = the bits of g_i, moved[i] = 0.  Otherwise moved[i] = 1 and
+ *     m_a  = double(S_a) / double(K);   C_ab = double(Q_ab) / double(K) - m_a * m_b   (div, mul, sub)
+ *     C goes through the cyclic Jacobi of pcgc_estimate_normals (at most 32 sweeps, rotations (0,1), (0,2), (1,2), the same
+ *     thresholds); jx = the smallest diagonal entry by its selection a11 < a00 ? (a22 < a11 ? 2 : 1) : (a22 < a00 ? 2 : 0);
+ *     n = that column of the eigenvector matrix divided by sqrt((n0*n0 + n1*n1) + n2*n2)
+ *     t = (m_0 n_0 + m_1 n_1) + m_2 n_2;   d = t / 65536.0;   out[i,a] = float32(double(g[i,a]) + d * n_a)
+ *   n needs no sign rule: negating it negates t exactly, and (-d)(-n_a) has the bits of d n_a.  C = 0 (every neighbour
+ *   coincides with g_i) gives t = 0 and the input back (a coordinate -0.0 comes back as +0.0).
+ *   out float32 [n,3] (not points itself: a pass reads the whole cloud and writes a new one), moved uint8 [n]; K int32 [n],
+ *   S int64 [n,3], Q int64 [n,6] are optional debug outputs, all three or all NULL.
+ *   Points that are not sorted or leave the grid, or a coordinate that is not finite, touch no memory out of bounds and
+ *   raise the workspace's flag: moved is then 255 everywhere.  A point with more than 2^22 neighbours raises it too: moved
+ *   is then 254 everywhere (the radius is too large for this density).  The other outputs of such a call mean nothing; the
+ *   next call is not affected.  Rejects a null pointer, out == points, a size that is not positive or too large, bad cells, a
+ *   radius outside (0, min(16, h)], a kmin outside [3, 2^22], one or two of K, S, Q, and a workspace smaller than
+ *   pcgc_smooth_workspace_bytes (0 for a bad size), before any memory is touched. */
+size_t pcgc_smooth_workspace_bytes(int res, int64_t n);
+int pcgc_smooth_step(const float* points, int64_t n, double h, int ox, int oy, int oz, int res, double radius, int kmin,
+                     float* out, uint8_t* moved, int32_t* K, int64_t* S, int64_t* Q, void* workspace,
+                     size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- Rendering (pcgcv1_amd/render.py; DESIGN.md "Rendering"; tests/_render_ref.py is the rule in numpy) ---------------
  * A cloud to an image: demo.ipynb:586,596,962,972 (o3d.visualization.draw_geometries), on a node without a display.
  * Orthographic, all integers after one rounding, so an image is defined bit for bit.

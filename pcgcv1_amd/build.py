@@ -40,6 +40,7 @@ HIP_SOURCES = {
     "color.hip": ["-ffp-contract=off"],
     "offgrid.hip": ["-ffp-contract=off"],
     "global.hip": ["-ffp-contract=off"],
+    "smooth.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "ingest.hip": ["-ffp-contract=off"],
     "clean.hip": [],

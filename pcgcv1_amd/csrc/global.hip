@@ -273,29 +273,6 @@ __global__ void __launch_bounds__(256) ransac_score_kernel(const double* poses, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-struct FeatureBuffers {
-  RankBuffers r;
-  int64_t* keys;             // [n]
-  int32_t* start;            // [n + 1]
-  int* bad;
-};
-
-size_t feature_bytes(int res, int64_t n) {
-  return rank_bytes(res) + align256((size_t)n * sizeof(int64_t)) + align256((size_t)(n + 1) * sizeof(int32_t)) + 256;
-}
-
-FeatureBuffers feature_layout(int res, int64_t n, void* workspace) {
-  FeatureBuffers b;
-  b.r = rank_layout(res, workspace);
-  char* w = b.r.rest;
-  b.keys = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)n * sizeof(int64_t));
-  b.start = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)(n + 1) * sizeof(int32_t));
-  b.bad = reinterpret_cast<int*>(w);
-  return b;
-}
-
 bool feature_sizes_ok(int res, int64_t n) { return res >= 1 && res <= kOffgridMaxRes && n > 0 && n <= kFeatureMaxPoints; }
 
 // the window of r in cells of edge h: a point within r of p lies at most floor(r / h) + 1 cells from p's cell
@@ -316,7 +293,7 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_feature_workspace_bytes(int res, int64_t n) { return feature_sizes_ok(res, n) ? feature_bytes(res, n) : 0; }
+size_t pcgc_feature_workspace_bytes(int res, int64_t n) { return feature_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
 
 int pcgc_feature_pairs(const float* kp, const float* normals, int64_t n, double h, int ox, int oy, int oz, int res, double radius,
                        uint32_t* S, int32_t* k, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
@@ -325,9 +302,9 @@ int pcgc_feature_pairs(const float* kp, const float* normals, int64_t n, double 
                "pcgc_feature_pairs: bad arguments");
   PCGC_REQUIRE(window_ok(radius, h, &w), "pcgc_feature_pairs: radius %g must be positive and below %d cells of edge %g", radius,
                kFeatureMaxWindow, h);
-  PCGC_REQUIRE(workspace_bytes >= feature_bytes(res, n), "pcgc_feature_pairs: workspace too small");
+  PCGC_REQUIRE(workspace_bytes >= cell_buffer_bytes(res, n), "pcgc_feature_pairs: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const FeatureBuffers b = feature_layout(res, n, workspace);
+  const CellBuffers b = cell_buffer_layout(res, n, workspace);
   Target t;
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, kp, n, s, &t);
   if (rc) return rc;
@@ -344,9 +321,9 @@ int pcgc_feature_combine(const float* kp, const float* normals, int64_t n, doubl
                "pcgc_feature_combine: bad arguments");
   PCGC_REQUIRE(window_ok(radius, h, &w), "pcgc_feature_combine: radius %g must be positive and below %d cells of edge %g", radius,
                kFeatureMaxWindow, h);
-  PCGC_REQUIRE(workspace_bytes >= feature_bytes(res, n), "pcgc_feature_combine: workspace too small");
+  PCGC_REQUIRE(workspace_bytes >= cell_buffer_bytes(res, n), "pcgc_feature_combine: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const FeatureBuffers b = feature_layout(res, n, workspace);
+  const CellBuffers b = cell_buffer_layout(res, n, workspace);
   Target t;
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, kp, n, s, &t);
   if (rc) return rc;

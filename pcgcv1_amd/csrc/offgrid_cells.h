@@ -106,5 +106,29 @@ int build_cells(const RankBuffers& r, int64_t* keys, int32_t* start, int* bad, c
   return 0;
 }
 
+// a workspace that holds the cells of a cloud of n points and nothing else: what build_cells fills (global.hip, smooth.hip)
+struct CellBuffers {
+  RankBuffers r;
+  int64_t* keys;             // [n]
+  int32_t* start;            // [n + 1]
+  int* bad;
+};
+
+size_t cell_buffer_bytes(int res, int64_t n) {
+  return rank_bytes(res) + align256((size_t)n * sizeof(int64_t)) + align256((size_t)(n + 1) * sizeof(int32_t)) + 256;
+}
+
+CellBuffers cell_buffer_layout(int res, int64_t n, void* workspace) {
+  CellBuffers b;
+  b.r = rank_layout(res, workspace);
+  char* w = b.r.rest;
+  b.keys = reinterpret_cast<int64_t*>(w);
+  w += align256((size_t)n * sizeof(int64_t));
+  b.start = reinterpret_cast<int32_t*>(w);
+  w += align256((size_t)(n + 1) * sizeof(int32_t));
+  b.bad = reinterpret_cast<int*>(w);
+  return b;
+}
+
 }  // namespace
 }  // namespace pcgc

@@ -2,6 +2,7 @@
 -> one integer point per occupied voxel with merged attributes, and the frame that maps it back.
 
     python -m pcgcv1_amd.ingest --input scan.ply --output scan_vox10.ply --bits 10      # or --voxel_size 0.002
+                                [--smooth 3:2]              # thin the noisy shell first: pcgcv1_amd/smooth.py
                                 [--clean stat:20:2.0]       # drop outlier voxels and refit the frame: voxelize_scan_clean
 
 writes the voxelised ply and scan_vox10.frame next to it.  The rule (include/pcgc.h, pcgc_ingest_*; DESIGN.md §7f;
@@ -180,17 +181,49 @@ def merge_device(keys, bits, colors=None, normals=None):
     return pts, counts, oc, on, n_out
 
 
-def voxelize_scan(points, colors=None, normals=None, frame=None, bits=None, voxel_size=None, clean=None):
+def smooth_points(points, frame=None, bits=None, voxel_size=None, smooth=None):
+    """The smoothing stage in front of the voxelisation (a --smooth spec, pcgcv1_amd/smooth.py) -> (points float64 [N,3] in
+    the scan's units, a device tensor; smooth.smooth_scan's report).  The radius is in voxels of `frame`, or of the frame fitted
+    to the raw scan for `bits` or `voxel_size`."""
+    from . import smooth as smoother
+    spec = smoother.parse_spec(smooth)
+    p_d = _device_points(points)
+    if frame is None:
+        lo, hi, _ = bounds(p_d)
+        frame = _frame_from_bounds(lo, hi, bits, voxel_size)
+    return smoother.smooth_scan_device(p_d, frame, spec)
+
+
+def voxel_count(points, frame):
+    """occupied voxels of a float cloud on `frame` (quantise and merge, nothing read back but the count)"""
+    _, keys = quantize(points, frame)
+    return int(merge_device(keys, frame.bits)[4].item())
+
+
+def smooth_line(raw, smoothed, report, bits=None, voxel_size=None, frame=None):
+    """the 'smooth: ...' line of the command lines: the occupied voxels of the raw and of the smoothed cloud, both on the frame
+    the voxelisation fits to the smoothed one (or on `frame`)"""
+    from . import smooth as smoother
+    if frame is None:
+        frame = fit_frame(smoothed, bits, voxel_size)
+    return smoother.summary_line(report, voxel_count(raw, frame), voxel_count(smoothed, frame))
+
+
+def voxelize_scan(points, colors=None, normals=None, frame=None, bits=None, voxel_size=None, clean=None, smooth=None):
     """A scan (float [N,3]; colors uint8 [N,3], normals float [N,3] or None) on the grid of `frame`, or of the frame fitted to it
     for `bits` or `voxel_size` -> (points int32 [M,3] in np.unique's order, colors uint8 [M,3] | None, normals float32
     [M,3] | None, counts int32 [M], frame, n_dropped).  Points outside a given frame are clamped to its grid.
-    clean (a --clean spec or a list of them, pcgcv1_amd/clean.py): voxelize_scan_clean's eight values instead."""
+    clean (a --clean spec or a list of them, pcgcv1_amd/clean.py): voxelize_scan_clean's eight values instead.
+    smooth (a --smooth spec, pcgcv1_amd/smooth.py): the positions go through smooth_points first, and everything else is
+    this function as it stands on what comes back, the fit of its own frame included."""
     if clean:
         if frame is not None:
             raise ValueError("voxelize_scan: clean refits the frame to what it keeps: give bits or voxel_size, not a frame")
-        return voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)
+        return voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean, smooth)
     if frame is not None and (bits is not None or voxel_size is not None):
         raise ValueError("voxelize_scan: give a frame, or bits / voxel_size to fit one")
+    if smooth:
+        points = smooth_points(points, frame, bits, voxel_size, smooth)[0]
     p_d = _device_points(points)
     lo, hi, n_dropped = bounds(p_d)
     if frame is None:
@@ -200,7 +233,7 @@ def voxelize_scan(points, colors=None, normals=None, frame=None, bits=None, voxe
     return pts, c, nrm, counts, frame, n_dropped
 
 
-def voxelize_scan_clean(points, colors=None, normals=None, bits=None, voxel_size=None, clean=()):
+def voxelize_scan_clean(points, colors=None, normals=None, bits=None, voxel_size=None, clean=(), smooth=None):
     """voxelize_scan with the outlier voxels of pcgcv1_amd/clean.py dropped and the frame fitted again to what is left ->
     (points, colors, normals, counts, frame, n_dropped, n_removed_voxels, n_removed_points):
       1. fit the frame, quantise, merge, and run the filters `clean` (a spec or a list, applied in order) on the voxels;
@@ -209,7 +242,10 @@ def voxelize_scan_clean(points, colors=None, normals=None, bits=None, voxel_size
       4. quantise and merge again.
     There is no second cleaning pass: the result is not filtered on its own, finer, grid.  With bits the resolution the
     outliers took comes back; with voxel_size the origin stays a multiple of the step, so the result is the kept voxels of
-    pass 1 shifted by whole cells, in possibly fewer bits.  ValueError when the filters would leave nothing."""
+    pass 1 shifted by whole cells, in possibly fewer bits.  ValueError when the filters would leave nothing.
+    smooth: as voxelize_scan, in front of step 1."""
+    if smooth:
+        points = smooth_points(points, None, bits, voxel_size, smooth)[0]
     return _voxelize_scan_clean(points, colors, normals, bits, voxel_size, clean)[0]
 
 
@@ -291,9 +327,13 @@ def frame_path(ply_or_stem):
 
 
 # ---------------------------------------------------------------------------- command line
-def voxelize_scan_report(points, colors=None, normals=None, bits=None, voxel_size=None, clean=None):
+def voxelize_scan_report(points, colors=None, normals=None, bits=None, voxel_size=None, clean=None, smooth=None):
     """what the command lines run -> (voxelize_scan's six values, the 'clean: ...' summary line, or None without clean; a
-    component filter adds a line of its own: clean.components_line)"""
+    component filter adds a line of its own: clean.components_line).  smooth: the 'smooth: ...' line comes first."""
+    if smooth:
+        smoothed, moved = smooth_points(points, None, bits, voxel_size, smooth)
+        out, line = voxelize_scan_report(smoothed, colors, normals, bits, voxel_size, clean)
+        return out, "\n".join([smooth_line(points, smoothed, moved, bits, voxel_size)] + ([line] if line else []))
     if not clean:
         return voxelize_scan(points, colors, normals, bits=bits, voxel_size=voxel_size), None
     from . import clean as cleaner
@@ -305,15 +345,16 @@ def voxelize_scan_report(points, colors=None, normals=None, bits=None, voxel_siz
     return out[:6], "\n".join([cleaner.summary_line(clean, len(vox), out[6], cubes, cleaner.n_cubes(out[0]), out[7])] + report)
 
 
-def ingest_file(filename, bits=None, voxel_size=None, clean=None):
+def ingest_file(filename, bits=None, voxel_size=None, clean=None, smooth=None):
     """load_ply_scan + voxelize_scan -> (points, colors | None, normals | None, counts, frame, n_dropped, n_input), and with
-    clean the 'clean: ...' summary line (and a component filter's line below it) as an eighth value"""
+    clean the 'clean: ...' summary line (and a component filter's line below it) as an eighth value; with smooth the
+    'smooth: ...' line, in front of clean's"""
     from .dataprocess.inout_points import load_ply_scan
     points, colors, normals = load_ply_scan(filename)
     if not len(points):
         raise ValueError("%s holds no points" % filename)
-    out, line = voxelize_scan_report(points, colors, normals, bits, voxel_size, clean)
-    return out + (len(points),) + ((line,) if clean else ())
+    out, line = voxelize_scan_report(points, colors, normals, bits, voxel_size, clean, smooth)
+    return out + (len(points),) + ((line,) if clean or smooth else ())
 
 
 def summary_line(n_input, n_dropped, counts, frame):
@@ -331,8 +372,11 @@ def parse_args(argv=None):
                     help="which attribute the ply carries when the scan has both (it has room for one)")
     from .clean import add_clean_argument, check_clean_argument
     add_clean_argument(ap)
+    from .smooth import add_smooth_argument, check_smooth_argument
+    add_smooth_argument(ap)
     args = ap.parse_args(argv)
     check_clean_argument(ap, args)
+    check_smooth_argument(ap, args)
     if (args.bits is None) == (args.voxel_size is None):
         ap.error("give --bits or --voxel_size, one of them")
     if args.bits is not None and not 1 <= args.bits <= MAX_BITS:
@@ -346,7 +390,7 @@ def main(argv=None):
     from .dataprocess.inout_points import write_ply_colors, write_ply_data, write_ply_normals
     args = parse_args(argv)
     try:
-        out = ingest_file(args.input, args.bits, args.voxel_size, args.clean)
+        out = ingest_file(args.input, args.bits, args.voxel_size, args.clean, args.smooth)
         points, colors, normals, counts, frame, n_dropped, n_input = out[:7]
     except ValueError as e:
         raise SystemExit("ingest: %s" % e)
@@ -358,7 +402,7 @@ def main(argv=None):
         write_ply_data(args.output, points)
     write_frame(frame_path(args.output), frame)
     print(summary_line(n_input, n_dropped, counts, frame))
-    if args.clean:
+    if args.clean or args.smooth:
         print(out[7])
     print("wrote {} and {}".format(args.output, frame_path(args.output)))
 

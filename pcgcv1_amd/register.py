@@ -3,7 +3,7 @@ of pcgcv1_amd/ingest.py.
 
     python -m pcgcv1_amd.register --input a.ply b.ply c.ply --output merged_vox10.ply --bits 10     # or --voxel_size S
                                   [--metric plane|point] [--max_dist 4,2,1] [--iters 50] [--tol 1e-3] [--estimate_normals]
-                                  [--init poses.json] [--clean SPEC] [--min_fitness 0.3]
+                                  [--init poses.json] [--smooth SPEC] [--clean SPEC] [--min_fitness 0.3]
                                   [--global_init [--feature_voxel 1] [--feature_radius 8] [--corr_dist 2] [--draws 100000] [--seed 0]]
 
 writes the voxelised ply and merged_vox10.frame as pcgcv1_amd.ingest would for the union of the aligned scans, and
@@ -290,6 +290,21 @@ def keypoints(points, normals, feature_voxel):
     return ingest.apply_frame(vox, frame).astype(np.float32), _unit_normals(nrm, len(vox))
 
 
+def cells_from_bounds(lo, hi, radius, who="global_align"):
+    """-> (h, ox, oy, oz, res): the cells a search within `radius` walks between the extremes lo and hi (float64 [3]) of a cloud:
+    the smallest power of two h >= max(1, radius) with at most 1024 cells per axis"""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    h = 1.0
+    while h < radius or int((np.floor(hi / h) - np.floor(lo / h)).max()) + 1 > FEATURE_MAX_CELLS:
+        h *= 2.0
+        if h > FEATURE_MAX_EDGE:
+            raise ValueError("%s: keypoints of extent %g with radius %g need cells wider than 2^20" % (who, float((hi - lo).max()), radius))
+    origin = np.floor(lo / h)
+    if float(np.abs(np.stack([origin, np.floor(hi / h)])).max()) >= 2.0 ** 28:
+        raise ValueError("%s: coordinate / cell edge reaches 2^28 (cell edge %g)" % (who, h))
+    return (h, int(origin[0]), int(origin[1]), int(origin[2]), int((np.floor(hi / h) - origin).max()) + 1)
+
+
 def feature_cells(kp, radius):
     """-> (h, ox, oy, oz, res): the cells pcgc_feature_* search keypoints in: the smallest power of two h >= max(1, radius)
     with at most 1024 cells per axis between the extremes of the finite rows"""
@@ -297,16 +312,20 @@ def feature_cells(kp, radius):
     p = p[np.isfinite(p).all(1)]
     if not len(p) or not (np.isfinite(radius) and radius > 0):
         raise ValueError("global_align: the keypoints need a finite row and radius must be positive (got %r)" % (radius,))
-    lo, hi = p.min(0), p.max(0)
-    h = 1.0
-    while h < radius or int((np.floor(hi / h) - np.floor(lo / h)).max()) + 1 > FEATURE_MAX_CELLS:
-        h *= 2.0
-        if h > FEATURE_MAX_EDGE:
-            raise ValueError("global_align: keypoints of extent %g with radius %g need cells wider than 2^20" % (float((hi - lo).max()), radius))
-    origin = np.floor(lo / h)
-    if float(np.abs(np.stack([origin, np.floor(hi / h)])).max()) >= 2.0 ** 28:
-        raise ValueError("global_align: coordinate / cell edge reaches 2^28 (cell edge %g)" % h)
-    return (h, int(origin[0]), int(origin[1]), int(origin[2]), int((np.floor(hi / h) - origin).max()) + 1)
+    return cells_from_bounds(p.min(0), p.max(0), radius)
+
+
+def cell_order(points, cells):
+    """points: a float32 [n,3] tensor, on the host or the device -> the stable order (int64 tensor, where the points lie) that
+    sorts them by the key of `cells`, which is how pcgc_feature_* and pcgc_smooth_step want them; a row outside the cells or
+    with a coordinate that is not finite sorts first (key -1), and the kernels refuse it"""
+    import torch
+    h, ox, oy, oz, res = cells
+    cell = torch.floor(points.to(torch.float64) / h) - torch.tensor([ox, oy, oz], dtype=torch.float64, device=points.device)
+    inside = torch.isfinite(cell).all(1) & (cell >= 0).all(1) & (cell < res).all(1)
+    c = torch.where(inside[:, None], cell, torch.zeros_like(cell)).to(torch.int64)
+    key = torch.where(inside, (c[:, 0] * res + c[:, 1]) * res + c[:, 2], torch.full_like(c[:, 0], -1))
+    return torch.sort(key, stable=True)[1]
 
 
 class _FeatureCloud(object):
@@ -321,12 +340,8 @@ class _FeatureCloud(object):
             raise ValueError("global_align: %d normals for %d keypoints" % (len(nrm), len(kp)))
         self.n, self.radius = len(kp), float(radius)
         self.cells = feature_cells(kp, radius) if cells is None else cells
-        h, ox, oy, oz, res = self.cells
-        with np.errstate(invalid="ignore"):
-            cell = np.floor(kp.astype(np.float64) / h) - np.array([ox, oy, oz], np.float64)
-        inside = np.isfinite(cell).all(1) & (cell >= 0).all(1) & (cell < res).all(1)
-        c = np.where(inside[:, None], cell, 0.0).astype(np.int64)
-        self.order = np.argsort(np.where(inside, (c[:, 0] * res + c[:, 1]) * res + c[:, 2], -1), kind="stable")
+        res = self.cells[4]
+        self.order = cell_order(torch.from_numpy(kp), self.cells).numpy()
         self.kp = torch.from_numpy(kp[self.order]).to(self.dev)
         self.normals = torch.from_numpy(nrm[self.order]).to(self.dev)
         self.ws = torch.empty(max(1, int(_lib.hip().pcgc_feature_workspace_bytes(res, self.n))), dtype=torch.uint8, device=self.dev)
@@ -584,15 +599,18 @@ def _finite_scan(k, scan):
 
 
 def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=DEFAULT_MAX_DIST, iters=50, tol=1e-3, init=None,
-                   estimate_normals=False, clean=None, names=None, global_init=False, global_options=None):
+                   estimate_normals=False, clean=None, names=None, global_init=False, global_options=None, smooth=None):
     """scans: list of (points float64 [n,3] in the scanner's units, colors uint8 [n,3] | None, normals [n,3] | None).  Scan 0
     defines the coordinates; scan k >= 1 is registered against the union of scan 0 and the aligned scans before it, on the
     grid of the ingest.Frame fitted to that union with bits / voxel_size.  init: per scan None or (R, t) in scan units;
     names: what to call the scans in an error.  global_init: a scan k >= 1 without an init starts from global_align against
     the union before it (global_options: its keyword arguments), normals a scan lacks estimated on its voxels; icp then runs
     unchanged, and the scan's pose entry gains "global": inliers, correspondences, hypotheses, draw.
+    smooth (a --smooth spec, pcgcv1_amd/smooth.py): the aligned union's positions are smoothed just before the merge, which is
+    where the sheets of the same surface lie on top of each other; the result gains "smooth", the line the command prints.
     -> dict: merged = ingest.voxelize_scan(union, ..., clean=clean) as it returns it, poses = per scan the icp result with
-    R, t in scan units and "pose" the 4x4 matrix (scan 0: the identity), aligned = the union's (points, colors, normals)."""
+    R, t in scan units and "pose" the 4x4 matrix (scan 0: the identity), aligned = the union's (points, colors, normals), as
+    registered: not smoothed."""
     from . import ingest
     if len(scans) < 1:
         raise ValueError("register_scans: no scans")
@@ -601,6 +619,9 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
     if (bits is None) == (voxel_size is None):
         raise ValueError("register_scans: give bits or voxel_size, one of them")
     gates = _schedule(max_dist)
+    if smooth:
+        from .smooth import parse_spec
+        smooth = parse_spec(smooth)
     scans = [_finite_scan(k, s) for k, s in enumerate(scans)]
     pts, cols, nrms = [scans[0][0]], [scans[0][1]], [scans[0][2]]
     poses = [{"R": np.eye(3), "t": np.zeros(3), "pose": np.eye(4), "iterations": [], "converged": True, "n_used": len(pts[0]),
@@ -636,8 +657,12 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
         nrms.append(None if nrm is None else (nrm.astype(np.float64) @ r["R"].T).astype(np.float32))
     union = (np.concatenate(pts), np.concatenate(cols) if all(c is not None for c in cols) else None,
              np.concatenate(nrms) if all(n is not None for n in nrms) else None)
-    merged = ingest.voxelize_scan(union[0], union[1], union[2], bits=bits, voxel_size=voxel_size, clean=clean)
-    return {"merged": merged, "poses": poses, "aligned": union}
+    if not smooth:
+        merged = ingest.voxelize_scan(union[0], union[1], union[2], bits=bits, voxel_size=voxel_size, clean=clean)
+        return {"merged": merged, "poses": poses, "aligned": union}
+    smoothed, moved = ingest.smooth_points(union[0], None, bits, voxel_size, smooth)
+    merged = ingest.voxelize_scan(smoothed, union[1], union[2], bits=bits, voxel_size=voxel_size, clean=clean)
+    return {"merged": merged, "poses": poses, "aligned": union, "smooth": ingest.smooth_line(union[0], smoothed, moved, bits, voxel_size)}
 
 
 # ---------------------------------------------------------------------------- <name>.poses.json
@@ -716,8 +741,11 @@ def parse_args(argv=None):
                     help="which attribute the ply carries when the union has both")
     from .clean import add_clean_argument, check_clean_argument
     add_clean_argument(ap)
+    from .smooth import add_smooth_argument, check_smooth_argument
+    add_smooth_argument(ap)
     args = ap.parse_args(argv)
     check_clean_argument(ap, args)
+    check_smooth_argument(ap, args)
     if (args.bits is None) == (args.voxel_size is None):
         ap.error("give --bits or --voxel_size, one of them")
     if args.bits is not None and not 1 <= args.bits <= ingest.MAX_BITS:
@@ -774,7 +802,7 @@ def main(argv=None):
                    "seed": args.seed}
         out = register_scans(scans, args.bits, args.voxel_size, args.metric, args.max_dist, args.iters, args.tol, init,
                              args.estimate_normals, args.clean, names=args.input, global_init=args.global_init,
-                             global_options=options)
+                             global_options=options, smooth=args.smooth)
     except ValueError as e:
         raise SystemExit("register: %s" % e)
     failed = []
@@ -800,6 +828,8 @@ def main(argv=None):
     ingest.write_frame(ingest.frame_path(args.output), frame)
     write_poses(poses_path(args.output), [os.path.basename(n) for n in args.input], out["poses"])
     print(ingest.summary_line(len(out["aligned"][0]), n_dropped, counts, frame))
+    if "smooth" in out:
+        print(out["smooth"])
     print("wrote {}, {} and {}".format(args.output, ingest.frame_path(args.output), poses_path(args.output)))
 
 

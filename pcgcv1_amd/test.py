@@ -68,10 +68,16 @@ def parse_args(argv=None):
                     help="compress only: as --voxelize, with voxels of edge S in the scan's units instead of a bit count")
     from .clean import add_clean_argument, check_clean_argument
     add_clean_argument(ap)
+    from .smooth import add_smooth_argument, check_smooth_argument
+    add_smooth_argument(ap)
     ap.add_argument("--render", default="", metavar="X.png",
                     help="decompress only: also draw the cloud just written into this png (pcgcv1_amd/render.py, default view and size)")
     args = ap.parse_args(argv)
     check_clean_argument(ap, args)
+    check_smooth_argument(ap, args)
+    if args.smooth and (args.command != "compress" or not (args.voxelize or args.voxel_size)):
+        ap.error("--smooth moves the float points of a raw scan: it belongs to compress --voxelize or --voxel_size (a voxelised "
+                 "ply has no float points)")
     if args.clean and args.command != "compress":
         ap.error("--clean belongs to compress: decompress writes what the stream holds")
     if args.clean and args.scale != 1:
@@ -93,7 +99,7 @@ def parse_args(argv=None):
         ap.error("--pointnums=d2 needs normals: %s has no nx ny nz properties (or cannot be read); write them into the ply, or "
                  "pass --estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
     # the line every run prints: the ingest flags show up in it only when they are given
-    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size", "clean") or v}))
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size", "clean", "smooth") or v}))
     return args
 
 
@@ -414,7 +420,7 @@ def _voxelize_input(args, coded_colors):
     try:
         (points, colors, normals, counts, frame, n_dropped), cleaned = ingest.voxelize_scan_report(
             scan, colors if coded_colors else None, normals if args.pointnums == "d2" else None,
-            bits=args.voxelize or None, voxel_size=args.voxel_size or None, clean=args.clean)
+            bits=args.voxelize or None, voxel_size=args.voxel_size or None, clean=args.clean, smooth=args.smooth)
     except ValueError as e:
         raise SystemExit("%s: %s" % (args.input, e))
     print(ingest.summary_line(len(scan), n_dropped, counts, frame))
