@@ -103,6 +103,12 @@ HIP_API = {
     "pcgc_smooth_workspace_bytes": (c_sz, [c_int, c_i64]),
     "pcgc_smooth_step": (c_int, [c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_color_gradient_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_color_gradient": (c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_register_color_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_register_color_step": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int,
+                                         c_int, c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_render_workspace_bytes": (c_sz, [c_int, c_int]),
     "pcgc_render_splat": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_int, c_int,
                                   c_int, c_vp, c_sz, c_vp]),

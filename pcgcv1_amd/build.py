@@ -41,6 +41,7 @@ HIP_SOURCES = {
     "offgrid.hip": ["-ffp-contract=off"],
     "global.hip": ["-ffp-contract=off"],
     "smooth.hip": ["-ffp-contract=off"],
+    "color_icp.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "ingest.hip": ["-ffp-contract=off"],
     "clean.hip": [],

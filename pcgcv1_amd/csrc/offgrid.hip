@@ -390,3 +390,144 @@ int pcgc_register_step(const float* p, int64_t np, const float* q, int64_t nq, c
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- coloured ICP
+// One step of the colour metric (include/pcgc.h, pcgc_register_color_step; tests/_color_icp_ref.py): the search,
+// the tie set, the weights and the gate of register_step_kernel, and per pair the point-to-plane terms plus, where the
+// target point has a gradient (pcgc_color_gradient, color_icp.hip), the photometric terms.  Two blocks of 28 sums of one shape
+// (the upper triangle of J J^T, J res, res^2), the count of valid pairs between them; the point-to-point moments are left out,
+// so that the 59 accumulators stay in registers.
+namespace pcgc {
+namespace {
+
+constexpr int kColSums = 59;
+constexpr int kColGeo = 2, kColWeight = 30, kColPhoto = 31;       // where the two blocks of 28 and the weight sum start
+constexpr double kIntensityScale = 2550000.0;                     // 255 * (2126 + 7152 + 722)
+
+// acc[0..20] += (w J_r) J_c for r <= c, acc[21..26] += (w J_r) res, acc[27] += (w res) res
+__device__ __forceinline__ void add_six_terms(double* acc, const double J[6], double res, double w) {
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double wj = w * J[r];
+#pragma unroll
+    for (int c = r; c < 6; ++c) acc[k++] += wj * J[c];
+    acc[21 + r] += wj * res;
+  }
+  acc[27] += (w * res) * res;
+}
+
+__global__ void __launch_bounds__(256) register_color_step_kernel(const float* p, int64_t np, const int32_t* Yp, Target t,
+                                                                  const float* normals_q, const int32_t* Yq, const double* grad_q,
+                                                                  const uint8_t* valid_q, Pose pose, double gate2, double* partial,
+                                                                  double* best_out, int32_t* ties_out, int* bad) {
+  __shared__ double sh[4][kColSums];
+  double acc[kColSums];
+#pragma unroll
+  for (int k = 0; k < kColSums; ++k) acc[k] = 0.0;
+  long long n_used = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
+    const double x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
+    float pf[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) pf[r] = (float)(((pose.R[3 * r] * x + pose.R[3 * r + 1] * y) + pose.R[3 * r + 2] * z) + pose.t[r]);
+    int cell[3], shell, ties = 0;
+    double best = NAN;
+    if (cell_of_point(t.c, pf, cell)) {
+      const double px = pf[0], py = pf[1], pz = pf[2];
+      best = nearest_offgrid(t, cell, px, py, pz, &shell);
+      if (best <= gate2) {
+        for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t, double, double, double) { ++ties; });
+        const double w = 1.0 / (double)ties;
+        const double a[3] = {px - pose.c[0], py - pose.c[1], pz - pose.c[2]};
+        const double ip = (double)Yp[i] / kIntensityScale;
+        for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t j, double, double, double) {
+          const float* q = t.q + (int64_t)j * 3;
+          const float* n = normals_q + (int64_t)j * 3;
+          const double d[3] = {a[0] - ((double)q[0] - pose.c[0]), a[1] - ((double)q[1] - pose.c[1]), a[2] - ((double)q[2] - pose.c[2])};
+          {
+            const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
+            const double res = (d[0] * n0 + d[1] * n1) + d[2] * n2;
+            const double J[6] = {a[1] * n2 - a[2] * n1, a[2] * n0 - a[0] * n2, a[0] * n1 - a[1] * n0, n0, n1, n2};
+            add_six_terms(acc + kColGeo, J, res, w);
+          }
+          if (valid_q[j]) {
+            const double* g = grad_q + (int64_t)j * 3;
+            const double g0 = g[0], g1 = g[1], g2 = g[2];
+            const double rc = ((double)Yq[j] / kIntensityScale - ip) + ((d[0] * g0 + d[1] * g1) + d[2] * g2);
+            const double Jc[6] = {a[1] * g2 - a[2] * g1, a[2] * g0 - a[0] * g2, a[0] * g1 - a[1] * g0, g0, g1, g2};
+            acc[kColWeight] += w;
+            add_six_terms(acc + kColPhoto, Jc, rc, w);
+          }
+        });
+        ++n_used;
+        acc[1] += best;
+      }
+    } else {
+      atomicOr(bad, 1);
+    }
+    if (best_out) { best_out[i] = best; ties_out[i] = ties; }
+  }
+  acc[0] = (double)n_used;                                    // below 2^31 per launch: exact, and so is every partial sum of them
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kColSums; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) sh[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kColSums)
+    partial[threadIdx.x * kOffgridBlocks + blockIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+// one wave: lane k adds sum k of the workgroups in index order; bad[0] is prepare's flag (the target), bad[1] this step's
+__global__ void __launch_bounds__(64) register_color_final_kernel(const double* partial, int nb, const int* bad, double* out59) {
+  const int k = threadIdx.x;
+  if (k >= kColSums) return;
+  double v = 0.0;
+  for (int i = 0; i < nb; ++i) v += partial[k * kOffgridBlocks + i];
+  out59[k] = (bad[0] | bad[1]) ? (double)NAN : v;
+}
+
+}  // namespace
+}  // namespace pcgc
+
+extern "C" {
+
+// the off-grid layout as it is, then [59, kOffgridBlocks] doubles: pcgc_register_prepare fills it as it fills its own
+size_t pcgc_register_color_workspace_bytes(int res, int64_t nq) {
+  const size_t base = pcgc_offgrid_workspace_bytes(res, nq);
+  return base ? base + align256((size_t)kColSums * kOffgridBlocks * sizeof(double)) : 0;
+}
+
+int pcgc_register_color_step(const float* p, const int32_t* Yp, int64_t np, const float* q, const float* normals_q, const int32_t* Yq,
+                             const double* grad_q, const uint8_t* valid_q, int64_t nq, double h, int ox, int oy, int oz, int res,
+                             const double* R9, const double* t3, const double* c3, double max_dist, double* out59, double* best,
+                             int32_t* n_ties, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(p && Yp && q && normals_q && Yq && grad_q && valid_q && R9 && t3 && c3 && out59 && workspace &&
+               grid_ok(h, ox, oy, oz, res, np, nq) && (best == nullptr) == (n_ties == nullptr), "pcgc_register_color_step: bad arguments");
+  PCGC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0, "pcgc_register_color_step: max_dist must be finite and positive (got %g)",
+               max_dist);
+  Pose pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R9[k];
+  for (int k = 0; k < 3; ++k) { pose.t[k] = t3[k]; pose.c[k] = c3[k]; }
+  bool finite = true;
+  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(pose.R[k]);
+  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(pose.t[k]) && std::isfinite(pose.c[k]);
+  PCGC_REQUIRE(finite, "pcgc_register_color_step: the pose and the centre must be finite");
+  PCGC_REQUIRE(workspace_bytes >= pcgc_register_color_workspace_bytes(res, nq), "pcgc_register_color_step: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const OffgridBuffers b = offgrid_layout(res, nq, workspace);               // as pcgc_register_prepare left it
+  const Target t{Cells{h, ox, oy, oz, res}, b.r.bits, b.r.rank, b.start, q};
+  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + offgrid_bytes(res, nq));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.bad + 1, 0, sizeof(int), s));
+  const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
+  hipLaunchKernelGGL(register_color_step_kernel, dim3(blocks), dim3(256), 0, s, p, np, Yp, t, normals_q, Yq, grad_q, valid_q, pose,
+                     max_dist * max_dist, partial, best, n_ties, b.bad + 1);
+  hipLaunchKernelGGL(register_color_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, b.bad, out59);
+  return launch_ok("colour registration step kernels");
+}
+
+}  // extern "C"

@@ -2,7 +2,8 @@
 of pcgcv1_amd/ingest.py.
 
     python -m pcgcv1_amd.register --input a.ply b.ply c.ply --output merged_vox10.ply --bits 10     # or --voxel_size S
-                                  [--metric plane|point] [--max_dist 4,2,1] [--iters 50] [--tol 1e-3] [--estimate_normals]
+                                  [--metric plane|point|color [--color_weight 0.9] [--color_radius 3] [--color_kmin 6]]
+                                  [--max_dist 4,2,1] [--iters 50] [--tol 1e-3] [--estimate_normals]
                                   [--init poses.json] [--smooth SPEC] [--clean SPEC] [--min_fitness 0.3]
                                   [--global_init [--feature_voxel 1] [--feature_radius 8] [--corr_dist 2] [--draws 100000] [--seed 0]]
 
@@ -13,7 +14,9 @@ The rule (include/pcgc.h, pcgc_register_*; tests/_register_ref.p
 units, neighbouring surface points about 1 apart.  One step (csrc/offgrid.hip) moves the source by the trial pose, finds
 every tied nearest neighbour in the target with the off-grid search, keeps the points within max_dist and reduces them to 45
 float64 sums in a fixed order.  The solve is numpy float64 on the host: Kabsch for point-to-point, the 6x6 normal equations
-with an exact Rodrigues rotation for point-to-plane.  max_dist is a coarse-to-fine schedule: with one wide gate the points
+with an exact Rodrigues rotation for point-to-plane.  metric="color" (tests/_color_icp_ref.py) adds a photometric
+term to the point-to-plane one: the target's intensity gradients are fitted once (csrc/color_icp.hip), a step gives 59 sums,
+and the solve mixes the two systems by color_weight.  max_dist is a coarse-to-fine schedule: with one wide gate the points
 beyond the overlap pair with the target's rim and pull the pose.  A start further off than the first gate bridges comes from
 init, or from the global alignment below (global_init / --global_init).
 
@@ -34,9 +37,17 @@ import numpy as np
 from . import _lib
 
 N_SUMS = 45
-MIN_PAIRS = {"point": 3, "plane": 6}
+N_COLOR_SUMS = 59            # pcgc_register_color_step: the plane block [2..29], the valid weight [30], the photometric block [31..58]
+MIN_PAIRS = {"point": 3, "plane": 6, "color": 6}
 COND_LIMIT = 1e12
 DEFAULT_MAX_DIST = (4.0, 2.0, 1.0)
+# the colour metric: the photometric share of the joint objective, and the ball the target's intensity gradients
+# are fitted in (voxels; at least kmin points, the point itself included).  Of the weights 0.5 and 0.9, 0.9 left the flat and
+# the spherical fixtures closest to the truth
+DEFAULT_COLOR_WEIGHT, DEFAULT_COLOR_RADIUS, DEFAULT_COLOR_KMIN = 0.9, 3.0, 6
+COLOR_MAX_RADIUS, COLOR_MIN_KMIN, COLOR_MAX_KMIN = 16.0, 3, 1 << 20
+INTENSITY_SCALE = 2550000    # 255 * (2126 + 7152 + 722)
+GRADIENT_BAD_INPUT, GRADIENT_TOO_DENSE = 255, 254              # what pcgc_color_gradient leaves in `valid` when its flag is raised
 # global alignment, grid units (neighbouring surface points about 1 apart): keypoints are the voxels ICP sees; a radius of 8
 # holds about 200 of them on a surface, enough for an 11-bin histogram and small enough to be local; a pair counts as an
 # inlier within 2, so the pose it votes for lands inside ICP's first gate of 4; triangles with a side under 6 fix a rotation
@@ -93,7 +104,34 @@ def solve_plane(S):
     cond = np.linalg.cond(A) if np.isfinite(A).all() else float("inf")
     if not cond <= COND_LIMIT:
         raise ValueError("icp: the point-to-plane system is singular (condition %.3g): the matched surface does not fix all six "
-                         "motions, as a plane, a sphere or too few pairs do not; use metric='point' or scans with more shape" % cond)
+                         "motions, as a plane, a sphere or too few pairs do not; use metric='color' when the scans carry texture, metric='point', or scans "
+                         "with more shape" % cond)
+    x = np.linalg.solve(A, g)
+    return rodrigues(x[:3]), x[3:]
+
+
+def color_system(S, weight):
+    """the joint system of the colour metric from the 59 sums -> (A symmetric 6x6, g): (1 - weight) times the point-to-plane
+    normal equations plus weight times the photometric ones"""
+    S = np.asarray(S, np.float64)
+    lam = float(weight)
+    if not 0.0 < lam < 1.0:
+        raise ValueError("icp: color_weight must lie strictly between 0 and 1 (got %r): 0 is metric='plane', and colour alone "
+                         "does not see the motion along the normals" % (weight,))
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = (1.0 - lam) * S[2:23] + lam * S[31:52]
+    return A + np.triu(A, 1).T, -((1.0 - lam) * S[23:29] + lam * S[52:58])
+
+
+def solve_color(S, weight):
+    """the joint normal equations A x = g of the colour metric -> (dR = the exact rotation of x[:3], dt = x[3:]).  Distances
+    are in voxels and intensities in [0, 1]: the weight balances those units."""
+    A, g = color_system(S, weight)
+    cond = np.linalg.cond(A) if np.isfinite(A).all() else float("inf")
+    if not cond <= COND_LIMIT:
+        raise ValueError("icp: the joint point-to-plane and colour system is singular (condition %.3g): neither the matched surface "
+                         "nor its texture fixes all six motions, as a plane of one colour or too few pairs do not; %d of the pairs "
+                         "have an intensity gradient" % (cond, int(round(S[30]))))
     x = np.linalg.solve(A, g)
     return rodrigues(x[:3]), x[3:]
 
@@ -147,6 +185,7 @@ def _float32_cloud(points, what):
 class Matcher(object):
     """A target cloud prepared once on the device (pcgc_register_prepare), and steps of a source cloud against it.
     source, target: float32 [n,3] / [m,3] in grid units; target_normals float [m,3] or None (point-to-point sums only)."""
+    n_sums, workspace_bytes = N_SUMS, "pcgc_register_workspace_bytes"
 
     def __init__(self, source, target, target_normals=None):
         import torch
@@ -167,8 +206,8 @@ class Matcher(object):
         t64 = target.astype(np.float64)
         self.lo, self.hi = t64.min(0), t64.max(0)
         lib = _lib.hip()
-        self.ws = torch.empty(int(lib.pcgc_register_workspace_bytes(self.cells.res, self.m)), dtype=torch.uint8, device=dev)
-        self.out = torch.empty(N_SUMS, dtype=torch.float64, device=dev)
+        self.ws = torch.empty(int(getattr(lib, self.workspace_bytes)(self.cells.res, self.m)), dtype=torch.uint8, device=dev)
+        self.out = torch.empty(self.n_sums, dtype=torch.float64, device=dev)
         _lib.check(lib.pcgc_register_prepare(_lib.dptr(self.cells.points), self.m, *self.cells.grid(), _lib.dptr(self.ws),
                                              self.ws.numel(), _lib.stream()), "pcgc_register_prepare")
 
@@ -185,6 +224,7 @@ class Matcher(object):
         order = torch.sort((cell[:, 0] * self.cells.res + cell[:, 1]) * self.cells.res + cell[:, 2], stable=True)[1]
         self.source_d = self.source_d[order].contiguous()
         self.order = order if self.order is None else self.order[order]
+        return order
 
     @property
     def centre(self):
@@ -219,6 +259,131 @@ class Matcher(object):
         return S
 
 
+# ---------------------------------------------------------------------------- the colour metric on the device
+def intensity(colors, n, what):
+    """colours [n,3] with whole values in 0..255 -> Y int32 [n] = 2126 R + 7152 G + 722 B (BT.709 in integers, 0 .. 2 550 000)"""
+    c = np.asarray(colors)
+    if c.size != 3 * n:
+        raise ValueError("icp: %d %s colours for %d points" % (c.size // 3 if c.size % 3 == 0 else -1, what, n))
+    c = c.reshape(n, 3)
+    with np.errstate(invalid="ignore"):
+        whole = c.dtype.kind in "ui" or bool(np.all(np.isfinite(c)) and np.all(c == np.rint(c)))
+    if c.dtype.kind not in "uif" or not whole or (c.size and (c.min() < 0 or c.max() > 255)):
+        raise ValueError("icp: the %s colours must be whole numbers in 0..255 (uint8 red, green, blue)" % what)
+    c = c.astype(np.int32)
+    return np.ascontiguousarray(2126 * c[:, 0] + 7152 * c[:, 1] + 722 * c[:, 2], np.int32)
+
+
+def check_color_options(color_weight, color_radius, color_kmin):
+    if not (np.isfinite(color_weight) and 0.0 < color_weight < 1.0):
+        raise ValueError("icp: color_weight must lie strictly between 0 and 1 (got %r)" % (color_weight,))
+    if not (np.isfinite(color_radius) and 0.0 < color_radius <= COLOR_MAX_RADIUS):
+        raise ValueError("icp: color_radius must be positive and at most %g voxels (got %r)" % (COLOR_MAX_RADIUS, color_radius))
+    if not COLOR_MIN_KMIN <= int(color_kmin) <= COLOR_MAX_KMIN:
+        raise ValueError("icp: color_kmin outside %d..%d (got %r)" % (COLOR_MIN_KMIN, COLOR_MAX_KMIN, color_kmin))
+
+
+def color_gradient_step(points_d, normals_d, Y_d, cells, radius, kmin, debug=False):
+    """pcgc_color_gradient on device tensors sorted by the key of `cells` (cells_from_bounds, cell_order): points float32
+    [n,3], unit normals float32 [n,3], Y int32 [n] -> (g float64 [n,3], valid uint8 [n]) device tensors, with debug also K int32
+    [n], Q int64 [n,6], B int64 [n,3].  RuntimeError when the call raised its flag."""
+    import torch
+    n, dev = int(points_d.shape[0]), points_d.device
+    lib = _lib.hip()
+    ws = torch.empty(max(1, int(lib.pcgc_color_gradient_workspace_bytes(cells[4], n))), dtype=torch.uint8, device=dev)
+    g = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    valid = torch.empty(n, dtype=torch.uint8, device=dev)
+    K = torch.empty(n, dtype=torch.int32, device=dev) if debug else None
+    Q = torch.empty((n, 6), dtype=torch.int64, device=dev) if debug else None
+    B = torch.empty((n, 3), dtype=torch.int64, device=dev) if debug else None
+    _lib.check(lib.pcgc_color_gradient(_lib.dptr(points_d), _lib.dptr(normals_d), _lib.dptr(Y_d), n, *cells, float(radius), int(kmin),
+                                       _lib.dptr(g), _lib.dptr(valid), _lib.dptr(K), _lib.dptr(Q), _lib.dptr(B), _lib.dptr(ws), ws.numel(),
+                                       _lib.stream()), "pcgc_color_gradient")
+    worst = int(valid.max().item())
+    if worst == GRADIENT_TOO_DENSE:
+        raise RuntimeError("pcgc_color_gradient: a point has more than %d neighbours within %g voxels: the radius is too large for "
+                           "this density; use a smaller color_radius or a coarser grid" % (COLOR_MAX_KMIN, radius))
+    if worst == GRADIENT_BAD_INPUT:
+        raise RuntimeError("pcgc_color_gradient: a coordinate is not finite or leaves the cells, an intensity lies outside 0..%d, or "
+                           "the points are not sorted by cell (include/pcgc.h)" % INTENSITY_SCALE)
+    return (g, valid, K, Q, B) if debug else (g, valid)
+
+
+def color_gradient(points, normals, Y, radius=DEFAULT_COLOR_RADIUS, kmin=DEFAULT_COLOR_KMIN, debug=False):
+    """The intensity gradients of a cloud (float32 [n,3] grid units, normals [n,3], Y int32 [n]) in the caller's order ->
+    (g float64 [n,3], valid bool [n]) device tensors; debug: also K, Q, B.  The points are sorted by cell for the kernel."""
+    import torch
+    dev = _lib.require_gpu()
+    p = _float32_cloud(points, "target")
+    if not np.isfinite(p).all():
+        raise ValueError("icp: metric='color' takes a target with finite coordinates")
+    p64 = p.astype(np.float64)
+    try:
+        cells = cells_from_bounds(p64.min(0), p64.max(0), float(radius), "icp")
+    except ValueError as e:
+        raise ValueError(str(e).replace("keypoints", "a target"))
+    p_d = torch.from_numpy(p).to(dev)
+    order = cell_order(p_d, cells)
+    n_d = torch.from_numpy(_unit_normals(normals, len(p))).to(dev)
+    Y_d = torch.from_numpy(np.ascontiguousarray(Y, np.int32).reshape(len(p))).to(dev)
+    got = color_gradient_step(p_d[order].contiguous(), n_d[order].contiguous(), Y_d[order].contiguous(), cells, radius, kmin, debug)
+    back = [torch.empty_like(a).index_copy_(0, order, a) for a in got]
+    back[1] = back[1] != 0
+    return tuple(back)
+
+
+class ColorMatcher(Matcher):
+    """Matcher for metric="color": the source's and the target's intensities travel with the points, and the target's
+    intensity gradients are fitted once (pcgc_color_gradient) and kept in the matcher's cell order.  colours: whole numbers
+    in 0..255, [n,3] / [m,3]; the target's normals are required."""
+    n_sums, workspace_bytes = N_COLOR_SUMS, "pcgc_register_color_workspace_bytes"
+
+    def __init__(self, source, target, target_normals, source_colors, target_colors, color_radius=DEFAULT_COLOR_RADIUS,
+                 color_kmin=DEFAULT_COLOR_KMIN):
+        import torch
+        if target_normals is None or source_colors is None or target_colors is None:
+            raise ValueError("icp: metric='color' needs the target's normals and the colours of both clouds")
+        Yp = intensity(source_colors, len(_float32_cloud(source, "source")), "source")
+        Yq = intensity(target_colors, len(_float32_cloud(target, "target")), "target")
+        Matcher.__init__(self, source, target, target_normals)
+        dev = self.source_d.device
+        grad, valid = color_gradient(target, target_normals, Yq, color_radius, color_kmin)
+        self.Yp_d = torch.from_numpy(Yp).to(dev)
+        self.Yq_d = torch.from_numpy(Yq).to(dev)[self.cells.order].contiguous()
+        self.grad_d = grad[self.cells.order].contiguous()
+        self.valid_d = valid.to(torch.uint8)[self.cells.order].contiguous()
+        self.n_valid = int(valid.sum().item())
+
+    def sort_source(self, R, t):
+        order = Matcher.sort_source(self, R, t)
+        self.Yp_d = self.Yp_d[order].contiguous()
+        return order
+
+    def step(self, R, t, c, max_dist, with_normals=True, per_point=False):
+        """-> S float64 [59]; per_point=True: (S, best float64 [n], ties int32 [n])"""
+        import torch
+        R9 = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9))
+        t3 = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
+        c3 = np.ascontiguousarray(np.asarray(c, np.float64).reshape(3))
+        dev = self.source_d.device
+        best = torch.empty(self.n, dtype=torch.float64, device=dev) if per_point else None
+        ties = torch.empty(self.n, dtype=torch.int32, device=dev) if per_point else None
+        _lib.check(_lib.hip().pcgc_register_color_step(
+            _lib.dptr(self.source_d), _lib.dptr(self.Yp_d), self.n, _lib.dptr(self.cells.points), _lib.dptr(self.normals_d),
+            _lib.dptr(self.Yq_d), _lib.dptr(self.grad_d), _lib.dptr(self.valid_d), self.m, *self.cells.grid(), _lib.nptr(R9), _lib.nptr(t3),
+            _lib.nptr(c3), float(max_dist), _lib.dptr(self.out), _lib.dptr(best), _lib.dptr(ties), _lib.dptr(self.ws), self.ws.numel(),
+            _lib.stream()), "pcgc_register_color_step")
+        S = self.out.cpu().numpy().copy()
+        if np.isnan(S).any():
+            raise RuntimeError("pcgc_register_color_step: a moved source coordinate is not finite or leaves every cell's reach, or "
+                               "the target breaks the cell rule (include/pcgc.h)")
+        if per_point:
+            if self.order is not None:
+                best, ties = torch.empty_like(best).index_copy_(0, self.order, best), torch.empty_like(ties).index_copy_(0, self.order, ties)
+            return S, best.cpu().numpy(), ties.cpu().numpy()
+        return S
+
+
 # ---------------------------------------------------------------------------- the loop
 def _schedule(max_dist):
     gates = [float(g) for g in (max_dist if isinstance(max_dist, (tuple, list, np.ndarray)) else (max_dist,))]
@@ -230,24 +395,52 @@ def _schedule(max_dist):
 def check_arguments(metric, have_normals, estimate_normals=False, iters=50, tol=1e-3):
     """the argument errors of icp / register_scans, before any work"""
     if metric not in MIN_PAIRS:
-        raise ValueError("icp: metric must be 'plane' or 'point' (got %r)" % (metric,))
-    if metric == "plane" and not have_normals and not estimate_normals:
-        raise ValueError("icp: metric='plane' needs the target's normals: give them, estimate them (estimate_normals / "
-                         "--estimate_normals), or use metric='point'")
+        raise ValueError("icp: metric must be 'plane', 'point' or 'color' (got %r)" % (metric,))
+    if metric in ("plane", "color") and not have_normals and not estimate_normals:
+        raise ValueError("icp: metric='%s' needs the target's normals: give them, estimate them (estimate_normals / "
+                         "--estimate_normals), or use metric='point'" % metric)
     if int(iters) < 1 or not (np.isfinite(tol) and tol > 0):
         raise ValueError("icp: iters must be at least 1 and tol positive (got %r, %r)" % (iters, tol))
 
 
-def icp(source, target, target_normals=None, metric="plane", max_dist=DEFAULT_MAX_DIST, iters=50, tol=1e-3, init=None):
+def _rows(a):
+    a = np.asarray(a)
+    return a.size // 3 if a.size % 3 == 0 else -1
+
+
+def check_color_arguments(n_source, n_target, source_colors, target_colors, color_weight, color_radius, color_kmin):
+    """the argument errors of metric='color', before any work"""
+    check_color_options(color_weight, color_radius, color_kmin)
+    if source_colors is None or target_colors is None:
+        raise ValueError("icp: metric='color' needs source_colors and target_colors (%s missing): scans without colours register "
+                         "with metric='plane' or 'point'" % ("both are" if source_colors is None and target_colors is None else
+                                                               "source_colors is" if source_colors is None else "target_colors is"))
+    for a, n, what in ((source_colors, n_source, "source"), (target_colors, n_target, "target")):
+        if _rows(a) != n:
+            raise ValueError("icp: %d %s colours for %d %s points" % (_rows(a), what, n, what))
+
+
+def icp(source, target, target_normals=None, metric="plane", max_dist=DEFAULT_MAX_DIST, iters=50, tol=1e-3, init=None,
+        source_colors=None, target_colors=None, color_weight=DEFAULT_COLOR_WEIGHT, color_radius=DEFAULT_COLOR_RADIUS,
+        color_kmin=DEFAULT_COLOR_KMIN):
     """Align `source` to `target` (float32 [n,3] / [m,3], grid units) from the pose init = (R, t), identity when None ->
     dict: R, t (target ~ R source + t), iterations (per stage), converged, n_used, fitness = n_used / n, rmse =
-    sqrt(sum of best / n_used), plane_rmse (plane mode, else None).  Each entry of max_dist is a stage of at most `iters`
-    steps that ends when the last step moved no point of the target's bounding box by `tol`; one more step at the final
-    pose gives the figures.  ValueError: nothing within max_dist, or a singular point-to-plane system."""
+    sqrt(sum of best / n_used), plane_rmse (plane and colour mode, else None).  Each entry of max_dist is a stage of at most
+    `iters` steps that ends when the last step moved no point of the target's bounding box by `tol`; one more step at the
+    final pose gives the figures.  ValueError: nothing within max_dist, or a singular system.
+    metric="color": source_colors and target_colors ([n,3] / [m,3], whole numbers in 0..255) are required with the target's
+    normals; color_weight in (0, 1) is the photometric share of the joint objective; the target's intensity gradients are
+    fitted over the points within color_radius voxels, at least color_kmin of them.  The result gains color_rmse =
+    sqrt(sum of w rc^2 / sum of w) over the pairs whose target point has a gradient, in intensity units of [0, 1], and
+    color_fitness = that sum of w / n_used."""
     check_arguments(metric, target_normals is not None, False, iters, tol)
     gates = _schedule(max_dist)
-    plane = metric == "plane"
-    m = Matcher(source, target, target_normals if plane else None)
+    plane, color = metric == "plane", metric == "color"
+    if color:
+        check_color_arguments(_rows(source), _rows(target), source_colors, target_colors, color_weight, color_radius, color_kmin)
+        m = ColorMatcher(source, target, target_normals, source_colors, target_colors, color_radius, color_kmin)
+    else:
+        m = Matcher(source, target, target_normals if plane else None)
     c, rho = m.centre, m.radius
     R, t = (np.eye(3), np.zeros(3)) if init is None else (np.array(init[0], np.float64).reshape(3, 3), np.array(init[1], np.float64).reshape(3))
     iterations, converged = [], True
@@ -257,7 +450,7 @@ def icp(source, target, target_normals=None, metric="plane", max_dist=DEFAULT_MA
         while k < int(iters) and not done:
             S = m.step(R, t, c, gate, plane)
             _check_pairs(S, metric, gate)
-            dR, dt = solve_plane(S) if plane else solve_point(S)
+            dR, dt = solve_color(S, color_weight) if color else solve_plane(S) if plane else solve_point(S)
             R, t = compose(R, t, c, dR, dt)
             k += 1
             done = rotation_angle(dR) * rho + float(np.linalg.norm(dt)) < tol
@@ -265,9 +458,13 @@ def icp(source, target, target_normals=None, metric="plane", max_dist=DEFAULT_MA
         converged = converged and done
     S = m.step(R, t, c, gates[-1], plane)
     n_used = int(S[0])
-    return {"R": R, "t": t, "iterations": iterations, "converged": converged, "n_used": n_used, "fitness": n_used / m.n,
-            "rmse": math.sqrt(S[1] / n_used) if n_used else float("nan"),
-            "plane_rmse": (math.sqrt(S[44] / n_used) if n_used else float("nan")) if plane else None}
+    out = {"R": R, "t": t, "iterations": iterations, "converged": converged, "n_used": n_used, "fitness": n_used / m.n,
+           "rmse": math.sqrt(S[1] / n_used) if n_used else float("nan"),
+           "plane_rmse": (math.sqrt(S[29 if color else 44] / n_used) if n_used else float("nan")) if plane or color else None}
+    if color:
+        out["color_rmse"] = math.sqrt(S[58] / S[30]) if S[30] > 0 else float("nan")
+        out["color_fitness"] = S[30] / n_used if n_used else float("nan")
+    return out
 
 
 # ---------------------------------------------------------------------------- global alignment: the device stages
@@ -599,7 +796,8 @@ def _finite_scan(k, scan):
 
 
 def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=DEFAULT_MAX_DIST, iters=50, tol=1e-3, init=None,
-                   estimate_normals=False, clean=None, names=None, global_init=False, global_options=None, smooth=None):
+                   estimate_normals=False, clean=None, names=None, global_init=False, global_options=None, smooth=None,
+                   color_weight=DEFAULT_COLOR_WEIGHT, color_radius=DEFAULT_COLOR_RADIUS, color_kmin=DEFAULT_COLOR_KMIN):
     """scans: list of (points float64 [n,3] in the scanner's units, colors uint8 [n,3] | None, normals [n,3] | None).  Scan 0
     defines the coordinates; scan k >= 1 is registered against the union of scan 0 and the aligned scans before it, on the
     grid of the ingest.Frame fitted to that union with bits / voxel_size.  init: per scan None or (R, t) in scan units;
@@ -608,6 +806,8 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
     unchanged, and the scan's pose entry gains "global": inliers, correspondences, hypotheses, draw.
     smooth (a --smooth spec, pcgcv1_amd/smooth.py): the aligned union's positions are smoothed just before the merge, which is
     where the sheets of the same surface lie on top of each other; the result gains "smooth", the line the command prints.
+    metric="color": every scan needs colours (the union's travel along as the target's); the target's normals follow the rule
+    of "plane"; color_weight, color_radius and color_kmin are icp's.
     -> dict: merged = ingest.voxelize_scan(union, ..., clean=clean) as it returns it, poses = per scan the icp result with
     R, t in scan units and "pose" the 4x4 matrix (scan 0: the identity), aligned = the union's (points, colors, normals), as
     registered: not smoothed."""
@@ -616,6 +816,12 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
         raise ValueError("register_scans: no scans")
     # the targets are the scans before the last: every one of them needs normals for the plane metric
     check_arguments(metric, all((tuple(s) + (None, None))[2] is not None for s in scans[:-1]), estimate_normals, iters, tol)
+    if metric == "color":
+        check_color_options(color_weight, color_radius, color_kmin)
+        for k, scan in enumerate(scans):
+            if (tuple(scan) + (None,))[1] is None:
+                raise ValueError("register_scans: metric='color' needs the colours of every scan, and %s has none: use metric='plane' "
+                                 "or 'point'" % (names[k] if names else "scan %d" % k))
     if (bits is None) == (voxel_size is None):
         raise ValueError("register_scans: give bits or voxel_size, one of them")
     gates = _schedule(max_dist)
@@ -631,7 +837,7 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
         target = np.concatenate(pts)
         frame = ingest.fit_frame(target, bits=bits, voxel_size=voxel_size)
         tn = None
-        if metric == "plane":
+        if metric in ("plane", "color"):
             tn = np.concatenate(nrms) if all(n is not None for n in nrms) else estimated_target_normals(target, frame)
         start = None if init is None or init[k] is None else pose_from_scan_units(init[k][0], init[k][1], frame)
         coarse = None
@@ -644,7 +850,11 @@ def register_scans(scans, bits=None, voxel_size=None, metric="plane", max_dist=D
                 own = nrm if nrm is not None else estimated_target_normals(p, ingest.fit_frame(p, voxel_size=frame.step))
                 coarse = global_align(to_grid(p, frame), to_grid(target, frame), own, given, **(global_options or {}))
                 start = (coarse["R"], coarse["t"])
-            r = icp(to_grid(p, frame), to_grid(target, frame), tn, metric, gates, iters, tol, start)
+            if metric == "color":
+                r = icp(to_grid(p, frame), to_grid(target, frame), tn, metric, gates, iters, tol, start, source_colors=col,
+                        target_colors=np.concatenate(cols), color_weight=color_weight, color_radius=color_radius, color_kmin=color_kmin)
+            else:
+                r = icp(to_grid(p, frame), to_grid(target, frame), tn, metric, gates, iters, tol, start)
         except ValueError as e:
             raise ValueError("%s: %s" % (names[k] if names else "scan %d" % k, e))
         if coarse is not None:
@@ -677,6 +887,9 @@ def write_poses(filename, names, poses):
                 "rmse": float(r["rmse"]), "plane_rmse": None if r["plane_rmse"] is None else float(r["plane_rmse"])}
                for name, r in zip(names, poses)]
     for e, r in zip(entries, poses):
+        for key in ("color_rmse", "color_fitness"):            # metric="color" only
+            if key in r:
+                e[key] = float(r[key])
         if "global" in r:                                      # the coarse start the scan's icp began from (--global_init)
             e["global"] = {key: int(v) for key, v in r["global"].items()}
     with open(filename, "w") as f:
@@ -698,10 +911,27 @@ def read_poses(filename):
 
 
 # ---------------------------------------------------------------------------- command line
+def _ply_has_colors(filename):
+    """whether the ply's header declares one of the colour triples load_ply_scan reads (False for a file that is missing or
+    has no header)"""
+    from .dataprocess.inout_points import _COLOR_NAMES
+    try:
+        with open(filename, "rb") as f:
+            head = f.read(1 << 16)
+    except (OSError, TypeError):
+        return False
+    end = head.find(b"end_header")
+    if end < 0:
+        return False
+    props = {ln.split()[-1].decode("ascii", "replace") for ln in head[:end].split(b"\n") if ln.strip().startswith(b"property")}
+    return any(set(names) <= props for names in _COLOR_NAMES)
+
+
 def summary_line(name, r):
-    return "register: {}: {} steps {}, {}, fitness {:.4f}, rmse {:.4f}{}".format(
+    return "register: {}: {} steps {}, {}, fitness {:.4f}, rmse {:.4f}{}{}".format(
         name, sum(r["iterations"]), r["iterations"], "converged" if r["converged"] else "NOT converged", r["fitness"], r["rmse"],
-        "" if r["plane_rmse"] is None else ", plane rmse {:.4f}".format(r["plane_rmse"]))
+        "" if r["plane_rmse"] is None else ", plane rmse {:.4f}".format(r["plane_rmse"]),
+        "" if "color_rmse" not in r else ", colour rmse {:.4f}, colour fitness {:.4f}".format(r["color_rmse"], r["color_fitness"]))
 
 
 def parse_args(argv=None):
@@ -711,7 +941,16 @@ def parse_args(argv=None):
     ap.add_argument("--output", required=True, help="the voxelised ply; <output without .ply>.frame and .poses.json are written next to it")
     ap.add_argument("--bits", type=int, default=None, help="fit the union into a grid of 2^bits cells per axis (1..12)")
     ap.add_argument("--voxel_size", type=float, default=None, help="voxel edge in the scans' units; the grid grows to hold the union")
-    ap.add_argument("--metric", choices=("plane", "point"), default="plane")
+    ap.add_argument("--metric", choices=("plane", "point", "color"), default="plane",
+                    help="color: point-to-plane plus a photometric term, for scans whose shape leaves a motion free (a wall, a vase, a "
+                         "sphere) and whose texture does not; every scan needs red, green and blue")
+    ap.add_argument("--color_weight", type=float, default=DEFAULT_COLOR_WEIGHT,
+                    help="--metric=color: the photometric share of the joint objective, strictly between 0 and 1 (default %(default)g)")
+    ap.add_argument("--color_radius", type=float, default=DEFAULT_COLOR_RADIUS,
+                    help="--metric=color: the target's intensity gradients are fitted over the points within this many voxels "
+                         "(default %(default)g, at most 16)")
+    ap.add_argument("--color_kmin", type=int, default=DEFAULT_COLOR_KMIN,
+                    help="--metric=color: a target point with fewer such points, itself included, has no gradient (default %(default)d)")
     ap.add_argument("--max_dist", default="4,2,1", help="the gates of the stages in voxels, coarse to fine")
     ap.add_argument("--iters", type=int, default=50, help="most steps per stage")
     ap.add_argument("--tol", type=float, default=1e-3, help="a stage ends when a step moves the target's box by less (voxels)")
@@ -760,13 +999,22 @@ def parse_args(argv=None):
         ap.error("--iters must be at least 1 and --tol positive")
     if len(args.input) < 2:
         ap.error("--input takes two scans or more: one has nothing to be registered against")
-    if args.metric == "plane" and not args.estimate_normals:
+    if args.metric == "color":
+        try:
+            check_color_options(args.color_weight, args.color_radius, args.color_kmin)
+        except ValueError as e:
+            ap.error(str(e).replace("icp: color_", "--color_"))
+        for name in args.input:                               # the headers only: no scan is parsed yet
+            if not _ply_has_colors(name):
+                ap.error("--metric=color needs colours: %s has no red green blue properties (or cannot be read); use --metric=plane "
+                         "or --metric=point" % name)
+    if args.metric in ("plane", "color") and not args.estimate_normals:
         # with the other argument errors, before anything is loaded: the plane metric measures against the target's normals
         from .test import _ply_has_normals
         for name in args.input[:-1]:
             if not _ply_has_normals(name):
-                ap.error("--metric=plane needs normals: %s has no nx ny nz properties (or cannot be read); pass --estimate_normals "
-                         "to estimate them, or --metric=point" % name)
+                ap.error("--metric=%s needs normals: %s has no nx ny nz properties (or cannot be read); pass --estimate_normals "
+                         "to estimate them, or --metric=point" % (args.metric, name))
     if args.global_init and args.init is not None:
         ap.error("--global_init finds the start itself: not together with --init")
     for name in ("feature_voxel", "feature_radius", "corr_dist"):
@@ -802,7 +1050,8 @@ def main(argv=None):
                    "seed": args.seed}
         out = register_scans(scans, args.bits, args.voxel_size, args.metric, args.max_dist, args.iters, args.tol, init,
                              args.estimate_normals, args.clean, names=args.input, global_init=args.global_init,
-                             global_options=options, smooth=args.smooth)
+                             global_options=options, smooth=args.smooth, color_weight=args.color_weight,
+                             color_radius=args.color_radius, color_kmin=args.color_kmin)
     except ValueError as e:
         raise SystemExit("register: %s" % e)
     failed = []
