@@ -3,10 +3,11 @@
 // DESIGN.md §7k state the rule; tests/_color_icp_ref.py restates it in numpy; pcgcv1_amd/register.py calls it once per target
 // and hands the result to pcgc_register_color_step (offgrid.hip).
 //
-// Built like smooth.hip.  The least-squares sums over the ball around a point are exact integers (offsets in 2^-16 of a grid
-// unit, intensities in 1 / 2 550 000, summed in int64), so they do not depend on the order the neighbours are met in;
-// everything behind them is IEEE float64, one operation per step in the order written (-ffp-contract=off).  The device and
-// numpy therefore agree bit for bit.
+// Built like smooth.hip, on the same walk (for_each_in_window), flag kernel and size check of offgrid_cells.h.  The
+// least-squares sums over the ball around a point are exact integers (offsets in 2^-16 of a grid unit, intensities in
+// 1 / 2 550 000, summed in int64), so they do not depend on the order the neighbours are met in; everything behind them is
+// IEEE float64, one operation per step in the order written (-ffp-contract=off).  The device and numpy therefore agree bit
+// for bit.
 //
 // One thread per point, the points in cell order (offgrid_cells.h): the lanes of a wave walk the same 27 cell ranges.  The
 // nine sums and the count live in registers; there are no atomics on data, no LDS and no scratch (DESIGN.md §7k quotes the
@@ -25,8 +26,6 @@ constexpr int kGradMaxK = 1 << 20;                  // ... and 2^20 terms stay i
 constexpr int kGradMaxY = 2550000;                  // 255 * (2126 + 7152 + 722)
 constexpr double kGradScale = 65536.0;
 constexpr double kGradDetFloor = 1e-6;
-constexpr int kFlagInput = 1, kFlagDense = 2;
-constexpr uint8_t kValidBadInput = 255, kValidTooDense = 254;
 
 __global__ void __launch_bounds__(256) color_gradient_kernel(Target t, int64_t n, const float* normals, const int32_t* Y, double r2,
                                                              int kmin, double* grad, uint8_t* valid, int32_t* Kout, int64_t* Qout,
@@ -41,31 +40,22 @@ __global__ void __launch_bounds__(256) color_gradient_kernel(Target t, int64_t n
   bool dense = false;
   int cell[3];
   if (cell_of_point(t.c, g, cell) && yi >= 0 && yi <= kGradMaxY) {
-    const int res = t.c.res;
-    const int x0 = max(cell[0] - 1, 0), x1 = min(cell[0] + 1, res - 1), y0 = max(cell[1] - 1, 0), y1 = min(cell[1] + 1, res - 1);
-    const int z0 = max(cell[2] - 1, 0), z1 = min(cell[2] + 1, res - 1);
-    for (int x = x0; x <= x1; ++x)
-      for (int y = y0; y <= y1; ++y)
-        for (int z = z0; z <= z1; ++z) {
-          if (!bit_at(t.bits, res, x, y, z)) continue;
-          const int64_t r = rank_of(t.bits, t.rank, cell_of(res, x, y, z));
-          for (int32_t j = t.start[r], end = t.start[r + 1]; j < end; ++j) {
-            const float* q = t.q + (int64_t)j * 3;
-            if (!(dist2(q, px, py, pz) <= r2)) continue;       // false for a NaN
-            if (K == kGradMaxK) {
-              dense = true;
-              continue;
-            }
-            const int64_t a = llrint(((double)q[0] - px) * kGradScale);
-            const int64_t b = llrint(((double)q[1] - py) * kGradScale);
-            const int64_t c = llrint(((double)q[2] - pz) * kGradScale);
-            // a neighbour's intensity outside the range raises the flag in its own thread; clamped here, it cannot overflow a sum
-            const int64_t dy = (int64_t)min(max(Y[j], 0), kGradMaxY) - (int64_t)yi;
-            ++K;
-            q00 += a * a; q01 += a * b; q02 += a * c; q11 += b * b; q12 += b * c; q22 += c * c;
-            b0 += a * dy; b1 += b * dy; b2 += c * dy;
-          }
-        }
+    for_each_in_window(t, window_of(cell, 1, t.c.res), [&](int32_t j) {
+      const float* q = t.q + (int64_t)j * 3;
+      if (!(dist2(q, px, py, pz) <= r2)) return;           // false for a NaN
+      if (K == kGradMaxK) {
+        dense = true;
+        return;
+      }
+      const int64_t a = llrint(((double)q[0] - px) * kGradScale);
+      const int64_t b = llrint(((double)q[1] - py) * kGradScale);
+      const int64_t c = llrint(((double)q[2] - pz) * kGradScale);
+      // a neighbour's intensity outside the range raises the flag in its own thread; clamped here, it cannot overflow a sum
+      const int64_t dy = (int64_t)min(max(Y[j], 0), kGradMaxY) - (int64_t)yi;
+      ++K;
+      q00 += a * a; q01 += a * b; q02 += a * c; q11 += b * b; q12 += b * c; q22 += c * c;
+      b0 += a * dy; b1 += b * dy; b2 += c * dy;
+    });
   } else {
     atomicOr(bad, kFlagInput);
   }
@@ -109,16 +99,6 @@ __global__ void __launch_bounds__(256) color_gradient_kernel(Target t, int64_t n
   valid[i] = 1;
 }
 
-// what a raised flag does to `valid`: one value everywhere that names the cause
-__global__ void __launch_bounds__(256) color_gradient_flag_kernel(const int* bad, int64_t n, uint8_t* valid) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int flag = *bad;
-  if (i >= n || !flag) return;
-  valid[i] = (flag & kFlagInput) ? kValidBadInput : kValidTooDense;
-}
-
-bool gradient_sizes_ok(int res, int64_t n) { return res >= 1 && res <= kOffgridMaxRes && n > 0 && n < 0x7FFFFFFF; }
-
 }  // namespace
 }  // namespace pcgc
 
@@ -126,12 +106,12 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_color_gradient_workspace_bytes(int res, int64_t n) { return gradient_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
+size_t pcgc_color_gradient_workspace_bytes(int res, int64_t n) { return cloud_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
 
 int pcgc_color_gradient(const float* points, const float* normals, const int32_t* Y, int64_t n, double h, int ox, int oy, int oz, int res,
                         double radius, int kmin, double* g, uint8_t* valid, int32_t* K, int64_t* Q, int64_t* B, void* workspace,
                         size_t workspace_bytes, pcgc_stream_t stream) {
-  PCGC_REQUIRE(points && normals && Y && g && valid && workspace && gradient_sizes_ok(res, n) && grid_ok(h, ox, oy, oz, res, n, n),
+  PCGC_REQUIRE(points && normals && Y && g && valid && workspace && cloud_sizes_ok(res, n) && grid_ok(h, ox, oy, oz, res, n, n),
                "pcgc_color_gradient: bad arguments");
   PCGC_REQUIRE((K != nullptr) == (Q != nullptr) && (K != nullptr) == (B != nullptr),
                "pcgc_color_gradient: K, Q and B come together or not at all");
@@ -146,7 +126,7 @@ int pcgc_color_gradient(const float* points, const float* normals, const int32_t
   if (rc) return rc;
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(color_gradient_kernel, dim3(grid), dim3(256), 0, s, t, n, normals, Y, radius * radius, kmin, g, valid, K, Q, B, b.bad);
-  hipLaunchKernelGGL(color_gradient_flag_kernel, dim3(grid), dim3(256), 0, s, b.bad, n, valid);
+  hipLaunchKernelGGL(flag_marks_kernel, dim3(grid), dim3(256), 0, s, b.bad, n, valid);
   return launch_ok("colour gradient kernels");
 }
 

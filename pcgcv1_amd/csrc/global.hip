@@ -9,8 +9,8 @@
 // Every output is an integer that does not depend on the order the work is done in, so the device and numpy agree bit for bit.
 // The float64 arithmetic in front of the binning is one operation per step in the order written (-ffp-contract=off).
 //
-// Stages 1 and 2 walk the cells of offgrid_cells.h: one wave per keypoint, the cells of the window of r around its cell in
-// wave-uniform loops, the lanes over the points of a cell.  The histogram of stage 1 lives in LDS (33 counters per wave,
+// Stages 1 and 2 walk the cells of offgrid_cells.h (window_of, for_each_run): one wave per keypoint, the cells of the window of
+// r around its cell in wave-uniform loops, the lanes over the points of a cell.  The histogram of stage 1 lives in LDS (33 counters per wave,
 // integer atomicAdd): counters indexed by a run-time bin would otherwise spill to scratch.  Stage 2 needs no atomics: the
 // lanes agree by ballot on the neighbours of a chunk, then lane b < 33 adds bin b of each.
 // Input that breaks the contract (keypoints not sorted by cell or outside the grid, a NaN coordinate) is met with no index
@@ -39,16 +39,6 @@ __device__ __forceinline__ bool usable_normal(const float* n) {
 __device__ __forceinline__ int bin_of(double f) {
   const double x = f * 11.0;
   return x < 10.0 ? (int)floor(x) : 10;
-}
-
-struct Window {
-  int x0, x1, y0, y1, z0, z1;
-};
-
-// the cells within w of `cell`, clipped to the grid (empty when the cell lies further outside than w)
-__device__ __forceinline__ Window window_of(const int cell[3], int w, int res) {
-  return Window{max(cell[0] - w, 0), min(cell[0] + w, res - 1), max(cell[1] - w, 0), min(cell[1] + w, res - 1),
-                max(cell[2] - w, 0), min(cell[2] + w, res - 1)};
 }
 
 // is j a neighbour of i (at p): j != i, 0 < d2 <= r2, a usable normal; d = p - q_j
@@ -84,27 +74,22 @@ __global__ void __launch_bounds__(256) feature_pairs_kernel(Target t, const floa
     if (walk) {
       const double px = t.q[i * 3], py = t.q[i * 3 + 1], pz = t.q[i * 3 + 2];
       const double nx = normals[i * 3], ny = normals[i * 3 + 1], nz = normals[i * 3 + 2];
-      const Window v = window_of(cell, w, t.c.res);
-      for (int x = v.x0; x <= v.x1; ++x)
-        for (int y = v.y0; y <= v.y1; ++y)
-          for (int z = v.z0; z <= v.z1; ++z) {
-            if (!bit_at(t.bits, t.c.res, x, y, z)) continue;
-            const int64_t r = rank_of(t.bits, t.rank, cell_of(t.c.res, x, y, z));
-            for (int32_t j = t.start[r] + lane, end = t.start[r + 1]; j < end; j += 64) {
-              double d[3], d2;
-              if (!is_neighbour(t, normals, i, j, px, py, pz, r2, d, &d2)) continue;
-              const double len = sqrt(d2);
-              const double ux = d[0] / len, uy = d[1] / len, uz = d[2] / len;
-              const double mx = normals[(int64_t)j * 3], my = normals[(int64_t)j * 3 + 1], mz = normals[(int64_t)j * 3 + 2];
-              const double f1 = fabs((nx * ux + ny * uy) + nz * uz);
-              const double f2 = fabs((mx * ux + my * uy) + mz * uz);
-              const double f3 = fabs((nx * mx + ny * my) + nz * mz);
-              atomicAdd(&hist[wave][bin_of(f1)], 1u);
-              atomicAdd(&hist[wave][kBins + bin_of(f2)], 1u);
-              atomicAdd(&hist[wave][2 * kBins + bin_of(f3)], 1u);
-              ++count;
-            }
-          }
+      for_each_run(t, window_of(cell, w, t.c.res), [&](int32_t first, int32_t end) {
+        for (int32_t j = first + lane; j < end; j += 64) {
+          double d[3], d2;
+          if (!is_neighbour(t, normals, i, j, px, py, pz, r2, d, &d2)) continue;
+          const double len = sqrt(d2);
+          const double ux = d[0] / len, uy = d[1] / len, uz = d[2] / len;
+          const double mx = normals[(int64_t)j * 3], my = normals[(int64_t)j * 3 + 1], mz = normals[(int64_t)j * 3 + 2];
+          const double f1 = fabs((nx * ux + ny * uy) + nz * uz);
+          const double f2 = fabs((mx * ux + my * uy) + mz * uz);
+          const double f3 = fabs((nx * mx + ny * my) + nz * mz);
+          atomicAdd(&hist[wave][bin_of(f1)], 1u);
+          atomicAdd(&hist[wave][kBins + bin_of(f2)], 1u);
+          atomicAdd(&hist[wave][2 * kBins + bin_of(f3)], 1u);
+          ++count;
+        }
+      });
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) count += __shfl_down(count, o, 64);
@@ -117,12 +102,11 @@ __global__ void __launch_bounds__(256) feature_pairs_kernel(Target t, const floa
   }
 }
 
-// what a raised flag does to the outputs of stage 1 (k = -1) or stage 2 (valid = 255)
-__global__ void __launch_bounds__(256) feature_flag_kernel(const int* bad, int64_t n, int32_t* k, uint8_t* valid) {
+// what a raised flag does to the output of stage 1: k = -1 (stage 2: valid = 255, flag_marks_kernel of offgrid_cells.h)
+__global__ void __launch_bounds__(256) feature_flag_kernel(const int* bad, int64_t n, int32_t* k) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n || !*bad) return;
-  if (k) k[i] = -1;
-  if (valid) valid[i] = 255;
+  k[i] = -1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- 2: combine
@@ -137,26 +121,21 @@ __global__ void __launch_bounds__(256) feature_combine_kernel(Target t, const fl
     walk = walk && usable_normal(normals + i * 3);
     if (walk) {
       const double px = t.q[i * 3], py = t.q[i * 3 + 1], pz = t.q[i * 3 + 2];
-      const Window v = window_of(cell, w, t.c.res);
-      for (int x = v.x0; x <= v.x1; ++x)
-        for (int y = v.y0; y <= v.y1; ++y)
-          for (int z = v.z0; z <= v.z1; ++z) {
-            if (!bit_at(t.bits, t.c.res, x, y, z)) continue;
-            const int64_t r = rank_of(t.bits, t.rank, cell_of(t.c.res, x, y, z));
-            for (int32_t first = t.start[r], end = t.start[r + 1]; first < end; first += 64) {
-              const int32_t j = first + lane;
-              double d[3], d2;
-              const bool member = j < end && is_neighbour(t, normals, i, j, px, py, pz, r2, d, &d2);
-              unsigned long long mask = __ballot(member);
-              while (mask) {
-                const int b = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const int64_t jj = (int64_t)first + b;
-                if (lane < kCounters) acc += S[jj * kCounters + lane];
-                else if (lane == kCounters) acc += (unsigned)k[jj];
-              }
-            }
+      for_each_run(t, window_of(cell, w, t.c.res), [&](int32_t first, int32_t end) {
+        for (; first < end; first += 64) {
+          const int32_t j = first + lane;
+          double d[3], d2;
+          const bool member = j < end && is_neighbour(t, normals, i, j, px, py, pz, r2, d, &d2);
+          unsigned long long mask = __ballot(member);
+          while (mask) {
+            const int b = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const int64_t jj = (int64_t)first + b;
+            if (lane < kCounters) acc += S[jj * kCounters + lane];
+            else if (lane == kCounters) acc += (unsigned)k[jj];
           }
+        }
+      });
     }
     const unsigned long long ki = (unsigned)k[i];
     const unsigned long long T = ki * ki + __shfl(acc, kCounters, 64);
@@ -309,7 +288,7 @@ int pcgc_feature_pairs(const float* kp, const float* normals, int64_t n, double 
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, kp, n, s, &t);
   if (rc) return rc;
   hipLaunchKernelGGL(feature_pairs_kernel, dim3(feature_blocks(n)), dim3(256), 0, s, t, normals, n, w, radius * radius, S, k, b.bad);
-  hipLaunchKernelGGL(feature_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.bad, n, k, (uint8_t*)nullptr);
+  hipLaunchKernelGGL(feature_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.bad, n, k);
   return launch_ok("feature pair kernels");
 }
 
@@ -329,7 +308,7 @@ int pcgc_feature_combine(const float* kp, const float* normals, int64_t n, doubl
   if (rc) return rc;
   hipLaunchKernelGGL(feature_combine_kernel, dim3(feature_blocks(n)), dim3(256), 0, s, t, normals, n, w, radius * radius, S, k, feat, valid,
                      b.bad);
-  hipLaunchKernelGGL(feature_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.bad, n, (int32_t*)nullptr, valid);
+  hipLaunchKernelGGL(flag_marks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b.bad, n, valid);
   return launch_ok("feature combine kernels");
 }
 

@@ -7,7 +7,7 @@
 // coordinates as they came, d2 = (dx*dx + dy*dy) + dz*dz with dx = double(p.x) - double(q.x) (the file is built with
 // -ffp-contract=off).  The cells are the occupancy bit set and rank table of voxel_grid.h; Q comes sorted by cell key, so
 // start[rank of a cell] .. start[rank + 1] are the points of that cell, any number of them.  The cells, the kernels that
-// build them and dist2 are in offgrid_cells.h, which global.hip shares.
+// build them, the walk over a window of them and dist2 are in offgrid_cells.h, which global.hip, smooth.hip and color_icp.hip share.
 //
 // One thread per source point p, two passes:
 //   1. Chebyshev shells of cells around p's cell, clipped to the grid, keeping the minimal d2.  A point in an unvisited
@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include "common.h"
-#include "offgrid_cells.h"     // Cells, Target, the cell kernels, dist2, for_each_in_cell, grid_ok, build_cells
+#include "offgrid_cells.h"     // Cells, Target, the cell kernels, dist2, window_of, for_each_in_window / _cell, grid_ok, build_cells
 
 namespace pcgc {
 namespace {
@@ -68,14 +68,10 @@ __device__ __forceinline__ double nearest_offgrid(const Target& t, const int cel
 template <typename F>
 __device__ __forceinline__ void for_each_tied_offgrid(const Target& t, const int cell[3], double px, double py, double pz, double best,
                                                       int shell, F f) {
-  const int last = t.c.res - 1;
-  for (int x = max(cell[0] - shell, 0); x <= min(cell[0] + shell, last); ++x)
-    for (int y = max(cell[1] - shell, 0); y <= min(cell[1] + shell, last); ++y)
-      for (int z = max(cell[2] - shell, 0); z <= min(cell[2] + shell, last); ++z)
-        for_each_in_cell(t, x, y, z, [&](int32_t j) {
-          const float* q = t.q + (int64_t)j * 3;
-          if (fabs(dist2(q, px, py, pz) - best) < kTieEps) f(j, px - (double)q[0], py - (double)q[1], pz - (double)q[2]);
-        });
+  for_each_in_window(t, window_of(cell, shell, t.c.res), [&](int32_t j) {
+    const float* q = t.q + (int64_t)j * 3;
+    if (fabs(dist2(q, px, py, pz) - best) < kTieEps) f(j, px - (double)q[0], py - (double)q[1], pz - (double)q[2]);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- normals
@@ -163,48 +159,96 @@ __global__ void offgrid_mse_final_kernel(const double* partial, int nb, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- registration
-// One ICP step (include/pcgc.h, pcgc_register_step; tests/_register_ref.py): the source under a trial pose, its tied nearest
-// neighbours, and the 45 sums of the point-to-point and point-to-plane normal equations.  The pose travels as a kernel argument.
-constexpr int kRegSums = 45;
-
+// One ICP step (include/pcgc.h, pcgc_register_step and pcgc_register_color_step; tests/_register_ref.py, _color_icp_ref.py): the
+// source under a trial pose, its tied nearest neighbours within the gate, and float64 sums over the pairs in a fixed order.  ONE
+// kernel does the search, the gate, the ties and the reduction; WHICH sums a pair adds to is a small "terms" policy:
+//   PlaneTerms  45 sums: the point-to-point moments and, with normals, the point-to-plane normal equations
+//   ColorTerms  59 sums: the point-to-plane block, the count of valid pairs, the photometric block over the
+//               target's intensity gradients (pcgc_color_gradient, color_icp.hip); no moments, so the sums stay in registers
+// Sums 0 and 1 are the number of source points used and the sum of their best d2 in both.  The pose travels as a kernel argument.
 struct Pose {
   double R[9], t[3], c[3];
 };
 
-// the terms of one pair (a, b, normal n, weight w) added to acc[2 ..]; without a normal acc[17 ..] is left alone
-__device__ __forceinline__ void add_pair_terms(double acc[kRegSums], const double a[3], const double b[3], const float* n, double w) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double wa = w * a[r];
-    acc[2 + r] += wa;
-    acc[5 + r] += w * b[r];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[8 + r * 3 + c] += wa * b[c];
-  }
-  if (!n) return;
-  const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
-  const double res = ((a[0] - b[0]) * n0 + (a[1] - b[1]) * n1) + (a[2] - b[2]) * n2;
-  const double J[6] = {a[1] * n2 - a[2] * n1, a[2] * n0 - a[0] * n2, a[0] * n1 - a[1] * n0, n0, n1, n2};
-  int k = 17;
+// a block of 28: acc[0..20] += (w J_r) J_c for r <= c, acc[21..26] += (w J_r) res, acc[27] += (w res) res
+__device__ __forceinline__ void add_six_terms(double* acc, const double J[6], double res, double w) {
+  int k = 0;
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
     const double wj = w * J[r];
 #pragma unroll
     for (int c = r; c < 6; ++c) acc[k++] += wj * J[c];
-    acc[38 + r] += wj * res;
+    acc[21 + r] += wj * res;
   }
-  acc[44] += (w * res) * res;
+  acc[27] += (w * res) * res;
 }
 
-// partial[k * kOffgridBlocks + b] = sum k of workgroup b.  45 accumulators per thread stay in registers; the workgroup's
-// sum is a shuffle tree per wave, then the four waves in order (4 x 45 doubles of LDS, not 45 x 256).
-__global__ void __launch_bounds__(256) register_step_kernel(const float* p, int64_t np, Target t, const float* normals_q, Pose pose,
-                                                            double gate2, double* partial, double* best_out, int32_t* ties_out,
-                                                            int* bad) {
-  __shared__ double sh[4][kRegSums];
-  double acc[kRegSums];
+// the point-to-plane block of the pair (a, b) with the target's normal n
+__device__ __forceinline__ void add_plane_terms(double* acc, const double a[3], const double b[3], const float* n, double w) {
+  const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
+  const double res = ((a[0] - b[0]) * n0 + (a[1] - b[1]) * n1) + (a[2] - b[2]) * n2;
+  const double J[6] = {a[1] * n2 - a[2] * n1, a[2] * n0 - a[0] * n2, a[0] * n1 - a[1] * n0, n0, n1, n2};
+  add_six_terms(acc, J, res, w);
+}
+
+// A terms policy: kSums accumulators; source(i), read once per source point that passes the gate; add(), the terms of the pair
+// of that point at a = p - c with target point j at b = q_j - c, weight w; and the names its entry point reports under.
+struct PlaneTerms {
+  static constexpr int kSums = 45;
+  static constexpr const char* kName = "pcgc_register_step";
+  static constexpr const char* kKernels = "registration step kernels";
+  const float* normals_q;                                    // or null: acc[17 ..] is left alone
+
+  __device__ __forceinline__ double source(int64_t) const { return 0.0; }
+  __device__ __forceinline__ void add(double* acc, double, const double a[3], const double b[3], int32_t j, double w) const {
 #pragma unroll
-  for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
+    for (int r = 0; r < 3; ++r) {
+      const double wa = w * a[r];
+      acc[2 + r] += wa;
+      acc[5 + r] += w * b[r];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[8 + r * 3 + c] += wa * b[c];
+    }
+    if (normals_q) add_plane_terms(acc + 17, a, b, normals_q + (int64_t)j * 3, w);
+  }
+};
+
+constexpr double kIntensityScale = 2550000.0;                       // 255 * (2126 + 7152 + 722)
+
+struct ColorTerms {
+  static constexpr int kSums = 59;
+  static constexpr int kGeo = 2, kWeight = 30, kPhoto = 31;         // where the two blocks of 28 and the weight sum start
+  static constexpr const char* kName = "pcgc_register_color_step";
+  static constexpr const char* kKernels = "colour registration step kernels";
+  const int32_t* Yp;
+  const float* normals_q;
+  const int32_t* Yq;
+  const double* grad_q;
+  const uint8_t* valid_q;
+
+  __device__ __forceinline__ double source(int64_t i) const { return (double)Yp[i] / kIntensityScale; }
+  __device__ __forceinline__ void add(double* acc, double ip, const double a[3], const double b[3], int32_t j, double w) const {
+    add_plane_terms(acc + kGeo, a, b, normals_q + (int64_t)j * 3, w);
+    if (!valid_q[j]) return;
+    const double* g = grad_q + (int64_t)j * 3;
+    const double g0 = g[0], g1 = g[1], g2 = g[2];
+    const double rc = ((double)Yq[j] / kIntensityScale - ip) + (((a[0] - b[0]) * g0 + (a[1] - b[1]) * g1) + (a[2] - b[2]) * g2);
+    const double Jc[6] = {a[1] * g2 - a[2] * g1, a[2] * g0 - a[0] * g2, a[0] * g1 - a[1] * g0, g0, g1, g2};
+    acc[kWeight] += w;
+    add_six_terms(acc + kPhoto, Jc, rc, w);
+  }
+};
+
+// partial[k * kOffgridBlocks + b] = sum k of workgroup b.  The accumulators of a thread stay in registers; the workgroup's
+// sum is a shuffle tree per wave, then the four waves in order (4 x kSums doubles of LDS, not kSums x 256).
+template <typename Terms>
+__global__ void __launch_bounds__(256) register_step_kernel(const float* p, int64_t np, Target t, Terms terms, Pose pose, double gate2,
+                                                            double* partial, double* best_out, int32_t* ties_out, int* bad) {
+  constexpr int kSums = Terms::kSums;
+  __shared__ double sh[4][kSums];
+  double acc[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
   long long n_used = 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
     const double x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
@@ -220,10 +264,11 @@ __global__ void __launch_bounds__(256) register_step_kernel(const float* p, int6
         for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t, double, double, double) { ++ties; });
         const double w = 1.0 / (double)ties;
         const double a[3] = {px - pose.c[0], py - pose.c[1], pz - pose.c[2]};
+        const double from_source = terms.source(i);
         for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t j, double, double, double) {
           const float* q = t.q + (int64_t)j * 3;
           const double b[3] = {(double)q[0] - pose.c[0], (double)q[1] - pose.c[1], (double)q[2] - pose.c[2]};
-          add_pair_terms(acc, a, b, normals_q ? normals_q + (int64_t)j * 3 : nullptr, w);
+          terms.add(acc, from_source, a, b, j, w);
         });
         ++n_used;
         acc[1] += best;
@@ -236,24 +281,24 @@ __global__ void __launch_bounds__(256) register_step_kernel(const float* p, int6
   acc[0] = (double)n_used;                                    // below 2^31 per launch: exact, and so is every partial sum of them
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < kRegSums; ++k) {
+  for (int k = 0; k < kSums; ++k) {
     double v = acc[k];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     if (lane == 0) sh[wave][k] = v;
   }
   __syncthreads();
-  if (threadIdx.x < kRegSums)
+  if (threadIdx.x < kSums)
     partial[threadIdx.x * kOffgridBlocks + blockIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
 }
 
-// one wave: lane k adds sum k of the workgroups in index order; bad[0] is prepare's flag (the target), bad[1] this step's
-__global__ void __launch_bounds__(64) register_final_kernel(const double* partial, int nb, const int* bad, double* out45) {
+// one wave: lane k < n_sums adds sum k of the workgroups in index order; bad[0] is prepare's flag (the target), bad[1] this step's
+__global__ void __launch_bounds__(64) register_final_kernel(const double* partial, int nb, int n_sums, const int* bad, double* out) {
   const int k = threadIdx.x;
-  if (k >= kRegSums) return;
+  if (k >= n_sums) return;
   double v = 0.0;
   for (int i = 0; i < nb; ++i) v += partial[k * kOffgridBlocks + i];
-  out45[k] = (bad[0] | bad[1]) ? (double)NAN : v;
+  out[k] = (bad[0] | bad[1]) ? (double)NAN : v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -293,6 +338,40 @@ OffgridBuffers offgrid_layout(int res, int64_t nq, void* workspace) {
 
 int build_target(const OffgridBuffers& b, const Cells& c, const float* q, int64_t nq, hipStream_t s, Target* t) {
   return build_cells(b.r, b.keys, b.start, b.bad, c, q, nq, s, t);
+}
+
+// the off-grid layout as it is, then [n_sums, kOffgridBlocks] doubles; the second word of the flag's 256 bytes is the step's flag
+size_t register_bytes(int res, int64_t nq, int n_sums) {
+  const size_t base = pcgc_offgrid_workspace_bytes(res, nq);
+  return base ? base + align256((size_t)n_sums * kOffgridBlocks * sizeof(double)) : 0;
+}
+
+// a step of either metric against the target pcgc_register_prepare left in the workspace; pointers_ok: the entry point's own
+template <typename Terms>
+int register_step(const Terms& terms, bool pointers_ok, const float* p, int64_t np, const float* q, int64_t nq, double h, int ox, int oy,
+                  int oz, int res, const double* R9, const double* t3, const double* c3, double max_dist, double* out, double* best,
+                  int32_t* n_ties, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
+  PCGC_REQUIRE(pointers_ok && p && q && R9 && t3 && c3 && out && workspace && grid_ok(h, ox, oy, oz, res, np, nq) &&
+               (best == nullptr) == (n_ties == nullptr), "%s: bad arguments", Terms::kName);
+  PCGC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0, "%s: max_dist must be finite and positive (got %g)", Terms::kName, max_dist);
+  Pose pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R9[k];
+  for (int k = 0; k < 3; ++k) { pose.t[k] = t3[k]; pose.c[k] = c3[k]; }
+  bool finite = true;
+  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(pose.R[k]);
+  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(pose.t[k]) && std::isfinite(pose.c[k]);
+  PCGC_REQUIRE(finite, "%s: the pose and the centre must be finite", Terms::kName);
+  PCGC_REQUIRE(workspace_bytes >= register_bytes(res, nq, Terms::kSums), "%s: workspace too small", Terms::kName);
+  hipStream_t s = (hipStream_t)stream;
+  const OffgridBuffers b = offgrid_layout(res, nq, workspace);               // as pcgc_register_prepare left it
+  const Target t{Cells{h, ox, oy, oz, res}, b.r.bits, b.r.rank, b.start, q};
+  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + offgrid_bytes(res, nq));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.bad + 1, 0, sizeof(int), s));
+  const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
+  hipLaunchKernelGGL(register_step_kernel<Terms>, dim3(blocks), dim3(256), 0, s, p, np, t, terms, pose, max_dist * max_dist, partial, best,
+                     n_ties, b.bad + 1);
+  hipLaunchKernelGGL(register_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, Terms::kSums, b.bad, out);
+  return launch_ok(Terms::kKernels);
 }
 
 }  // namespace
@@ -345,11 +424,10 @@ int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, con
   return launch_ok("off-grid mse kernels");
 }
 
-// the off-grid layout as it is, then [45, kOffgridBlocks] doubles; the second word of the flag's 256 bytes is the step's flag
-size_t pcgc_register_workspace_bytes(int res, int64_t nq) {
-  const size_t base = pcgc_offgrid_workspace_bytes(res, nq);
-  return base ? base + align256((size_t)kRegSums * kOffgridBlocks * sizeof(double)) : 0;
-}
+size_t pcgc_register_workspace_bytes(int res, int64_t nq) { return register_bytes(res, nq, PlaneTerms::kSums); }
+
+// pcgc_register_prepare fills the colour step's workspace as it fills the plain step's
+size_t pcgc_register_color_workspace_bytes(int res, int64_t nq) { return register_bytes(res, nq, ColorTerms::kSums); }
 
 int pcgc_register_prepare(const float* q, int64_t nq, double h, int ox, int oy, int oz, int res, void* workspace,
                           size_t workspace_bytes, pcgc_stream_t stream) {
@@ -366,168 +444,16 @@ int pcgc_register_prepare(const float* q, int64_t nq, double h, int ox, int oy, 
 int pcgc_register_step(const float* p, int64_t np, const float* q, int64_t nq, const float* normals_q, double h, int ox, int oy, int oz,
                        int res, const double* R9, const double* t3, const double* c3, double max_dist, double* out45, double* best,
                        int32_t* n_ties, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
-  PCGC_REQUIRE(p && q && R9 && t3 && c3 && out45 && workspace && grid_ok(h, ox, oy, oz, res, np, nq) &&
-               (best == nullptr) == (n_ties == nullptr), "pcgc_register_step: bad arguments");
-  PCGC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0, "pcgc_register_step: max_dist must be finite and positive (got %g)", max_dist);
-  Pose pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R9[k];
-  for (int k = 0; k < 3; ++k) { pose.t[k] = t3[k]; pose.c[k] = c3[k]; }
-  bool finite = true;
-  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(pose.R[k]);
-  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(pose.t[k]) && std::isfinite(pose.c[k]);
-  PCGC_REQUIRE(finite, "pcgc_register_step: the pose and the centre must be finite");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_register_workspace_bytes(res, nq), "pcgc_register_step: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const OffgridBuffers b = offgrid_layout(res, nq, workspace);               // as pcgc_register_prepare left it
-  const Target t{Cells{h, ox, oy, oz, res}, b.r.bits, b.r.rank, b.start, q};
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + offgrid_bytes(res, nq));
-  PCGC_CHECK_HIP(hipMemsetAsync(b.bad + 1, 0, sizeof(int), s));
-  const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
-  hipLaunchKernelGGL(register_step_kernel, dim3(blocks), dim3(256), 0, s, p, np, t, normals_q, pose, max_dist * max_dist, partial, best,
-                     n_ties, b.bad + 1);
-  hipLaunchKernelGGL(register_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, b.bad, out45);
-  return launch_ok("registration step kernels");
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------- coloured ICP
-// One step of the colour metric (include/pcgc.h, pcgc_register_color_step; tests/_color_icp_ref.py): the search,
-// the tie set, the weights and the gate of register_step_kernel, and per pair the point-to-plane terms plus, where the
-// target point has a gradient (pcgc_color_gradient, color_icp.hip), the photometric terms.  Two blocks of 28 sums of one shape
-// (the upper triangle of J J^T, J res, res^2), the count of valid pairs between them; the point-to-point moments are left out,
-// so that the 59 accumulators stay in registers.
-namespace pcgc {
-namespace {
-
-constexpr int kColSums = 59;
-constexpr int kColGeo = 2, kColWeight = 30, kColPhoto = 31;       // where the two blocks of 28 and the weight sum start
-constexpr double kIntensityScale = 2550000.0;                     // 255 * (2126 + 7152 + 722)
-
-// acc[0..20] += (w J_r) J_c for r <= c, acc[21..26] += (w J_r) res, acc[27] += (w res) res
-__device__ __forceinline__ void add_six_terms(double* acc, const double J[6], double res, double w) {
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const double wj = w * J[r];
-#pragma unroll
-    for (int c = r; c < 6; ++c) acc[k++] += wj * J[c];
-    acc[21 + r] += wj * res;
-  }
-  acc[27] += (w * res) * res;
-}
-
-__global__ void __launch_bounds__(256) register_color_step_kernel(const float* p, int64_t np, const int32_t* Yp, Target t,
-                                                                  const float* normals_q, const int32_t* Yq, const double* grad_q,
-                                                                  const uint8_t* valid_q, Pose pose, double gate2, double* partial,
-                                                                  double* best_out, int32_t* ties_out, int* bad) {
-  __shared__ double sh[4][kColSums];
-  double acc[kColSums];
-#pragma unroll
-  for (int k = 0; k < kColSums; ++k) acc[k] = 0.0;
-  long long n_used = 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < np; i += (int64_t)gridDim.x * 256) {
-    const double x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-    float pf[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) pf[r] = (float)(((pose.R[3 * r] * x + pose.R[3 * r + 1] * y) + pose.R[3 * r + 2] * z) + pose.t[r]);
-    int cell[3], shell, ties = 0;
-    double best = NAN;
-    if (cell_of_point(t.c, pf, cell)) {
-      const double px = pf[0], py = pf[1], pz = pf[2];
-      best = nearest_offgrid(t, cell, px, py, pz, &shell);
-      if (best <= gate2) {
-        for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t, double, double, double) { ++ties; });
-        const double w = 1.0 / (double)ties;
-        const double a[3] = {px - pose.c[0], py - pose.c[1], pz - pose.c[2]};
-        const double ip = (double)Yp[i] / kIntensityScale;
-        for_each_tied_offgrid(t, cell, px, py, pz, best, shell, [&](int32_t j, double, double, double) {
-          const float* q = t.q + (int64_t)j * 3;
-          const float* n = normals_q + (int64_t)j * 3;
-          const double d[3] = {a[0] - ((double)q[0] - pose.c[0]), a[1] - ((double)q[1] - pose.c[1]), a[2] - ((double)q[2] - pose.c[2])};
-          {
-            const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
-            const double res = (d[0] * n0 + d[1] * n1) + d[2] * n2;
-            const double J[6] = {a[1] * n2 - a[2] * n1, a[2] * n0 - a[0] * n2, a[0] * n1 - a[1] * n0, n0, n1, n2};
-            add_six_terms(acc + kColGeo, J, res, w);
-          }
-          if (valid_q[j]) {
-            const double* g = grad_q + (int64_t)j * 3;
-            const double g0 = g[0], g1 = g[1], g2 = g[2];
-            const double rc = ((double)Yq[j] / kIntensityScale - ip) + ((d[0] * g0 + d[1] * g1) + d[2] * g2);
-            const double Jc[6] = {a[1] * g2 - a[2] * g1, a[2] * g0 - a[0] * g2, a[0] * g1 - a[1] * g0, g0, g1, g2};
-            acc[kColWeight] += w;
-            add_six_terms(acc + kColPhoto, Jc, rc, w);
-          }
-        });
-        ++n_used;
-        acc[1] += best;
-      }
-    } else {
-      atomicOr(bad, 1);
-    }
-    if (best_out) { best_out[i] = best; ties_out[i] = ties; }
-  }
-  acc[0] = (double)n_used;                                    // below 2^31 per launch: exact, and so is every partial sum of them
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kColSums; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) sh[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kColSums)
-    partial[threadIdx.x * kOffgridBlocks + blockIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-// one wave: lane k adds sum k of the workgroups in index order; bad[0] is prepare's flag (the target), bad[1] this step's
-__global__ void __launch_bounds__(64) register_color_final_kernel(const double* partial, int nb, const int* bad, double* out59) {
-  const int k = threadIdx.x;
-  if (k >= kColSums) return;
-  double v = 0.0;
-  for (int i = 0; i < nb; ++i) v += partial[k * kOffgridBlocks + i];
-  out59[k] = (bad[0] | bad[1]) ? (double)NAN : v;
-}
-
-}  // namespace
-}  // namespace pcgc
-
-extern "C" {
-
-// the off-grid layout as it is, then [59, kOffgridBlocks] doubles: pcgc_register_prepare fills it as it fills its own
-size_t pcgc_register_color_workspace_bytes(int res, int64_t nq) {
-  const size_t base = pcgc_offgrid_workspace_bytes(res, nq);
-  return base ? base + align256((size_t)kColSums * kOffgridBlocks * sizeof(double)) : 0;
+  return register_step(PlaneTerms{normals_q}, true, p, np, q, nq, h, ox, oy, oz, res, R9, t3, c3, max_dist, out45, best, n_ties, workspace,
+                       workspace_bytes, stream);
 }
 
 int pcgc_register_color_step(const float* p, const int32_t* Yp, int64_t np, const float* q, const float* normals_q, const int32_t* Yq,
                              const double* grad_q, const uint8_t* valid_q, int64_t nq, double h, int ox, int oy, int oz, int res,
                              const double* R9, const double* t3, const double* c3, double max_dist, double* out59, double* best,
                              int32_t* n_ties, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
-  PCGC_REQUIRE(p && Yp && q && normals_q && Yq && grad_q && valid_q && R9 && t3 && c3 && out59 && workspace &&
-               grid_ok(h, ox, oy, oz, res, np, nq) && (best == nullptr) == (n_ties == nullptr), "pcgc_register_color_step: bad arguments");
-  PCGC_REQUIRE(std::isfinite(max_dist) && max_dist > 0.0, "pcgc_register_color_step: max_dist must be finite and positive (got %g)",
-               max_dist);
-  Pose pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R9[k];
-  for (int k = 0; k < 3; ++k) { pose.t[k] = t3[k]; pose.c[k] = c3[k]; }
-  bool finite = true;
-  for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(pose.R[k]);
-  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(pose.t[k]) && std::isfinite(pose.c[k]);
-  PCGC_REQUIRE(finite, "pcgc_register_color_step: the pose and the centre must be finite");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_register_color_workspace_bytes(res, nq), "pcgc_register_color_step: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const OffgridBuffers b = offgrid_layout(res, nq, workspace);               // as pcgc_register_prepare left it
-  const Target t{Cells{h, ox, oy, oz, res}, b.r.bits, b.r.rank, b.start, q};
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + offgrid_bytes(res, nq));
-  PCGC_CHECK_HIP(hipMemsetAsync(b.bad + 1, 0, sizeof(int), s));
-  const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
-  hipLaunchKernelGGL(register_color_step_kernel, dim3(blocks), dim3(256), 0, s, p, np, Yp, t, normals_q, Yq, grad_q, valid_q, pose,
-                     max_dist * max_dist, partial, best, n_ties, b.bad + 1);
-  hipLaunchKernelGGL(register_color_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, b.bad, out59);
-  return launch_ok("colour registration step kernels");
+  return register_step(ColorTerms{Yp, normals_q, Yq, grad_q, valid_q}, Yp && normals_q && Yq && grad_q && valid_q, p, np, q, nq, h, ox, oy,
+                       oz, res, R9, t3, c3, max_dist, out59, best, n_ties, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

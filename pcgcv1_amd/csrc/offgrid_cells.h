@@ -1,5 +1,6 @@
-// The cells a float32 cloud is searched in, shared by the off-grid D1 / D2 and registration kernels (offgrid.hip) and the
-// descriptor kernels of the global alignment (global.hip).  The cloud Q is bucketed into cubic cells of edge h (a power of
+// The cells a float32 cloud is searched in, and the one walk over them, shared by the off-grid D1 / D2 and registration
+// kernels (offgrid.hip), the descriptor kernels of the global alignment (global.hip), the smoothing (smooth.hip) and the
+// colour gradient (color_icp.hip).  The cloud Q is bucketed into cubic cells of edge h (a power of
 // two): cell = floor(q / h) - origin per axis, inside a grid of res^3 cells.  Coordinates are never shifted or rescaled: every
 // distance is float64 arithmetic on the float32 coordinates as they came, d2 = (dx*dx + dy*dy) + dz*dz with dx = double(p.x)
 // - double(q.x) (the including files are built with -ffp-contract=off).  The cells are the occupancy bit set and rank table
@@ -74,12 +75,54 @@ __device__ __forceinline__ double dist2(const float* q, double px, double py, do
   return (dx * dx + dy * dy) + dz * dz;
 }
 
+struct Window {
+  int x0, x1, y0, y1, z0, z1;
+};
+
+// the cells within w of `cell`, clipped to the grid (empty when the cell lies further outside than w)
+__device__ __forceinline__ Window window_of(const int cell[3], int w, int res) {
+  return Window{max(cell[0] - w, 0), min(cell[0] + w, res - 1), max(cell[1] - w, 0), min(cell[1] + w, res - 1),
+                max(cell[2] - w, 0), min(cell[2] + w, res - 1)};
+}
+
+// THE cell walk: calls f(first, end) with the run of points of every occupied cell of a window inside the grid, the cells in
+// x, y, z order.  What a caller does with a run is its own: a thread takes every point (for_each_in_window), the lanes of a
+// wave stride over it (global.hip).
+template <typename F>
+__device__ __forceinline__ void for_each_run(const Target& t, const Window& v, F f) {
+  for (int x = v.x0; x <= v.x1; ++x)
+    for (int y = v.y0; y <= v.y1; ++y)
+      for (int z = v.z0; z <= v.z1; ++z) {
+        if (!bit_at(t.bits, t.c.res, x, y, z)) continue;
+        const int64_t r = rank_of(t.bits, t.rank, cell_of(t.c.res, x, y, z));
+        f(t.start[r], t.start[r + 1]);
+      }
+}
+
+// calls f(j) for every point j of the window, the points of a cell in Q's order
+template <typename F>
+__device__ __forceinline__ void for_each_in_window(const Target& t, const Window& v, F f) {
+  for_each_run(t, v, [&](int32_t j, int32_t end) {
+    for (; j < end; ++j) f(j);
+  });
+}
+
 // calls f(j) for every point j of the cell (x, y, z), which lies inside the grid
 template <typename F>
 __device__ __forceinline__ void for_each_in_cell(const Target& t, int x, int y, int z, F f) {
-  if (!bit_at(t.bits, t.c.res, x, y, z)) return;
-  const int64_t r = rank_of(t.bits, t.rank, cell_of(t.c.res, x, y, z));
-  for (int32_t j = t.start[r], end = t.start[r + 1]; j < end; ++j) f(j);
+  for_each_in_window(t, Window{x, x, y, y, z, z}, f);
+}
+
+// Kernels of one thread per point of the cloud itself (smooth.hip, color_icp.hip) report through a uint8 per point.  A raised
+// flag overwrites all of them with one value that names the cause.
+constexpr int kFlagInput = 1, kFlagDense = 2;
+constexpr uint8_t kMarkBadInput = 255, kMarkTooDense = 254;
+
+__global__ void __launch_bounds__(256) flag_marks_kernel(const int* bad, int64_t n, uint8_t* marks) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int flag = *bad;
+  if (i >= n || !flag) return;
+  marks[i] = (flag & kFlagInput) ? kMarkBadInput : kMarkTooDense;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -92,6 +135,9 @@ bool grid_ok(double h, int ox, int oy, int oz, int res, int64_t np, int64_t nq) 
   return edge_ok(h) && res >= 1 && res <= kOffgridMaxRes && std::abs((double)ox) < kCellLimit && std::abs((double)oy) < kCellLimit &&
          std::abs((double)oz) < kCellLimit && np > 0 && nq > 0 && np <= 0x7FFFFFFF && nq < 0x7FFFFFFF;
 }
+
+// the sizes a cloud that is searched in its own cells may have (smooth.hip, color_icp.hip)
+bool cloud_sizes_ok(int res, int64_t n) { return res >= 1 && res <= kOffgridMaxRes && n > 0 && n < 0x7FFFFFFF; }
 
 // the cells of Q into r, keys [nq] and start [nq + 1]: keys, bit set, rank table, cell starts; the flag starts at zero
 int build_cells(const RankBuffers& r, int64_t* keys, int32_t* start, int* bad, const Cells& c, const float* q, int64_t nq, hipStream_t s,

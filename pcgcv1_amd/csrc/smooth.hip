@@ -9,8 +9,8 @@
 // numpy therefore agree bit for bit.
 //
 // One thread per point, the points in cell order (offgrid_cells.h): the lanes of a wave lie in the same or neighbouring
-// cells, so they walk the same 27 cell ranges and their loads of the neighbours coincide.  The ten sums and the count live
-// in registers; there are no atomics on data and no scratch (DESIGN.md §7j quotes the register counts).
+// cells, so they walk the same 27 cell ranges (for_each_in_window) and their loads of the neighbours coincide.  The ten sums
+// and the count live in registers; there are no atomics on data and no scratch (DESIGN.md §7j quotes the register counts).
 // Input that breaks the contract (points not sorted by cell or outside the grid, a coordinate that is not finite) is met
 // with no index out of bounds: it raises the flag in the workspace, and `moved` says so.
 #include <cmath>
@@ -24,8 +24,6 @@ namespace {
 constexpr double kSmoothMaxRadius = 16.0;           // |offset| <= 2^20, a product below 2^41
 constexpr int kSmoothMaxK = 1 << 22;                // ... so 2^22 terms stay inside int64
 constexpr double kSmoothScale = 65536.0;
-constexpr int kFlagInput = 1, kFlagDense = 2;
-constexpr uint8_t kMovedBadInput = 255, kMovedTooDense = 254;
 
 __global__ void __launch_bounds__(256) smooth_step_kernel(Target t, int64_t n, double r2, int kmin, float* out, uint8_t* moved,
                                                           int32_t* Kout, int64_t* Sout, int64_t* Qout, int* bad) {
@@ -38,29 +36,20 @@ __global__ void __launch_bounds__(256) smooth_step_kernel(Target t, int64_t n, d
   bool dense = false;
   int cell[3];
   if (cell_of_point(t.c, g, cell)) {
-    const int res = t.c.res;
-    const int x0 = max(cell[0] - 1, 0), x1 = min(cell[0] + 1, res - 1), y0 = max(cell[1] - 1, 0), y1 = min(cell[1] + 1, res - 1);
-    const int z0 = max(cell[2] - 1, 0), z1 = min(cell[2] + 1, res - 1);
-    for (int x = x0; x <= x1; ++x)
-      for (int y = y0; y <= y1; ++y)
-        for (int z = z0; z <= z1; ++z) {
-          if (!bit_at(t.bits, res, x, y, z)) continue;
-          const int64_t r = rank_of(t.bits, t.rank, cell_of(res, x, y, z));
-          for (int32_t j = t.start[r], end = t.start[r + 1]; j < end; ++j) {
-            const float* q = t.q + (int64_t)j * 3;
-            if (!(dist2(q, px, py, pz) <= r2)) continue;       // false for a NaN
-            if (K == kSmoothMaxK) {
-              dense = true;
-              continue;
-            }
-            const int64_t a = llrint(((double)q[0] - px) * kSmoothScale);
-            const int64_t b = llrint(((double)q[1] - py) * kSmoothScale);
-            const int64_t c = llrint(((double)q[2] - pz) * kSmoothScale);
-            ++K;
-            s0 += a; s1 += b; s2 += c;
-            q00 += a * a; q01 += a * b; q02 += a * c; q11 += b * b; q12 += b * c; q22 += c * c;
-          }
-        }
+    for_each_in_window(t, window_of(cell, 1, t.c.res), [&](int32_t j) {
+      const float* q = t.q + (int64_t)j * 3;
+      if (!(dist2(q, px, py, pz) <= r2)) return;           // false for a NaN
+      if (K == kSmoothMaxK) {
+        dense = true;
+        return;
+      }
+      const int64_t a = llrint(((double)q[0] - px) * kSmoothScale);
+      const int64_t b = llrint(((double)q[1] - py) * kSmoothScale);
+      const int64_t c = llrint(((double)q[2] - pz) * kSmoothScale);
+      ++K;
+      s0 += a; s1 += b; s2 += c;
+      q00 += a * a; q01 += a * b; q02 += a * c; q11 += b * b; q12 += b * c; q22 += c * c;
+    });
   } else {
     atomicOr(bad, kFlagInput);
   }
@@ -101,16 +90,6 @@ __global__ void __launch_bounds__(256) smooth_step_kernel(Target t, int64_t n, d
   moved[i] = 1;
 }
 
-// what a raised flag does to `moved`: one value everywhere that names the cause
-__global__ void __launch_bounds__(256) smooth_flag_kernel(const int* bad, int64_t n, uint8_t* moved) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int flag = *bad;
-  if (i >= n || !flag) return;
-  moved[i] = (flag & kFlagInput) ? kMovedBadInput : kMovedTooDense;
-}
-
-bool smooth_sizes_ok(int res, int64_t n) { return res >= 1 && res <= kOffgridMaxRes && n > 0 && n < 0x7FFFFFFF; }
-
 }  // namespace
 }  // namespace pcgc
 
@@ -118,11 +97,11 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_smooth_workspace_bytes(int res, int64_t n) { return smooth_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
+size_t pcgc_smooth_workspace_bytes(int res, int64_t n) { return cloud_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
 
 int pcgc_smooth_step(const float* points, int64_t n, double h, int ox, int oy, int oz, int res, double radius, int kmin, float* out,
                      uint8_t* moved, int32_t* K, int64_t* S, int64_t* Q, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
-  PCGC_REQUIRE(points && out && moved && workspace && out != points && smooth_sizes_ok(res, n) && grid_ok(h, ox, oy, oz, res, n, n),
+  PCGC_REQUIRE(points && out && moved && workspace && out != points && cloud_sizes_ok(res, n) && grid_ok(h, ox, oy, oz, res, n, n),
                "pcgc_smooth_step: bad arguments");
   PCGC_REQUIRE((K != nullptr) == (S != nullptr) && (K != nullptr) == (Q != nullptr), "pcgc_smooth_step: K, S and Q come together or not at all");
   PCGC_REQUIRE(std::isfinite(radius) && radius > 0.0 && radius <= kSmoothMaxRadius && radius <= h,
@@ -136,7 +115,7 @@ int pcgc_smooth_step(const float* points, int64_t n, double h, int ox, int oy, i
   if (rc) return rc;
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(smooth_step_kernel, dim3(grid), dim3(256), 0, s, t, n, radius * radius, kmin, out, moved, K, S, Q, b.bad);
-  hipLaunchKernelGGL(smooth_flag_kernel, dim3(grid), dim3(256), 0, s, b.bad, n, moved);
+  hipLaunchKernelGGL(flag_marks_kernel, dim3(grid), dim3(256), 0, s, b.bad, n, moved);
   return launch_ok("smooth kernels");
 }
 

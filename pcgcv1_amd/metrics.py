@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .cells import cell_keys
 
 
 def _d1_one_way(a_d, b_d, res, ws):
@@ -251,9 +252,9 @@ class _OffgridTarget:
         self.h, origin, self.res = _offgrid_cells(target, source)
         self.origin = [int(v) for v in origin]
         q = torch.from_numpy(target).to(dev)
-        cell = torch.floor(q.to(torch.float64) / self.h).to(torch.int64) - torch.from_numpy(origin).to(dev)
-        keys = (cell[:, 0] * self.res + cell[:, 1]) * self.res + cell[:, 2]
-        self.order = torch.sort(keys, stable=True)[1]
+        # every row is finite and lies inside (the cells come from the target's extremes), so no treatment of outside rows
+        # applies; clamp=True is the one with fewer device operations
+        self.order = torch.sort(cell_keys(q, self.grid(), clamp=True), stable=True)[1]
         self.points = q[self.order].contiguous()
 
     def grid(self):

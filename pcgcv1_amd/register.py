@@ -35,6 +35,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .cells import cell_keys, cell_order, cells_from_bounds, feature_cells              # noqa: F401  (re-exported: tests, tools)
 
 N_SUMS = 45
 N_COLOR_SUMS = 59            # pcgc_register_color_step: the plane block [2..29], the valid weight [30], the photometric block [31..58]
@@ -57,7 +58,6 @@ DEFAULT_DRAWS = 100000
 DRAW_BATCH = 16384           # triples per call of the generator: part of the rule, the stream of draws depends on it
 EDGE_RATIO = 0.9
 FEATURE_BINS, FEATURE_ROW = 33, 36
-FEATURE_MAX_CELLS, FEATURE_MAX_EDGE = 1024, 2.0 ** 20
 
 
 # ---------------------------------------------------------------------------- the solves (host, float64)
@@ -185,7 +185,7 @@ def _float32_cloud(points, what):
 class Matcher(object):
     """A target cloud prepared once on the device (pcgc_register_prepare), and steps of a source cloud against it.
     source, target: float32 [n,3] / [m,3] in grid units; target_normals float [m,3] or None (point-to-point sums only)."""
-    n_sums, workspace_bytes = N_SUMS, "pcgc_register_workspace_bytes"
+    n_sums, workspace_bytes, step_symbol = N_SUMS, "pcgc_register_workspace_bytes", "pcgc_register_step"
 
     def __init__(self, source, target, target_normals=None):
         import torch
@@ -219,9 +219,7 @@ class Matcher(object):
         dev = self.source_d.device
         moved = self.source_d.to(torch.float64) @ torch.from_numpy(np.asarray(R, np.float64).reshape(3, 3).T.copy()).to(dev)
         moved += torch.from_numpy(np.asarray(t, np.float64).reshape(3)).to(dev)
-        cell = torch.floor(torch.nan_to_num(moved, nan=0.0) / self.cells.h) - torch.tensor(self.cells.origin, dtype=torch.float64, device=dev)
-        cell = cell.clamp_(0, self.cells.res - 1).to(torch.int64)
-        order = torch.sort((cell[:, 0] * self.cells.res + cell[:, 1]) * self.cells.res + cell[:, 2], stable=True)[1]
+        order = torch.sort(cell_keys(moved, self.cells.grid(), clamp=True), stable=True)[1]         # a point outside: the nearest cell
         self.source_d = self.source_d[order].contiguous()
         self.order = order if self.order is None else self.order[order]
         return order
@@ -234,8 +232,12 @@ class Matcher(object):
     def radius(self):
         return float(np.linalg.norm(self.hi - self.lo)) / 2.0
 
+    def _clouds(self, with_normals):
+        """the arguments of `step_symbol` in front of the cells: the two clouds and what travels with their points"""
+        return (_lib.dptr(self.source_d), self.n, _lib.dptr(self.cells.points), self.m, _lib.dptr(self.normals_d if with_normals else None))
+
     def step(self, R, t, c, max_dist, with_normals=True, per_point=False):
-        """-> S float64 [45]; per_point=True: (S, best float64 [n], ties int32 [n]).  RuntimeError when a moved coordinate
+        """-> S float64 [n_sums]; per_point=True: (S, best float64 [n], ties int32 [n]).  RuntimeError when a moved coordinate
         is a NaN or out of every cell's reach."""
         import torch
         R9 = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9))
@@ -244,14 +246,13 @@ class Matcher(object):
         dev = self.source_d.device
         best = torch.empty(self.n, dtype=torch.float64, device=dev) if per_point else None
         ties = torch.empty(self.n, dtype=torch.int32, device=dev) if per_point else None
-        _lib.check(_lib.hip().pcgc_register_step(
-            _lib.dptr(self.source_d), self.n, _lib.dptr(self.cells.points), self.m, _lib.dptr(self.normals_d if with_normals else None),
-            *self.cells.grid(), _lib.nptr(R9), _lib.nptr(t3), _lib.nptr(c3), float(max_dist), _lib.dptr(self.out), _lib.dptr(best),
-            _lib.dptr(ties), _lib.dptr(self.ws), self.ws.numel(), _lib.stream()), "pcgc_register_step")
+        _lib.check(getattr(_lib.hip(), self.step_symbol)(
+            *self._clouds(with_normals), *self.cells.grid(), _lib.nptr(R9), _lib.nptr(t3), _lib.nptr(c3), float(max_dist),
+            _lib.dptr(self.out), _lib.dptr(best), _lib.dptr(ties), _lib.dptr(self.ws), self.ws.numel(), _lib.stream()), self.step_symbol)
         S = self.out.cpu().numpy().copy()
         if np.isnan(S).any():
-            raise RuntimeError("pcgc_register_step: a moved source coordinate is not finite or leaves every cell's reach, or the "
-                               "target breaks the cell rule (include/pcgc.h)")
+            raise RuntimeError("%s: a moved source coordinate is not finite or leaves every cell's reach, or the target breaks the "
+                               "cell rule (include/pcgc.h)" % self.step_symbol)
         if per_point:
             if self.order is not None:
                 best, ties = torch.empty_like(best).index_copy_(0, self.order, best), torch.empty_like(ties).index_copy_(0, self.order, ties)
@@ -336,7 +337,7 @@ class ColorMatcher(Matcher):
     """Matcher for metric="color": the source's and the target's intensities travel with the points, and the target's
     intensity gradients are fitted once (pcgc_color_gradient) and kept in the matcher's cell order.  colours: whole numbers
     in 0..255, [n,3] / [m,3]; the target's normals are required."""
-    n_sums, workspace_bytes = N_COLOR_SUMS, "pcgc_register_color_workspace_bytes"
+    n_sums, workspace_bytes, step_symbol = N_COLOR_SUMS, "pcgc_register_color_workspace_bytes", "pcgc_register_color_step"
 
     def __init__(self, source, target, target_normals, source_colors, target_colors, color_radius=DEFAULT_COLOR_RADIUS,
                  color_kmin=DEFAULT_COLOR_KMIN):
@@ -359,29 +360,9 @@ class ColorMatcher(Matcher):
         self.Yp_d = self.Yp_d[order].contiguous()
         return order
 
-    def step(self, R, t, c, max_dist, with_normals=True, per_point=False):
-        """-> S float64 [59]; per_point=True: (S, best float64 [n], ties int32 [n])"""
-        import torch
-        R9 = np.ascontiguousarray(np.asarray(R, np.float64).reshape(9))
-        t3 = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
-        c3 = np.ascontiguousarray(np.asarray(c, np.float64).reshape(3))
-        dev = self.source_d.device
-        best = torch.empty(self.n, dtype=torch.float64, device=dev) if per_point else None
-        ties = torch.empty(self.n, dtype=torch.int32, device=dev) if per_point else None
-        _lib.check(_lib.hip().pcgc_register_color_step(
-            _lib.dptr(self.source_d), _lib.dptr(self.Yp_d), self.n, _lib.dptr(self.cells.points), _lib.dptr(self.normals_d),
-            _lib.dptr(self.Yq_d), _lib.dptr(self.grad_d), _lib.dptr(self.valid_d), self.m, *self.cells.grid(), _lib.nptr(R9), _lib.nptr(t3),
-            _lib.nptr(c3), float(max_dist), _lib.dptr(self.out), _lib.dptr(best), _lib.dptr(ties), _lib.dptr(self.ws), self.ws.numel(),
-            _lib.stream()), "pcgc_register_color_step")
-        S = self.out.cpu().numpy().copy()
-        if np.isnan(S).any():
-            raise RuntimeError("pcgc_register_color_step: a moved source coordinate is not finite or leaves every cell's reach, or "
-                               "the target breaks the cell rule (include/pcgc.h)")
-        if per_point:
-            if self.order is not None:
-                best, ties = torch.empty_like(best).index_copy_(0, self.order, best), torch.empty_like(ties).index_copy_(0, self.order, ties)
-            return S, best.cpu().numpy(), ties.cpu().numpy()
-        return S
+    def _clouds(self, with_normals):
+        return (_lib.dptr(self.source_d), _lib.dptr(self.Yp_d), self.n, _lib.dptr(self.cells.points), _lib.dptr(self.normals_d),
+                _lib.dptr(self.Yq_d), _lib.dptr(self.grad_d), _lib.dptr(self.valid_d), self.m)
 
 
 # ---------------------------------------------------------------------------- the loop
@@ -485,44 +466,6 @@ def keypoints(points, normals, feature_voxel):
     if normals is None:
         nrm = metrics.estimate_normals(vox)
     return ingest.apply_frame(vox, frame).astype(np.float32), _unit_normals(nrm, len(vox))
-
-
-def cells_from_bounds(lo, hi, radius, who="global_align"):
-    """-> (h, ox, oy, oz, res): the cells a search within `radius` walks between the extremes lo and hi (float64 [3]) of a cloud:
-    the smallest power of two h >= max(1, radius) with at most 1024 cells per axis"""
-    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
-    h = 1.0
-    while h < radius or int((np.floor(hi / h) - np.floor(lo / h)).max()) + 1 > FEATURE_MAX_CELLS:
-        h *= 2.0
-        if h > FEATURE_MAX_EDGE:
-            raise ValueError("%s: keypoints of extent %g with radius %g need cells wider than 2^20" % (who, float((hi - lo).max()), radius))
-    origin = np.floor(lo / h)
-    if float(np.abs(np.stack([origin, np.floor(hi / h)])).max()) >= 2.0 ** 28:
-        raise ValueError("%s: coordinate / cell edge reaches 2^28 (cell edge %g)" % (who, h))
-    return (h, int(origin[0]), int(origin[1]), int(origin[2]), int((np.floor(hi / h) - origin).max()) + 1)
-
-
-def feature_cells(kp, radius):
-    """-> (h, ox, oy, oz, res): the cells pcgc_feature_* search keypoints in: the smallest power of two h >= max(1, radius)
-    with at most 1024 cells per axis between the extremes of the finite rows"""
-    p = np.asarray(kp, np.float64).reshape(-1, 3)
-    p = p[np.isfinite(p).all(1)]
-    if not len(p) or not (np.isfinite(radius) and radius > 0):
-        raise ValueError("global_align: the keypoints need a finite row and radius must be positive (got %r)" % (radius,))
-    return cells_from_bounds(p.min(0), p.max(0), radius)
-
-
-def cell_order(points, cells):
-    """points: a float32 [n,3] tensor, on the host or the device -> the stable order (int64 tensor, where the points lie) that
-    sorts them by the key of `cells`, which is how pcgc_feature_* and pcgc_smooth_step want them; a row outside the cells or
-    with a coordinate that is not finite sorts first (key -1), and the kernels refuse it"""
-    import torch
-    h, ox, oy, oz, res = cells
-    cell = torch.floor(points.to(torch.float64) / h) - torch.tensor([ox, oy, oz], dtype=torch.float64, device=points.device)
-    inside = torch.isfinite(cell).all(1) & (cell >= 0).all(1) & (cell < res).all(1)
-    c = torch.where(inside[:, None], cell, torch.zeros_like(cell)).to(torch.int64)
-    key = torch.where(inside, (c[:, 0] * res + c[:, 1]) * res + c[:, 2], torch.full_like(c[:, 0], -1))
-    return torch.sort(key, stable=True)[1]
 
 
 class _FeatureCloud(object):

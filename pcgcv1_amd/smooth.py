@@ -23,6 +23,7 @@ colours and normals stay with their rows.
 import numpy as np
 
 from . import _lib
+from .cells import cell_order, cells_from_bounds
 
 MAX_RADIUS, MIN_ITERS, MAX_ITERS, MIN_KMIN, MAX_KMIN = 16.0, 1, 8, 3, 1 << 22
 DEFAULT_ITERS, DEFAULT_KMIN = 2, 6
@@ -72,7 +73,7 @@ def parse_spec(spec):
 # ---------------------------------------------------------------------------- the device loop
 def smooth_step(points_d, cells, radius, kmin, debug=False):
     """One pass (pcgc_smooth_step) over a device tensor float32 [n,3] that is sorted by the key of `cells` (h, ox, oy, oz,
-    res: register.cells_from_bounds, register.cell_order) -> (out float32 [n,3], moved uint8 [n]) device tensors, with debug
+    res: cells.cells_from_bounds, cells.cell_order) -> (out float32 [n,3], moved uint8 [n]) device tensors, with debug
     also K int32 [n], S int64 [n,3], Q int64 [n,6].  RuntimeError when the step raised its flag."""
     import torch
     n, dev = int(points_d.shape[0]), points_d.device
@@ -100,7 +101,6 @@ def smooth_grid_device(g_d, spec):
     tensors, rows in the caller's order"""
     import torch
     from .ingest import bounds
-    from .register import cell_order, cells_from_bounds
     cur = g_d
     rows = torch.arange(len(cur), device=cur.device)           # cur[k] is the caller's row rows[k]
     moved_any = torch.zeros(len(cur), dtype=torch.bool, device=cur.device)

@@ -126,6 +126,23 @@ def test_every_error_names_its_cause():
     assert h == 4.0 and ox < 0 and res <= 1024
 
 
+def test_cell_keys_and_rows_outside_the_cells():
+    """the key (x * res + y) * res + z of floor(p / h) - origin (pcgcv1_amd/cells.py): -1 for a row outside the cells or not
+    finite, which cell_order sorts first; clamp=True gives such a row the nearest cell's key, a NaN counting as 0"""
+    import torch
+    from pcgcv1_amd import cells
+    assert register.cell_order is cells.cell_order and register.cells_from_bounds is cells.cells_from_bounds
+    grid = (2.0, -3, 0, 1, 4)                                  # x in [-6, 2), y in [0, 8), z in [2, 10)
+    nan, inf = float("nan"), float("inf")
+    p = torch.tensor([[-6.0, 0.0, 2.0], [1.5, 7.5, 9.5], [-0.5, 3.0, 4.0], [2.0, 3.0, 4.0], [-6.5, 3.0, 4.0], [0.0, nan, 4.0],
+                      [0.0, 3.0, -inf], [inf, 9.0, 1.0]], dtype=torch.float32)
+    inside = [(0 * 4 + 0) * 4 + 0, (3 * 4 + 3) * 4 + 3, (2 * 4 + 1) * 4 + 1]
+    assert cells.cell_keys(p, grid).tolist() == inside + [-1] * 5
+    assert cells.cell_keys(p, grid, clamp=True).tolist() == inside + [(3 * 4 + 1) * 4 + 1, (0 * 4 + 1) * 4 + 1, (3 * 4 + 0) * 4 + 1,
+                                                                     (3 * 4 + 1) * 4 + 0, (3 * 4 + 3) * 4 + 0]
+    assert cells.cell_order(p, grid).tolist() == [3, 4, 5, 6, 7, 0, 2, 1]
+
+
 def test_argument_errors_of_the_command_line(tmp_path, capsys):
     missing = [str(tmp_path / ("scan%d.ply" % k)) for k in range(2)]
     base = ["--input"] + missing + ["--output", str(tmp_path / "merged.ply"), "--bits", "10"]
