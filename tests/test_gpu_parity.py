@@ -268,21 +268,24 @@ def test_entropy_models_vs_oracle(dense):
     sc = SymmetricConditional()
     v, lik = sc(y, loc, scale, False)
     v_ref, lik_ref = oent.sc_call(y, loc, scale)
+    bits = lambda a: (a.cpu().numpy() if torch.is_tensor(a) else a).view(np.uint32)                      # noqa: E731
     assert np.array_equal(v.cpu().numpy(), v_ref)
-    np.testing.assert_allclose(lik.cpu().numpy(), lik_ref, rtol=2e-5, atol=1e-9)
+    # likelihoods: the oracle's bits, as the pmf of the same function already had to be (measured before it was demanded:
+    # 0 of 2 097 925 differ with noise, test_gpu_entropy_forms.py)
+    assert np.array_equal(bits(lik), bits(lik_ref))
     assert lik.cpu().numpy()[0, 0, 0, 1, 0] == np.float32(1e-9)
     noise = (rng.random(y.shape) - 0.5).astype(np.float32)
     v, lik = sc(y, loc, scale, True, noise=torch.from_numpy(noise))
     v_ref, lik_ref = oent.sc_call(y, loc, scale, training=True, noise=noise)
     np.testing.assert_allclose(v.cpu().numpy(), v_ref, rtol=0, atol=0)
-    np.testing.assert_allclose(lik.cpu().numpy(), lik_ref, rtol=2e-5, atol=1e-9)
+    assert np.array_equal(bits(lik), bits(lik_ref))
     # factorized prior
     eb = EntropyBottleneck().load_weights(dense, "estimator")
     z = (rng.standard_normal((3, 8, 8, 8, 8)) * 2).astype(np.float32)
     zv, zl = eb(z, False)
     zv_ref, zl_ref = oent.eb_call(onets.sub(dense, "estimator"), z)
     assert np.array_equal(zv.cpu().numpy(), zv_ref)
-    np.testing.assert_allclose(zl.cpu().numpy(), zl_ref, rtol=5e-5, atol=1e-9)
+    assert np.array_equal(bits(zl), bits(zl_ref))
     s, mn, mx = eb.compress(z)
     assert (mn, mx) == (int(np.rint(z).min()), int(np.rint(z).max()))
     assert np.array_equal(eb.decompress(s, mn, mx, z.shape).cpu().numpy(), np.rint(z))
@@ -389,7 +392,10 @@ def test_laplace_cdf_integer_algorithm_bit_exact():
     """The device quantiser (run-length form of TF's greedy correction) against the oracle's step-by-step C
     restatement on the SAME float pmf: the pmf of every symbol is produced by pcgc_laplace_likelihood (the same
     device function the CDF kernel evaluates), so every row must match exactly — including rows whose support
-    holds little of the mass (deficits of tens of thousands) and rows that overshoot (sum > 2^16)."""
+    holds little of the mass (deficits of tens of thousands) and rows that overshoot (sum > 2^16).
+    One launch at ncols = 31, cdf_lower only: that is laplace_cdf_kernel<32> (test_laplace_cdf_rows_vs_oracle, ncols = 14, runs
+    <16>).  The instantiations <4> and <8>, which the committed checkpoints run, every ncols at which the choice changes and
+    the encoder's lohi output are pinned in test_gpu_entropy_forms.py."""
     from oracle import coder as ocoder
     rng = np.random.default_rng(77)
     rows = 4096 * 6
