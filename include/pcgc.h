@@ -803,6 +803,67 @@ int pcgc_plane_count(const int32_t* points, int64_t n, int bits, const int64_t* 
 int pcgc_plane_select(const int32_t* points, int64_t n, int bits, const int64_t* plane, uint8_t* mask, int64_t* sums,
                       pcgc_stream_t stream);
 
+/* ---- a triangle mesh from a voxel cloud (pcgcv1_amd/surface.py; tests/_surface_ref.py is the rule in numpy) ----
+ * points int32 [n,3], distinct, on the grid of res = 2^bits cells per axis, 1 <= bits <= 12, 1 <= n < 2^31; normals float32
+ * [n,3] of unit length.  All float arithmetic is float64 in the order written here, without contraction.
+ *
+ * Orientation (pcgc_surface_orient): sign int8 [n] in {+1, -1} such that sign * normal is consistent over a component.  Two
+ * voxels are linked as in pcgc_clean_components with the gap G, 1 <= G <= 8.  seed uint8 [n] marks one voxel per component
+ * (the caller picks the one with the largest key); its sign is -1 if nx < 0 else +1.  Rounds are Jacobi: a round reads the signs
+ * the round before left.  With the stage thresholds tau[0 .. n_tau) (1 <= n_tau <= 8, each within [0, 1], the last 0.0) and the
+ * stage k, 0 at the start, a round takes for every unset voxel i, among its linked voxels j that are set, the j with the
+ * largest |c_ij|, c_ij = (nix njx + niy njy) + niz njz, the smallest key among equals, and if |c_ij| >= tau[k] sets sign[i] =
+ * sign[j] * (+1 if c_ij >= 0 else -1).  A round that set something puts k back to 0, one that set nothing raises it by one;
+ * rounds run while a voxel is unset.  *rounds (host) = the number of rounds run, *readbacks (host, may be NULL) = the number of
+ * times the 16-byte state was read back: `batch` rounds (1..4096) are queued per read, which changes neither sign nor rounds.
+ * The call synchronises the stream.  A component without a seed is an error (sign is not written).
+ *
+ * The lattice (pcgc_surface_lattice): a cell is the unit box centred on an integer point c; the candidate cells are the voxels
+ * and their 26 neighbours, unclipped, c in [-1, res]^3.  Lattice vertex k stands at k + 0.5; the corners of cell c are
+ * c - 1 + {0,1}^3, so k lies in [-2, res]^3, and its key is ((kx + 2) * S + (ky + 2)) * S + (kz + 2) with S = res + 3.  counts
+ * int64 [2] (device) = the number of candidate cells and of their distinct corners.  The workspace keeps both sets for the
+ * calls below, which must follow with the same bits, n and workspace.
+ *
+ * The implicit value (pcgc_surface_implicit): oriented_normals float64 [n,3] = sign * normal, radius R in 3..8; n_vertices =
+ * counts[1].  vertex_keys int64 [n_vertices] ascending; f float64 [n_vertices]: over the occupied q = k + o, o in [-R, R+1]^3
+ * ascending in (ox, oy, oz), with dd = (2k + 1) - 2q and d2 = |dd|^2 (integers), skipping d2 > 4 R^2: t = 1.0 - d2 / (4 R^2 + 1),
+ * w = t * t, num += w * ((Nx ddx + Ny ddy) + Nz ddz), W += w; f = 0.5 * num / W.  A vertex is inside iff f < 0.  Every vertex
+ * sees a voxel within 1.5 sqrt 3 < R, so W > 0.
+ *
+ * Marching tetrahedra (pcgc_surface_triangles, twice: with `count` int64 [1] (device) and triangle_ids NULL it counts, with
+ * triangle_ids int64 [n_triangles,3] and count NULL it writes).  Every candidate cell with lowest corner v0 is cut into the six
+ * Kuhn tetrahedra (v0, v0 + e_p0, v0 + e_p0 + e_p1, v0 + (1,1,1)), one per permutation p of the axes in lexicographic order.  A
+ * lattice edge whose ends a < b differ in `inside` carries a mesh vertex with the id key(a) * 7 + direction, the directions
+ * b - a = 100 010 001 110 101 011 111 numbered 0..6.  With I and O the inside and outside corners in the tetrahedron's order:
+ * one inside corner gives (I0 O0, I0 O1, I0 O2), three give (I0 O0, I1 O0, I2 O0), two give the quad I0 O0, I0 O1, I1 O1, I1 O0
+ * as (1st, 2nd, 3rd) and (1st, 3rd, 4th).  A triangle keeps that order when sign(p) * sign of the sequence (I.., O..) as a
+ * permutation of 0..3 is positive and has its last two corners swapped otherwise: counter-clockwise seen from f >= 0, decided
+ * without a float test, so zero-area triangles (an f of exactly 0) are wound like their neighbours and kept.  Triangles come in
+ * the order of the cells' keys.
+ *
+ * The mesh (pcgc_surface_mesh): edge_ids int64 [n_edges] = the distinct triangle_ids ascending (the caller sorts); vertices
+ * float64 [n_edges,3]: with t = f_a / (f_a - f_b), a + 0.5 + t (b - a) per axis as (a + 0.5) + t * (b - a); triangles int32
+ * [n_triangles,3] = the index of each id in edge_ids.
+ *
+ * Integer atomics only: two calls give the same bytes.  A bad argument returns an error before any memory is touched.  Only
+ * pcgc_surface_orient reads anything back.  Rows that repeat or leave the grid are the caller's to refuse; they index nothing out
+ * of bounds.  workspace: pcgc_surface_workspace_bytes(bits, n) (0 for a bad argument): bit sets and rank tables over res^3 and
+ * (res + 3)^3 cells, a bit set over (res + 2)^3, and 30 bytes per point. */
+size_t pcgc_surface_workspace_bytes(int bits, int64_t n);
+int pcgc_surface_orient(const int32_t* points, const float* normals, const uint8_t* seed, int64_t n, int bits, int gap,
+                        const double* tau, int n_tau, int batch, int8_t* sign, int32_t* rounds, int32_t* readbacks,
+                        void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_surface_lattice(const int32_t* points, int64_t n, int bits, int64_t* counts, void* workspace,
+                         size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_surface_implicit(const double* oriented_normals, int64_t n, int bits, int radius, int64_t n_vertices,
+                          int64_t* vertex_keys, double* f, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_surface_triangles(const double* f, int64_t n_vertices, int64_t n, int bits, int64_t n_triangles,
+                           int64_t* triangle_ids, int64_t* count, void* workspace, size_t workspace_bytes,
+                           pcgc_stream_t stream);
+int pcgc_surface_mesh(const int64_t* edge_ids, int64_t n_edges, const int64_t* triangle_ids, int64_t n_triangles,
+                      const double* f, int64_t n_vertices, int64_t n, int bits, double* vertices, int32_t* triangles,
+                      void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

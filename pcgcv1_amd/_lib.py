@@ -78,6 +78,12 @@ HIP_API = {
     "pcgc_clean_components": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_plane_count": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp]),
     "pcgc_plane_select": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "pcgc_surface_workspace_bytes": (c_sz, [c_int, c_i64]),
+    "pcgc_surface_orient": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_surface_lattice": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_surface_implicit": (c_int, [c_vp, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_surface_triangles": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_surface_mesh": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d1_workspace_bytes": (c_sz, [c_int]),
     "pcgc_d1_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),

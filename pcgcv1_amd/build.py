@@ -47,6 +47,7 @@ HIP_SOURCES = {
     "clean.hip": [],
     "components.hip": [],
     "plane.hip": [],
+    "surface.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

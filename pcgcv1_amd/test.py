@@ -72,6 +72,9 @@ def parse_args(argv=None):
     add_smooth_argument(ap)
     ap.add_argument("--render", default="", metavar="X.png",
                     help="decompress only: also draw the cloud just written into this png (pcgcv1_amd/render.py, default view and size)")
+    ap.add_argument("--mesh", default="", metavar="X.obj",
+                    help="decompress only: also reconstruct a triangle mesh (.obj or .off) from the cloud just written "
+                         "(pcgcv1_amd/surface.py: estimated normals, default radius and orientation)")
     args = ap.parse_args(argv)
     check_clean_argument(ap, args)
     check_smooth_argument(ap, args)
@@ -224,14 +227,28 @@ def _self_launch(argv, n):
 
 def main(argv=None):
     args = parse_args(argv)
-    if not args.render:
+    if not args.render and not args.mesh:
         return _main(args, argv)
-    if args.command != "decompress":
+    several = args.gpu > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if args.render and args.command != "decompress":
         raise SystemExit("--render belongs to decompress: it draws the cloud decompress has just written")
-    if args.gpu > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if args.render and several:
         raise SystemExit("--render runs on one GPU")
+    if args.mesh:
+        if args.command != "decompress":
+            raise SystemExit("--mesh belongs to decompress: it reconstructs a surface from the cloud decompress has just written")
+        if several:
+            raise SystemExit("--mesh runs on one GPU")
+        from .surface import check_output
+        try:
+            check_output(args.mesh)
+        except ValueError as e:
+            raise SystemExit(str(e))
     _main(args, argv)
-    _render_output(args)
+    if args.render:
+        _render_output(args)
+    if args.mesh:
+        _mesh_output(args)
 
 
 def _render_output(args):
@@ -242,6 +259,24 @@ def _render_output(args):
     points, colors = load_ply_colors(args.output, as_float=True)
     write_png(args.render, render(points, colors))
     print("Render {} to {}: {}s ({} points)".format(args.output, args.render, round(time.time() - t0, 4), len(points)))
+
+
+def _mesh_output(args):
+    """--mesh: a surface from the ply decompress has just written (args.output): estimated normals, default radius and orientation.
+    Where <name>.frame put the cloud into a scan's units, the voxels are taken back to the grid and the mesh is written in those units."""
+    import numpy as np
+    from .dataprocess.inout_points import load_ply_scan
+    from .surface import mesh_file
+    t0 = time.time()
+    points, _, _ = load_ply_scan(args.output)
+    frame = None
+    if os.path.exists(args.input + ".frame"):
+        from .ingest import read_frame
+        frame = read_frame(args.input + ".frame")
+        points = (points - frame.origin) / frame.step
+    voxels = np.unique(np.rint(points).astype(np.int32), axis=0)
+    print(mesh_file(voxels, None, args.mesh, frame=frame))
+    print("Mesh {} to {}: {}s".format(args.output, args.mesh, round(time.time() - t0, 4)))
 
 
 def _main(args, argv):

@@ -1,0 +1,88 @@
+"""What surface reconstruction costs: the parts of pcgcv1_amd.surface.reconstruct one by one and the whole call, with normals from
+metrics.estimate_normals, on two clouds:
+  * sparse: tools/register_bench.py's scan (1 000 000 points of ingest_bench's sphere, squeezed and with a bump) at 10 bits, about
+    800 k voxels, the size of the codec's bench cloud.  A million points over a surface of more than a million voxels leave a
+    cloud full of holes: many components, few rounds, a mesh in pieces;
+  * dense: 4 000 000 points of the same surface at 9 bits, a closed sheet that the propagation has to walk across;
+and for scale the numpy rule (tests/_surface_ref.py) next to the device on a cloud the rule finishes in seconds (a sphere of
+radius 50 at 7 bits).
+
+    python tools/surface_bench.py [--repeats 7] > profiles/surface_bench.txt
+
+Per line: two warm-up calls, then the median (and the range) of `repeats` calls, each timed with a host clock around the call
+and a device synchronise."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from components_bench import voxels                                      # noqa: E402
+from ingest_bench import line, timed                                      # noqa: E402
+from register_bench import make_scan                                      # noqa: E402
+from pcgcv1_amd import _lib, metrics, surface                            # noqa: E402
+
+
+def one_cloud(name, n_points, bits_, radius, repeats):
+    points, _ = make_scan(n_points, 1)
+    vox = voxels(points, bits_).contiguous()
+    out, ts = timed(lambda: metrics.estimate_normals(vox), 3, warmup=1)
+    print("%s: the scan of tools/register_bench.py, %d points, %d bits: %d occupied voxels; radius %d; %d repeats" % (
+        name, len(points), bits_, len(vox), radius, repeats))
+    line("estimate_normals (not part of the call below)", ts)
+    p, nr, key, bits = surface._validated(vox, out, bits_)
+    spec, tau = surface.parse_orient("propagate"), surface.DEFAULT_TAU
+    lat = surface._Lattice(p, bits)
+    (seed, n_components), ts = timed(lambda: surface._seeds(p, key, bits, spec.gap), repeats)
+    line("seeds: components, the largest key per label", ts, "   %d components" % n_components.item())
+    for batch in (8, surface.ROUNDS_PER_READ, 256):
+        (sign, rounds, reads), ts = timed(lambda: lat.orient(nr, seed, spec.gap, tau, batch), repeats)
+        line("pcgc_surface_orient, %d rounds per read-back" % batch, ts, "   %d rounds, %d read-backs" % (rounds, reads))
+    N = (sign.double()[:, None] * nr.double()).contiguous()
+    (n_cells, n_lattice), ts = timed(lat.lattice, repeats)
+    line("pcgc_surface_lattice (cells and vertices)", ts, "   %d cells, %d vertices" % (n_cells, n_lattice))
+    (_, f), ts = timed(lambda: lat.implicit(N, radius), repeats)
+    line("pcgc_surface_implicit, R = %d" % radius, ts)
+    if radius != 5:
+        line("pcgc_surface_implicit, R = 5", timed(lambda: lat.implicit(N, 5), repeats)[1])
+    ids, ts = timed(lambda: lat.triangle_ids(f), repeats)
+    line("pcgc_surface_triangles (count, read, emit)", ts, "   %d triangles" % len(ids))
+    (v, t), ts = timed(lambda: lat.mesh(f, ids), repeats)
+    line("torch.unique of the ids, pcgc_surface_mesh", ts, "   %d vertices" % len(v))
+    del ids, v, t
+    (v, t, report), ts = timed(lambda: surface.reconstruct(p, nr, bits, radius), repeats)
+    line("surface.reconstruct (normals given, mesh to the host)", ts)
+    print("  " + surface.summary_line(report))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--radius", type=int, default=surface.DEFAULT_RADIUS)
+    ap.add_argument("--no_rule", action="store_true", help="skip the numpy rule at 7 bits")
+    a = ap.parse_args()
+    _lib.require_gpu()
+    one_cloud("sparse", 1000000, 10, a.radius, a.repeats)
+    one_cloud("dense", 4000000, 9, a.radius, a.repeats)
+    if a.no_rule:
+        return
+    import _surface_ref as ref
+    ball = ref.sphere((63.5, 63.5, 63.5), 50.0, n=1500000)
+    normals = metrics.estimate_normals(ball)
+    t0 = time.perf_counter()
+    want_v, want_t, _ = ref.reconstruct(ball, normals, 7, a.radius)
+    dt = time.perf_counter() - t0
+    (v, t, _), ts = timed(lambda: surface.reconstruct(ball, normals, 7, a.radius), a.repeats)
+    same = v.tobytes() == want_v.tobytes() and np.array_equal(surface.canonical(t), surface.canonical(want_t))
+    line("a sphere of %d voxels at 7 bits: surface.reconstruct" % len(ball), ts, "   the numpy rule (CPU, one call): %.2f s, %s" % (
+        dt, "the same mesh" if same else "ANOTHER MESH"))
+
+
+if __name__ == "__main__":
+    main()
