@@ -864,6 +864,56 @@ int pcgc_surface_mesh(const int64_t* edge_ids, int64_t n_edges, const int64_t* t
                       const double* f, int64_t n_vertices, int64_t n, int bits, double* vertices, int32_t* triangles,
                       void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
 
+/* ---- a smaller mesh: quadric vertex clustering (pcgcv1_amd/surface.py: simplify; tests/_simplify_ref.py is the
+ * rule in numpy) ----
+ * vertices float64 [V,3] in voxel units, finite and within [-2, res + 2) on every axis, res = 2^bits, 1 <= bits <= 12, 1 <= V <
+ * 2^31; triangles int32 [T,3] with indices in 0..V-1, 3 T < 2^31; cell an integer in 1..64.  All float arithmetic is float64 in
+ * the order written here, without contraction; the sums start at 0.0.
+ *
+ * 0. Canonical order (the caller's): every triangle rotated so that its smallest index comes first, the rows sorted
+ *    lexicographically.  Everything below takes the triangles in that order, so the result is a function of the mesh as a set of
+ *    oriented triangles.
+ * 1. Clusters (pcgc_simplify_keys): c = floor((v + 2.0) / cell) per axis, M = (res + 4 + cell - 1) / cell (integers), the key
+ *    (cx * M + cy) * M + cz; -1 for a vertex outside the range.  The clusters are the distinct keys ascending (the caller
+ *    uniques), K of them; rank int32 [V] = the position of a vertex' key among them.  A cluster's centre is o = (c + 0.5) * cell -
+ *    2.
+ * 2. Quadric.  A triangle belongs to each of the distinct clusters of its three corners, once each; a cluster takes its triangles
+ *    in ascending canonical position.  pcgc_simplify_incidence writes words int32 [T,3]: the rank of each corner, or K where an
+ *    earlier corner of the same triangle has that rank already; the caller sorts the 3 T words stably, tri_entry int64 [3 T] =
+ *    the indices of the sorted words (entry e is corner e % 3 of triangle e / 3), tri_start int64 [K + 1] = where each rank's run
+ *    starts (tri_start[K] = the first word K); vert_index int64 [V] = the vertices sorted stably by rank and vert_start int64
+ *    [K + 1] likewise.  Per triangle with the corners v0 v1 v2: q0 = v0 - o, e1 = (v1 - o) - q0, e2 = (v2 - o) - q0, n = e1 x e2 as
+ *    (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x) (unnormalised: the weight is the squared area), d = -((nx q0x + ny
+ *    q0y) + nz q0z); A += (nx nx, nx ny, nx nz, ny ny, ny nz, nz nz), b += (nx d, ny d, nz d).  sum += v - o over the cluster's
+ *    vertices in ascending index, m = sum / count.
+ * 3. Placement (pcgc_simplify_place): r_i = (-b_i) - ((A_i0 m0 + A_i1 m1) + A_i2 m2); the cyclic Jacobi of the normal estimation
+ *    (csrc/jacobi3.h) on a copy of A gives the eigenvalues l_i and the eigenvectors E_i (columns); lmax = the largest l_i; s = 0,
+ *    and for i = 0, 1, 2 with l_i > 1e-3 * lmax: t = ((E_0i r0 + E_1i r1) + E_2i r2) / l_i, s_j = s_j + E_ji * t; x = m + s.  Where
+ *    lmax is not positive or some |x_j| > cell / 2 (the optimum left the cube) the cluster falls back to x = m and fallback uint8
+ *    [K] is 1.  placed float64 [K,3] = o + x.  The truncation keeps a flat or a creased cluster well-posed.
+ * 4. Triangles, as a chain (pcgc_simplify_remap, then the caller's sort, unique and integer scatter-add).  Every corner maps to
+ *    its rank; a triangle with two equal corners is degenerate: triples int32 [T,3] = (-1, -1, -1), sign int32 [T] = 0, packed -1.
+ *    Otherwise, rotated so that its smallest rank a comes first, it reads (a, b, c): triples = (a, lo, hi) = (a, min(b, c),
+ *    max(b, c)), sign = +1 if b < c else -1, packed int64 [T] (may be NULL; needs K <= 2^21) = a << 42 | lo << 21 | hi.  The net
+ *    multiplicity of a triple is the sum of the signs of the triangles that map to it: 0, the triple vanishes (cancelled);
+ *    otherwise it gives one triangle, (a, lo, hi) if positive and (a, hi, lo) if negative (folded where the absolute value is 2 or
+ *    more).  The output triangles ascend in (a, lo, hi); the clusters none of them names are removed and the rest renumbered in
+ *    ascending key.  The output is the image of the input 2-chain under the vertex map: where no triple is folded, a closed input
+ *    gives an output in which every undirected edge is traversed equally often in both directions.
+ *
+ * No atomics, no workspace, nothing read back; two calls give the same bytes.  A bad argument returns an error before any memory
+ * is touched.  Vertices outside the range and indices outside the vertices are the caller's to refuse; every index is checked
+ * before it is used, so they touch nothing out of bounds. */
+int pcgc_simplify_keys(const double* vertices, int64_t n_vertices, int bits, int cell, int64_t* keys, pcgc_stream_t stream);
+int pcgc_simplify_incidence(const int32_t* triangles, int64_t n_triangles, const int32_t* rank, int64_t n_vertices,
+                            int64_t n_clusters, int32_t* words, pcgc_stream_t stream);
+int pcgc_simplify_place(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                        const int64_t* cluster_keys, int64_t n_clusters, int bits, int cell, const int64_t* tri_start,
+                        const int64_t* tri_entry, const int64_t* vert_start, const int64_t* vert_index, double* placed,
+                        uint8_t* fallback, pcgc_stream_t stream);
+int pcgc_simplify_remap(const int32_t* triangles, int64_t n_triangles, const int32_t* rank, int64_t n_vertices,
+                        int64_t n_clusters, int32_t* triples, int32_t* sign, int64_t* packed, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

@@ -84,6 +84,10 @@ HIP_API = {
     "pcgc_surface_implicit": (c_int, [c_vp, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_surface_triangles": (c_int, [c_vp, c_i64, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_surface_mesh": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_simplify_keys": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
+    "pcgc_simplify_incidence": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "pcgc_simplify_place": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pcgc_simplify_remap": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "pcgc_d1_workspace_bytes": (c_sz, [c_int]),
     "pcgc_d1_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),

@@ -48,6 +48,7 @@ HIP_SOURCES = {
     "components.hip": [],
     "plane.hip": [],
     "surface.hip": ["-ffp-contract=off"],
+    "simplify.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

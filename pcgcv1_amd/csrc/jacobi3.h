@@ -1,20 +1,28 @@
 // The symmetric 3x3 eigen-solver the normal estimation (mesh.hip) and the scan smoothing (smooth.hip) share: one copy, so that
 // both follow the same operations in the same order.  The including files are built with -ffp-contract=off; tests/_smooth_ref.py
-// restates the loop in numpy operation for operation.  Internal linkage: the objects link into one library.
+// restates the loop in numpy operation for operation.  Internal linkage: the objects link into one library.  Without hipcc
+// (tests/surface_quadric_check.cpp, through surface_quadric.h) the same text is a host function.
 #pragma once
 #include <cmath>
+#if defined(__HIPCC__)
 #include "common.h"
+#define PCGC_JACOBI_FN __device__
+#else
+#define PCGC_JACOBI_FN inline
+#endif
 
 namespace pcgc {
 namespace {
 
 // cyclic Jacobi on the symmetric 3x3 a (destroyed): eigenvalues on the diagonal, eigenvectors in the columns of v
-__device__ void jacobi3(double a[3][3], double v[3][3]) {
+PCGC_JACOBI_FN void jacobi3(double a[3][3], double v[3][3]) {
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) v[r][c] = r == c ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 32; ++sweep) {
     if (a[0][1] == 0.0 && a[0][2] == 0.0 && a[1][2] == 0.0) break;
+#if defined(__HIPCC__)
 #pragma unroll
+#endif
     for (int pq = 0; pq < 3; ++pq) {
       const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
       const double apq = a[p][q];

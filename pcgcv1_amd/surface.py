@@ -7,8 +7,12 @@ neighbours; marching tetrahedra over the Kuhn cut of those boxes give an indexed
 cloud is a closed sheet.  torch sorts and uniques (the seeds per component, the lattice edges that carry a vertex); everything
 else is a kernel.
 
+A fourth, optional part makes the mesh small enough to use (pcgc_simplify_*; csrc/simplify.hip; DESIGN.md §7m;
+tests/_simplify_ref.py is its rule): the vertices in a cube of CELL voxels become one, placed by the quadric of the triangles
+that touch the cube, and the triangles follow as a chain.  It runs on the device, before the mesh goes to the host.
+
     python -m pcgcv1_amd.surface --input X_rec.ply --output X.obj [--radius R] [--orient given|propagate[:G]|view:X,Y,Z]
-                                 [--estimate_normals] [--frame X.frame]
+                                 [--estimate_normals] [--frame X.frame] [--simplify CELL]
 """
 import argparse
 import ctypes
@@ -24,7 +28,9 @@ MAX_GAP, DEFAULT_GAP = 8, 1
 DEFAULT_TAU = (0.9, 0.0)
 MAX_STAGES = 8
 NORM_TOLERANCE = 1e-3
-ROUNDS_PER_READ = 32        # rounds queued per read-back of the state word; the result does not depend on it
+MAX_CELL = 64               # simplify: the largest cluster cube, in voxels
+PACK_LIMIT = 1 << 21        # simplify: three indices below this pack into one int64 sort key
+ROUNDS_PER_READ = 32       # rounds queued per read-back of the state word; the result does not depend on it
 
 
 # ---------------------------------------------------------------------------- specs
@@ -88,6 +94,12 @@ def check_tau(tau):
     if tau[-1] != 0.0:
         raise ValueError("surface: the last stage threshold is %r, it must be 0.0 (the propagation would not end)" % (tau[-1],))
     return tau
+
+
+def check_cell(cell):
+    if isinstance(cell, bool) or int(cell) != cell or not 1 <= int(cell) <= MAX_CELL:
+        raise ValueError("surface: simplify: cell = %r outside 1..%d" % (cell, MAX_CELL))
+    return int(cell)
 
 
 def check_bits(bits):
@@ -332,11 +344,176 @@ def bits_for(points):
     return clean_bits_for(points)
 
 
-def reconstruct(points, normals=None, bits=None, radius=DEFAULT_RADIUS, orient="propagate", frame=None, gap=DEFAULT_GAP, tau=DEFAULT_TAU):
+# ---------------------------------------------------------------------------- simplification
+def _validated_mesh(vertices, triangles, bits):
+    """float64 [V,3] and int32 [T,3] on the device; a ValueError names the first bad row (one read-back)"""
+    import torch
+    dev = _lib.require_gpu()
+    v = vertices if torch.is_tensor(vertices) else torch.from_numpy(np.ascontiguousarray(np.asarray(vertices, np.float64).reshape(-1, 3)))
+    v = v.to(dev, torch.float64).reshape(-1, 3).contiguous()
+    t = triangles if torch.is_tensor(triangles) else torch.from_numpy(np.ascontiguousarray(np.asarray(triangles).reshape(-1, 3).astype(np.int64)))
+    t = t.to(dev).reshape(-1, 3)
+    V, T = int(v.shape[0]), int(t.shape[0])
+    if V >= 2 ** 31 or 3 * T >= 2 ** 31:
+        raise ValueError("surface: simplify: %d vertices and %d triangles are too many (V and 3 T below 2^31)" % (V, T))
+    hi = float((1 << bits) + 2)
+    bad_v = ~(torch.isfinite(v) & (v >= -2.0) & (v < hi)).all(1)
+    bad_t = ((t < 0) | (t >= V)).any(1)
+    flags = torch.stack([bad_v.any(), bad_t.any()]).tolist()             # one read-back
+    if flags[0]:
+        row = int(bad_v.nonzero()[0])
+        raise ValueError("surface: simplify: vertex row %d, %s, is not finite or lies outside [-2, %d)" % (row, v[row].tolist(), int(hi)))
+    if flags[1]:
+        row = int(bad_t.nonzero()[0])
+        raise ValueError("surface: simplify: triangle row %d, %s, names a vertex outside 0..%d" % (row, t[row].tolist(), V - 1))
+    return v, t.to(torch.int32).contiguous()
+
+
+def _sorted_rows(a, b, c, limit, pack_limit):
+    """the order that sorts the rows (a, b, c) of int64 columns below `limit` lexicographically: one sort of the packed rows
+    where three columns fit 63 bits, stable sorts from the last column to the first otherwise"""
+    import torch
+    if limit <= pack_limit <= PACK_LIMIT:
+        return torch.argsort(a << 42 | b << 21 | c, stable=True)
+    order = torch.argsort(c, stable=True)
+    return order[torch.argsort((a << 31 | b)[order], stable=True)]
+
+
+def _canonical_device(t, n_vertices, pack_limit):
+    """canonical() on the device tensor int32 [T,3]"""
+    import torch
+    t = t.long()
+    first = torch.where((t[:, 0] <= t[:, 1]) & (t[:, 0] <= t[:, 2]), 0, torch.where(t[:, 1] <= t[:, 2], 1, 2))
+    cols = [torch.gather(t, 1, ((first + s) % 3)[:, None])[:, 0] for s in range(3)]
+    order = _sorted_rows(cols[0], cols[1], cols[2], n_vertices, pack_limit)
+    return torch.stack(cols, 1)[order].to(torch.int32).contiguous()
+
+
+class _Simplifier(object):
+    """the steps of the rule on device tensors, one method per part (tools/surface_bench.py times them one by one)"""
+
+    def __init__(self, v, bits, cell, pack_limit=None):
+        import torch
+        self.torch, self.lib, self.v, self.bits, self.cell = torch, _lib.hip(), v, bits, cell
+        self.V, self.dev = int(v.shape[0]), v.device
+        self.pack_limit = PACK_LIMIT if pack_limit is None else int(pack_limit)
+
+    def clusters(self):
+        torch = self.torch
+        keys = torch.empty(self.V, dtype=torch.int64, device=self.dev)
+        _lib.check(self.lib.pcgc_simplify_keys(_lib.dptr(self.v), self.V, self.bits, self.cell, _lib.dptr(keys), _lib.stream()), "pcgc_simplify_keys")
+        self.keys, rank = torch.unique(keys, return_inverse=True)
+        self.K = int(self.keys.shape[0])
+        self.rank = rank.to(torch.int32).contiguous()
+        self.marks = torch.arange(self.K + 1, dtype=torch.int32, device=self.dev)
+        by_rank, self.vert_index = torch.sort(self.rank, stable=True)
+        self.vert_start = torch.searchsorted(by_rank, self.marks).contiguous()
+        return self.K
+
+    def incidence(self, t):
+        torch = self.torch
+        T = int(t.shape[0])
+        if T == 0:
+            self.tri_entry, self.tri_start = None, torch.zeros(self.K + 1, dtype=torch.int64, device=self.dev)
+            return
+        words = torch.empty(T * 3, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.pcgc_simplify_incidence(_lib.dptr(t), T, _lib.dptr(self.rank), self.V, self.K, _lib.dptr(words), _lib.stream()),
+                   "pcgc_simplify_incidence")
+        words, self.tri_entry = torch.sort(words, stable=True)
+        self.tri_start = torch.searchsorted(words, self.marks).contiguous()
+
+    def place(self, t):
+        torch = self.torch
+        placed = torch.empty((self.K, 3), dtype=torch.float64, device=self.dev)
+        fallback = torch.empty(self.K, dtype=torch.uint8, device=self.dev)
+        T = int(t.shape[0])
+        _lib.check(self.lib.pcgc_simplify_place(_lib.dptr(self.v), self.V, _lib.dptr(t) if T else None, T, _lib.dptr(self.keys), self.K, self.bits,
+                                                self.cell, _lib.dptr(self.tri_start), _lib.dptr(self.tri_entry), _lib.dptr(self.vert_start),
+                                                _lib.dptr(self.vert_index), _lib.dptr(placed), _lib.dptr(fallback), _lib.stream()),
+                   "pcgc_simplify_place")
+        return placed, fallback
+
+    def remap(self, t):
+        """-> (rows int64 [n,3]: the distinct triples ascending, mult int64 [n], total int64 [n], the number of degenerate triangles
+        (a device scalar))"""
+        torch = self.torch
+        T = int(t.shape[0])
+        if T == 0:
+            none = torch.zeros(0, dtype=torch.int64, device=self.dev)
+            return none.reshape(0, 3), none, none, none.sum()
+        packs = self.K <= self.pack_limit <= PACK_LIMIT
+        triples = torch.empty((T, 3), dtype=torch.int32, device=self.dev)
+        sign = torch.empty(T, dtype=torch.int32, device=self.dev)
+        packed = torch.empty(T, dtype=torch.int64, device=self.dev) if packs else None
+        _lib.check(self.lib.pcgc_simplify_remap(_lib.dptr(t), T, _lib.dptr(self.rank), self.V, self.K, _lib.dptr(triples), _lib.dptr(sign),
+                                                _lib.dptr(packed), _lib.stream()), "pcgc_simplify_remap")
+        keep = triples[:, 0] >= 0
+        sign = sign[keep].long()
+        n_degenerate = T - keep.sum()
+        if packs:
+            uk, inv, total = torch.unique(packed[keep], return_inverse=True, return_counts=True)
+            rows = torch.stack([uk >> 42, (uk >> 21) & (PACK_LIMIT - 1), uk & (PACK_LIMIT - 1)], 1)
+        else:
+            rows = triples[keep].long()
+            order = _sorted_rows(rows[:, 0], rows[:, 1], rows[:, 2], self.K, self.pack_limit)
+            rows, sign = rows[order], sign[order]
+            new = torch.ones(rows.shape[0], dtype=torch.bool, device=self.dev)
+            new[1:] = (rows[1:] != rows[:-1]).any(1)
+            inv = torch.cumsum(new, 0) - 1
+            rows = rows[new]
+            total = torch.zeros(rows.shape[0], dtype=torch.int64, device=self.dev).index_add_(0, inv, torch.ones_like(inv))
+        mult = torch.zeros(rows.shape[0], dtype=torch.int64, device=self.dev).index_add_(0, inv, sign)      # integer: any order, the same sum
+        return rows, mult, total, n_degenerate
+
+
+def _simplify_device(v, t, bits, cell, pack_limit=None):
+    """the rule on validated device tensors -> (vertices float64 [V',3], triangles int32 [T',3], report), on the device"""
+    import torch
+    V, T = int(v.shape[0]), int(t.shape[0])
+    report = dict(cell=cell, clusters=0, vertices_in=V, triangles_in=T, degenerate=0, cancelled=0, merged=0, folded=0, fallback=0, unused=0)
+    if V == 0:
+        return v, t, report
+    s = _Simplifier(v, bits, cell, pack_limit)
+    t = _canonical_device(t, V, s.pack_limit)
+    K = s.clusters()
+    s.incidence(t)
+    placed, fallback = s.place(t)
+    rows, mult, total, n_degenerate = s.remap(t)
+    live = mult != 0
+    kept, positive = rows[live], (mult[live] > 0)[:, None]
+    tri = torch.where(positive, kept, kept[:, [0, 2, 1]])
+    used = torch.unique(tri)
+    counts = torch.stack([n_degenerate, (~live).sum(), (total > 1).sum(), (mult.abs() >= 2).sum(), fallback.sum()]).tolist()    # one read-back
+    report.update(clusters=K, degenerate=counts[0], cancelled=counts[1], merged=counts[2], folded=counts[3], fallback=counts[4],
+                  unused=K - int(used.shape[0]))
+    return placed[used].contiguous(), torch.searchsorted(used, tri.contiguous()).to(torch.int32).reshape(-1, 3), report
+
+
+def simplify(vertices, triangles, bits, cell, report=None, _pack_limit=None):
+    """Quadric vertex clustering (include/pcgc.h, pcgc_simplify_*; tests/_simplify_ref.py is the rule in numpy): one vertex per
+    cube of `cell` voxels, placed where the summed squared distance to the planes of the triangles that touch the cube is
+    smallest; the triangles are the image of the input's oriented triangles.  vertices float64 [V,3] in voxel units within
+    [-2, 2^bits + 2), triangles int32 [T,3] -> (vertices, triangles), numpy arrays or device tensors as given.  report (a dict)
+    gains cell, clusters, vertices_in, triangles_in, degenerate, cancelled, merged, folded, fallback and unused.  _pack_limit (the
+    tests'): the largest count whose rows are still ordered by one packed sort."""
+    import torch
+    bits, cell = check_bits(bits), check_cell(cell)
+    as_tensors = torch.is_tensor(vertices)
+    v, t = _validated_mesh(vertices, triangles, bits)
+    v, t, rep = _simplify_device(v, t, bits, cell, _pack_limit)
+    if report is not None:
+        report.update(rep)
+    return (v, t) if as_tensors else (v.cpu().numpy(), t.cpu().numpy())
+
+
+def reconstruct(points, normals=None, bits=None, radius=DEFAULT_RADIUS, orient="propagate", frame=None, gap=DEFAULT_GAP, tau=DEFAULT_TAU,
+                simplify=None):
     """points int32 [n,3] distinct voxels -> (vertices float64 [V,3], triangles int32 [T,3], report dict), numpy.  Without normals
     metrics.estimate_normals supplies them; without bits the frame's, or the fewest that hold the cloud.  The vertices are in
-    voxel units (voxel q is the unit box about q), or with an ingest.Frame in the scan's own."""
+    voxel units (voxel q is the unit box about q), or with an ingest.Frame in the scan's own.  simplify: a cell size in voxels;
+    the mesh goes through `simplify` on the device before it is measured and brought to the host (report["simplify"])."""
     radius, spec, tau = check_radius(radius), _spec(orient, gap), check_tau(tau)
+    cell = None if simplify is None else check_cell(simplify)
     if bits is None:
         bits = frame.bits if frame is not None else bits_for(points.cpu().numpy() if hasattr(points, "cpu") else points)
     if normals is None:
@@ -353,6 +530,8 @@ def reconstruct(points, normals=None, bits=None, radius=DEFAULT_RADIUS, orient="
     n_cells, n_lattice = lat.lattice()
     _, f = lat.implicit(N, radius)
     vertices, triangles = lat.mesh(f, lat.triangle_ids(f))
+    if cell is not None:                                                  # in voxel units, before anything crosses to the host
+        vertices, triangles, report["simplify"] = _simplify_device(vertices, triangles, bits, cell)
     n_boundary = _boundary_edges_device(triangles, int(vertices.shape[0]))
     vertices, triangles = vertices.cpu().numpy(), triangles.cpu().numpy()
     report.update(rounds=rounds, cells=n_cells, lattice_vertices=n_lattice, vertices=len(vertices), triangles=len(triangles),
@@ -364,8 +543,15 @@ def reconstruct(points, normals=None, bits=None, radius=DEFAULT_RADIUS, orient="
 
 
 def summary_line(report):
-    return "surface: %d voxels, %d components, %d rounds, %d vertices, %d triangles, %d boundary edges" % tuple(
+    """one line; a second one where the mesh was simplified:
+    simplify: cell 2, 6086 vertices and 12168 triangles -> 458 and 912, 18 of 458 clusters placed at their mean"""
+    line = "surface: %d voxels, %d components, %d rounds, %d vertices, %d triangles, %d boundary edges" % tuple(
         report[k] for k in ("voxels", "components", "rounds", "vertices", "triangles", "boundary_edges"))
+    if "simplify" in report:
+        s = report["simplify"]
+        line += "\nsimplify: cell %d, %d vertices and %d triangles -> %d and %d, %d of %d clusters placed at their mean" % (
+            s["cell"], s["vertices_in"], s["triangles_in"], report["vertices"], report["triangles"], s["fallback"], s["clusters"])
+    return line
 
 
 # ---------------------------------------------------------------------------- command line
@@ -385,8 +571,12 @@ def parse_args(argv=None):
                     help="how the normals get a side: as they are, by propagation over links of gap G, or towards an eye")
     ap.add_argument("--estimate_normals", action="store_true", help="estimate the normals (radius 10, 20 neighbours) instead of reading them")
     ap.add_argument("--frame", default="", metavar="X.frame", help="write the vertices in the scan's units (pcgcv1_amd/ingest.py)")
+    ap.add_argument("--simplify", type=int, default=None, metavar="CELL",
+                    help="simplify the mesh on the GPU before it is written: one vertex per cube of CELL voxels (1..%d), placed by its quadric" % MAX_CELL)
     args = ap.parse_args(argv)
     try:                                                                  # before any file is read
+        if args.simplify is not None:
+            check_cell(args.simplify)
         args.radius = check_radius(args.radius)
         args.orient = parse_orient(args.orient)
         check_output(args.output)
@@ -395,9 +585,10 @@ def parse_args(argv=None):
     return args
 
 
-def mesh_file(points, normals, output, radius=DEFAULT_RADIUS, orient="propagate", frame=None):
-    """reconstruct and write -> the summary line"""
-    vertices, triangles, report = reconstruct(points, normals, frame.bits if frame is not None else None, radius, orient, frame)
+def mesh_file(points, normals, output, radius=DEFAULT_RADIUS, orient="propagate", frame=None, simplify=None):
+    """reconstruct (and simplify) and write -> the summary line (two lines with simplify)"""
+    vertices, triangles, report = reconstruct(points, normals, frame.bits if frame is not None else None, radius, orient, frame,
+                                              simplify=simplify)
     write_mesh(output, vertices, triangles)
     return summary_line(report)
 
@@ -414,7 +605,7 @@ def main(argv=None):
         normals = None
     elif normals is None:
         raise SystemExit("%s has no nx ny nz properties: write them into the ply, or pass --estimate_normals" % args.input)
-    print(mesh_file(points, normals, args.output, args.radius, args.orient, frame))
+    print(mesh_file(points, normals, args.output, args.radius, args.orient, frame, args.simplify))
     print("wrote " + args.output)
 
 

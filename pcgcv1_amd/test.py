@@ -75,9 +75,20 @@ def parse_args(argv=None):
     ap.add_argument("--mesh", default="", metavar="X.obj",
                     help="decompress only: also reconstruct a triangle mesh (.obj or .off) from the cloud just written "
                          "(pcgcv1_amd/surface.py: estimated normals, default radius and orientation)")
+    ap.add_argument("--mesh_simplify", type=int, default=None, metavar="CELL",
+                    help="with --mesh: simplify the mesh on the GPU before it is written, one vertex per cube of CELL voxels (1..64) "
+                         "placed by its quadric (pcgcv1_amd/surface.py: simplify)")
     args = ap.parse_args(argv)
     check_clean_argument(ap, args)
     check_smooth_argument(ap, args)
+    if args.mesh_simplify is not None:
+        from .surface import check_cell
+        try:
+            check_cell(args.mesh_simplify)
+        except ValueError as e:
+            ap.error(str(e))
+        if not args.mesh:
+            ap.error("--mesh_simplify=%d simplifies the mesh --mesh writes: give --mesh X.obj too" % args.mesh_simplify)
     if args.smooth and (args.command != "compress" or not (args.voxelize or args.voxel_size)):
         ap.error("--smooth moves the float points of a raw scan: it belongs to compress --voxelize or --voxel_size (a voxelised "
                  "ply has no float points)")
@@ -102,7 +113,7 @@ def parse_args(argv=None):
         ap.error("--pointnums=d2 needs normals: %s has no nx ny nz properties (or cannot be read); write them into the ply, or "
                  "pass --estimate_normals to estimate them (radius 10, 20 neighbours)" % args.input)
     # the line every run prints: the ingest flags show up in it only when they are given
-    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size", "clean", "smooth") or v}))
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("voxelize", "voxel_size", "clean", "smooth", "mesh_simplify") or v}))
     return args
 
 
@@ -263,7 +274,8 @@ def _render_output(args):
 
 def _mesh_output(args):
     """--mesh: a surface from the ply decompress has just written (args.output): estimated normals, default radius and orientation.
-    Where <name>.frame put the cloud into a scan's units, the voxels are taken back to the grid and the mesh is written in those units."""
+    Where <name>.frame put the cloud into a scan's units, the voxels are taken back to the grid and the mesh is written in those units.
+    --mesh_simplify CELL: the mesh is simplified on the device first (surface.simplify), and a second line reports it."""
     import numpy as np
     from .dataprocess.inout_points import load_ply_scan
     from .surface import mesh_file
@@ -275,7 +287,7 @@ def _mesh_output(args):
         frame = read_frame(args.input + ".frame")
         points = (points - frame.origin) / frame.step
     voxels = np.unique(np.rint(points).astype(np.int32), axis=0)
-    print(mesh_file(voxels, None, args.mesh, frame=frame))
+    print(mesh_file(voxels, None, args.mesh, frame=frame, simplify=args.mesh_simplify))
     print("Mesh {} to {}: {}s".format(args.output, args.mesh, round(time.time() - t0, 4)))
 
 

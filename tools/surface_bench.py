@@ -4,6 +4,7 @@ metrics.estimate_normals, on two clouds:
     800 k voxels, the size of the codec's bench cloud.  A million points over a surface of more than a million voxels leave a
     cloud full of holes: many components, few rounds, a mesh in pieces;
   * dense: 4 000 000 points of the same surface at 9 bits, a closed sheet that the propagation has to walk across;
+then the parts of surface.simplify at cell 2 on the mesh just built and reconstruct(simplify=2) next to reconstruct(),
 and for scale the numpy rule (tests/_surface_ref.py) next to the device on a cloud the rule finishes in seconds (a sphere of
 radius 50 at 7 bits).
 
@@ -55,10 +56,27 @@ def one_cloud(name, n_points, bits_, radius, repeats):
     line("pcgc_surface_triangles (count, read, emit)", ts, "   %d triangles" % len(ids))
     (v, t), ts = timed(lambda: lat.mesh(f, ids), repeats)
     line("torch.unique of the ids, pcgc_surface_mesh", ts, "   %d vertices" % len(v))
-    del ids, v, t
+    # the parts of simplify at cell 2 on that mesh, as _simplify_device chains them
+    tc, ts = timed(lambda: surface._canonical_device(t, len(v), surface.PACK_LIMIT), repeats)
+    line("simplify: canonical order of the triangles", ts)
+    s = surface._Simplifier(v, bits, 2)
+    K, ts = timed(s.clusters, repeats)
+    line("simplify: keys, unique, vertices by cluster", ts, "   %d clusters" % K)
+    _, ts = timed(lambda: s.incidence(tc), repeats)
+    line("simplify: incidence words, their stable sort", ts)
+    _, ts = timed(lambda: s.place(tc), repeats)
+    line("simplify: pcgc_simplify_place", ts)
+    _, ts = timed(lambda: s.remap(tc), repeats)
+    line("simplify: remap, unique, multiplicities", ts)
+    (sv, st, _), ts = timed(lambda: surface._simplify_device(v, t, bits, 2), repeats)
+    line("simplify: the whole of it on the device", ts, "   %d vertices, %d triangles" % (len(sv), len(st)))
+    del ids, v, t, tc, s, sv, st
     (v, t, report), ts = timed(lambda: surface.reconstruct(p, nr, bits, radius), repeats)
     line("surface.reconstruct (normals given, mesh to the host)", ts)
     print("  " + surface.summary_line(report))
+    (v, t, report), ts = timed(lambda: surface.reconstruct(p, nr, bits, radius, simplify=2), repeats)
+    line("surface.reconstruct(simplify=2), the same session", ts)
+    print("  " + surface.summary_line(report).replace("\n", "\n  "))
 
 
 def main():
