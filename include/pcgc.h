@@ -914,6 +914,64 @@ int pcgc_simplify_place(const double* vertices, int64_t n_vertices, const int32_
 int pcgc_simplify_remap(const int32_t* triangles, int64_t n_triangles, const int32_t* rank, int64_t n_vertices,
                         int64_t n_clusters, int32_t* triples, int32_t* sign, int64_t* packed, pcgc_stream_t stream);
 
+/* ---- a mesh against its cloud: the distance from a point to a triangle mesh (pcgcv1_amd/metrics.py: mesh_error; DESIGN.md §7n;
+ * tests/_mesh_error_ref.py is the rule in numpy, by brute force) ----
+ * points float64 [N,3], vertices float64 [V,3], triangles int32 [T,3] with indices in 0..V-1; every coordinate finite with
+ * |coordinate| < 2^20; 1 <= N, V < 2^31, 1 <= T, 3 T < 2^31.  Everything is IEEE float64, each operation one step in the order
+ * written, without contraction.  For three-vectors x and y:
+ *   x - y   = (x0 - y0, x1 - y1, x2 - y2)
+ *   x . y   = (x0 * y0 + x1 * y1) + x2 * y2
+ *   x cross y = (x1 * y2 - x2 * y1, x2 * y0 - x0 * y2, x0 * y1 - x1 * y0)
+ *   min of x and y = x < y ? x : y
+ * The rule, for a point p and a triangle (a, b, c) (csrc/point_triangle.h is this text as code, for the host and the device):
+ *   seg of p, u, v:  e = v - u, w = p - u, l = e . e, s = w . e;  t = 0 when !(l > 0), otherwise t = s / l, then t = 0 if t < 0,
+ *                then t = 1 if t > 1;  r_k = w_k - t * e_k;  the value is r . r.
+ *   face:        n = (b - a) cross (c - a), nn = n . n;  u = a - p, v = b - p, w = c - p.  The face term counts iff nn > 0 and
+ *                n . (u cross v) >= 0 and n . (v cross w) >= 0 and n . (w cross u) >= 0.  Its value is dn * dn / nn (the product
+ *                first) with dn = n . (p - a).
+ *   d2 of p and the triangle:  m = min of (seg of p, a, b) and (seg of p, b, c);  m = min of m and (seg of p, c, a);  where the face term
+ *                counts, m = min of m and the face term.
+ * A triangle of zero area is a segment or a point; nothing divides by zero.
+ * Per point: best = the minimum of d2 over all triangles, nearest = the smallest triangle index that attains it.  With a gate
+ * max_dist (> 0; +infinity for none) a point with best > max_dist * max_dist is far: best = +infinity, nearest = -1.  The
+ * figures: out4[0] = the sum of best over the points that are not far, in the caller's point order (per thread in grid-stride
+ * order over 256 * min(ceil(N / 256), 1024) threads, a fixed tree per workgroup, the workgroups in index order), divided by
+ * their number; out4[1] = the maximum of those best; both NaN where every point is far; out4[2] = the number of far points;
+ * out4[3] = the number of point-triangle pairs evaluated (the one figure that depends on the cells).  best, nearest and the
+ * other figures depend on the points and the triangle list alone: not on the cells, not on `order`.
+ *
+ * The search lists every triangle in each cubic cell of edge h (a power of two >= 1) that its axis-aligned bounding box
+ * overlaps; the cell of a coordinate x is floor(x / h) - origin, inside a grid of res^3 cells, res <= 1024, that holds the whole
+ * mesh:
+ *   pcgc_meshdist_count: counts int64 [T] = the cells each triangle's box overlaps.  The caller scans them.
+ *   pcgc_meshdist_emit:  words int64 [n_pairs] (n_pairs = the sum, < 2^31): for triangle t, from offsets[t] (the exclusive scan)
+ *                on, cell key << 31 | t for the cells of its box in x, y, z order, key = (x * res + y) * res + z.  The caller sorts
+ *                the words ascending: by cell and, inside a cell, by triangle.
+ *   pcgc_meshdist_prepare: from the sorted words, the cells in the workspace (bit set, rank table, starts: csrc/voxel_grid.h,
+ *                csrc/offgrid_cells.h) and packed float64 [T,9] = the corners of every triangle side by side.
+ *   pcgc_meshdist_query: the walk of one thread per point over Chebyshev shells of cells about its own (which may lie outside
+ *                the grid), clipped to the grid.  After the shell of half-width w every triangle not met lies farther than w h
+ *                from p, so the walk ends once min(best, max_dist^2) < (1 - 2^-20) (w h)^2, or with the grid; the margin covers
+ *                the rounding of d2 (csrc/point_triangle.h argues it).  order int32 [N] (or NULL): a permutation; thread s takes
+ *                point order[s], so a caller that sorts the points by cell has the lanes of a wave walk the same cells.  best
+ *                float64 [N] and nearest int32 [N] are written at the caller's index.
+ * flag int32 [1], zeroed by the caller before the first call, is raised by a triangle that names a vertex outside 0..V-1, a
+ * coordinate that is not finite or reaches 2^20, a triangle outside the grid, offsets or words that do not fit, an order entry
+ * outside 0..N-1.  The query then returns NaN in out4 and in every best, and -1 in every nearest.  Every index is checked
+ * before it is used, so none of this touches memory out of bounds.  No float atomics: two calls give the same bytes. */
+int pcgc_meshdist_count(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, double h, int ox,
+                        int oy, int oz, int res, int64_t* counts, int32_t* flag, pcgc_stream_t stream);
+int pcgc_meshdist_emit(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, double h, int ox,
+                       int oy, int oz, int res, const int64_t* offsets, int64_t n_pairs, int64_t* words, int32_t* flag,
+                       pcgc_stream_t stream);
+size_t pcgc_meshdist_workspace_bytes(int res, int64_t n_pairs, int64_t n_points);
+int pcgc_meshdist_prepare(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
+                          const int64_t* words, int64_t n_pairs, int res, int64_t n_points, double* packed, int32_t* flag,
+                          void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+int pcgc_meshdist_query(const double* points, int64_t n_points, const int32_t* order, const double* packed, int64_t n_triangles,
+                        int64_t n_pairs, double h, int ox, int oy, int oz, int res, double max_dist, double* out4, double* best,
+                        int32_t* nearest, int32_t* flag, void* workspace, size_t workspace_bytes, pcgc_stream_t stream);
+
 /* ---- training step (train_hyper.py:174-214) ------------------------------ */
 /* Gradient of one Conv3D / Conv3DTranspose layer.  D = spatial size of the layer's INPUT x; dz = gradient w.r.t.
  * the layer's pre-activation output (apply pcgc_relu_bwd first), contiguous [B,Do^3,Cout].  Replaces what

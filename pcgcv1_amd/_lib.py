@@ -88,6 +88,12 @@ HIP_API = {
     "pcgc_simplify_incidence": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pcgc_simplify_place": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pcgc_simplify_remap": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "pcgc_meshdist_count": (c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "pcgc_meshdist_emit": (c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pcgc_meshdist_workspace_bytes": (c_sz, [c_int, c_i64, c_i64]),
+    "pcgc_meshdist_prepare": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcgc_meshdist_query": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d1_workspace_bytes": (c_sz, [c_int]),
     "pcgc_d1_mse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcgc_d2_workspace_bytes": (c_sz, [c_int, c_i64]),

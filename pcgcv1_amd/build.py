@@ -49,6 +49,7 @@ HIP_SOURCES = {
     "plane.hip": [],
     "surface.hip": ["-ffp-contract=off"],
     "simplify.hip": ["-ffp-contract=off"],
+    "meshdist.hip": ["-ffp-contract=off"],
     "raht.hip": ["-ffp-contract=off"],
     "rans.hip": [],
     "color_rc.hip": ["-ffp-contract=off"],

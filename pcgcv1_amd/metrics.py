@@ -7,6 +7,8 @@ pc_error_d binary cannot ship, its answers on seeded clouds are pinned in tests/
 `d2_metrics` adds the point-to-plane figures ("mseF,PSNR (p2plane)", eval.py's D2) with pc_error's tie handling
 and normal transfer (csrc/tail.hip), pinned in tests/golden/pc_error_d2.npz.
 `color_metrics` is the tool's `--color=1` table (csrc/color.hip), pinned in tests/golden/pc_error_color.npz.
+`mesh_error` measures a cloud against a triangle mesh: the exact distance from every point to the nearest triangle
+(csrc/meshdist.hip), held to tests/_mesh_error_ref.py bit for bit.
 """
 import numpy as np
 import torch
@@ -368,6 +370,206 @@ def pc_error(points_a, points_b, normals_a=None, resolution=1023, colors_a=None,
     if colors_a is not None:
         out.update(color_metrics(points_a, colors_a, points_b, colors_b))
     return out
+
+
+# ---------------------------------------------------------------------------- a mesh against its cloud
+MESH_MAX_COORD = 2.0 ** 20        # every coordinate of the cloud and the mesh lies strictly inside (include/pcgc.h, pcgc_meshdist_*)
+MESH_PAIRS_PER_TRIANGLE = 32      # the cell edge doubles while the triangles are listed in more cells than this, on average
+
+
+def mesh_cells(lo, hi, h):
+    """-> (h, ox, oy, oz, res): the cells of edge h that cover the box lo .. hi (float64 [3])"""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    origin = np.floor(lo / h)
+    return (float(h), int(origin[0]), int(origin[1]), int(origin[2]), int((np.floor(hi / h) - origin).max()) + 1)
+
+
+def mesh_first_edge(lo, hi):
+    """the smallest power of two h >= 1 whose cells cover the box with at most OFFGRID_MAX_CELLS per axis"""
+    h = 1.0
+    while mesh_cells(lo, hi, h)[4] > OFFGRID_MAX_CELLS:
+        h *= 2.0
+    return h
+
+
+def choose_mesh_cells(lo, hi, n_triangles, count_pairs, edge=None):
+    """-> (cells, pairs).  The cells the triangles of a mesh with the bounding box lo .. hi are listed in: the edge starts at
+    mesh_first_edge and doubles while count_pairs(cells), the number of (cell, triangle) pairs, exceeds 32 per triangle.  It
+    ends: once the edge reaches the widest bounding box, a triangle overlaps at most 8 cells.  edge: that edge and no other."""
+    first = mesh_first_edge(lo, hi)
+    if edge is not None:
+        h = float(edge)
+        if not (h >= first and h <= OFFGRID_MAX_EDGE and np.frexp(h)[0] == 0.5):
+            raise ValueError("mesh_error: the cell edge %r must be a power of two within %g .. 2^20" % (edge, first))
+        cells = mesh_cells(lo, hi, h)
+        return cells, int(count_pairs(cells))
+    h = first
+    while True:
+        cells = mesh_cells(lo, hi, h)
+        pairs = int(count_pairs(cells))
+        if pairs <= MESH_PAIRS_PER_TRIANGLE * n_triangles or h >= OFFGRID_MAX_EDGE:
+            return cells, pairs
+        h *= 2.0
+
+
+def check_max_dist(max_dist):
+    if max_dist is None:
+        return float("inf")
+    if isinstance(max_dist, bool) or not (np.isfinite(max_dist) and max_dist > 0):
+        raise ValueError("mesh_error: max_dist = %r must be finite and positive (None: no gate)" % (max_dist,))
+    return float(max_dist)
+
+
+def _mesh_error_input(points, vertices, triangles):
+    """float64 [N,3], float64 [V,3], int32 [T,3] on the device and the bounding box of the triangles' corners; a ValueError
+    names the first bad row (one read-back)"""
+    dev = _lib.require_gpu()
+
+    def tensor(x, dtype, np_dtype):
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1, 3).astype(np_dtype)))
+        x = x.to(dev).reshape(-1, 3)
+        return (x if dtype is None else x.to(dtype)).contiguous()
+    p, v = tensor(points, torch.float64, np.float64), tensor(vertices, torch.float64, np.float64)
+    t = tensor(triangles, None, np.int64)                                 # in its own integer type until the indices are checked
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.to(torch.int64)
+    N, V, T = int(p.shape[0]), int(v.shape[0]), int(t.shape[0])
+    if N == 0:
+        raise ValueError("mesh_error: the cloud has no points")
+    if T == 0 or V == 0:
+        raise ValueError("mesh_error: the mesh has no triangles")
+    if N >= 2 ** 31 or V >= 2 ** 31 or 3 * T >= 2 ** 31:
+        raise ValueError("mesh_error: %d points, %d vertices and %d triangles are too many (N, V and 3 T below 2^31)" % (N, V, T))
+    bad_p = ~(p.abs() < MESH_MAX_COORD).all(1)                            # a NaN is not below
+    bad_v = ~(v.abs() < MESH_MAX_COORD).all(1)
+    bad_t = ((t < 0) | (t >= V)).any(1)
+    inside = t.clamp(0, V - 1)                                            # what this clamps is refused below
+    used = torch.zeros(V, dtype=torch.bool, device=dev).index_fill_(0, inside.reshape(-1).long(), True)[:, None]
+    lo, hi = torch.where(used, v, float("inf")).min(0)[0], torch.where(used, v, float("-inf")).max(0)[0]       # of the corners alone
+    got = torch.cat([torch.stack([bad_p.any(), bad_v.any(), bad_t.any()]).double(), lo, hi]).tolist()
+    if got[0]:
+        row = int(bad_p.nonzero()[0])
+        raise ValueError("mesh_error: point row %d, %s, is not finite or reaches 2^20" % (row, p[row].tolist()))
+    if got[1]:
+        row = int(bad_v.nonzero()[0])
+        raise ValueError("mesh_error: vertex row %d, %s, is not finite or reaches 2^20" % (row, v[row].tolist()))
+    if got[2]:
+        row = int(bad_t.nonzero()[0])
+        raise ValueError("mesh_error: triangle row %d, %s, names a vertex outside 0..%d" % (row, t[row].tolist(), V - 1))
+    return p, v, inside.to(torch.int32).contiguous(), np.array(got[3:6]), np.array(got[6:9])
+
+
+class _MeshSearch(object):
+    """the triangles of a mesh in their cells, one method per part (tools/surface_bench.py times them one by one)"""
+
+    def __init__(self, v, t, lo, hi):
+        self.lib, self.v, self.t, self.lo, self.hi, self.dev = _lib.hip(), v, t, lo, hi, v.device
+        self.V, self.T = int(v.shape[0]), int(t.shape[0])
+        self.flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    def count(self, cells):
+        self.counts = torch.empty(self.T, dtype=torch.int64, device=self.dev)
+        _lib.check(self.lib.pcgc_meshdist_count(_lib.dptr(self.v), self.V, _lib.dptr(self.t), self.T, *cells, _lib.dptr(self.counts),
+                                                _lib.dptr(self.flag), _lib.stream()), "pcgc_meshdist_count")
+        return int(self.counts.sum().item())                             # the one read-back per edge tried
+
+    def choose(self, edge=None):
+        self.cells, self.pairs = choose_mesh_cells(self.lo, self.hi, self.T, self.count, edge)
+        if not 1 <= self.pairs < 2 ** 31 - 1:
+            raise ValueError("mesh_error: %d pairs of cell and triangle (1 .. 2^31 - 2 are searched)" % self.pairs)
+        return self.cells, self.pairs
+
+    def emit(self):
+        """the pairs of the chosen cells (self.counts are theirs: the last edge counted), sorted"""
+        offsets = (torch.cumsum(self.counts, 0) - self.counts).contiguous()
+        words = torch.full((self.pairs,), -1, dtype=torch.int64, device=self.dev)
+        _lib.check(self.lib.pcgc_meshdist_emit(_lib.dptr(self.v), self.V, _lib.dptr(self.t), self.T, *self.cells, _lib.dptr(offsets),
+                                               self.pairs, _lib.dptr(words), _lib.dptr(self.flag), _lib.stream()), "pcgc_meshdist_emit")
+        self.words = torch.sort(words)[0]
+
+    def prepare(self, n_points):
+        self.n_points = int(n_points)
+        self.ws = torch.empty(int(self.lib.pcgc_meshdist_workspace_bytes(self.cells[4], self.pairs, self.n_points)), dtype=torch.uint8,
+                              device=self.dev)
+        self.packed = torch.empty((self.T, 9), dtype=torch.float64, device=self.dev)
+        _lib.check(self.lib.pcgc_meshdist_prepare(_lib.dptr(self.v), self.V, _lib.dptr(self.t), self.T, _lib.dptr(self.words), self.pairs,
+                                                  self.cells[4], self.n_points, _lib.dptr(self.packed), _lib.dptr(self.flag),
+                                                  _lib.dptr(self.ws), self.ws.numel(), _lib.stream()), "pcgc_meshdist_prepare")
+
+    def order(self, p):
+        """the points by the key of their cell (the nearest cell for a point outside), so that a wave's lanes walk the same cells"""
+        return torch.sort(cell_keys(p, self.cells, clamp=True), stable=True)[1].to(torch.int32).contiguous()
+
+    def query(self, p, order, max_dist):
+        """-> (out4 float64 [4], best float64 [N], nearest int32 [N]), device tensors"""
+        n = int(p.shape[0])
+        out = torch.empty(4, dtype=torch.float64, device=self.dev)
+        best = torch.empty(n, dtype=torch.float64, device=self.dev)
+        nearest = torch.empty(n, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.pcgc_meshdist_query(_lib.dptr(p), n, _lib.dptr(order), _lib.dptr(self.packed), self.T, self.pairs, *self.cells,
+                                                max_dist, _lib.dptr(out), _lib.dptr(best), _lib.dptr(nearest), _lib.dptr(self.flag),
+                                                _lib.dptr(self.ws), self.ws.numel(), _lib.stream()), "pcgc_meshdist_query")
+        return out, best, nearest
+
+
+def _mesh_error_device(p, v, t, lo, hi, max_dist=float("inf"), edge=None, sort_points=True):
+    """the search on validated device tensors -> (figures dict, best, nearest, candidates evaluated)"""
+    s = _MeshSearch(v, t, lo, hi)
+    cells, pairs = s.choose(edge)
+    s.emit()
+    s.prepare(p.shape[0])
+    out, best, nearest = s.query(p, s.order(p) if sort_points else None, max_dist)
+    mse, top, far, evaluated = out.tolist()
+    if np.isnan(far):
+        raise RuntimeError("pcgc_meshdist_*: the mesh or the cloud breaks the rule's contract (include/pcgc.h)")
+    n = int(p.shape[0])
+    figures = {"points": n, "far": int(far), "mse (p2mesh)": mse, "rms (p2mesh)": float(np.sqrt(mse)), "h. (p2mesh)": top,
+               "edge": int(cells[0]), "pairs": pairs}
+    return figures, best, nearest, int(evaluated)
+
+
+def mesh_error(points, vertices, triangles, max_dist=None, samples=0, seed=0, per_point=False, _edge=None, _sort_points=True):
+    """How far a cloud lies from a triangle mesh (csrc/meshdist.hip; include/pcgc.h, pcgc_meshdist_*; tests/_mesh_error_ref.py is
+    the rule in numpy): for every point the exact squared distance to the nearest triangle, faces, edges and corners alike, in
+    float64.  points [N,3] integer voxels or floats, vertices float64 [V,3], triangles int [T,3], numpy arrays or device
+    tensors, all in the same units (voxel units: surface.reconstruct's before a frame is applied), |coordinate| < 2^20.
+    max_dist: a point farther than it from the mesh is far and counts in no mean (None: no gate); it also bounds the walk of a
+    point that lies many cells from every triangle, which without a gate looks at every cell on its way.  -> a dict:
+      points, far                          how many points, and how many of them far
+      mse (p2mesh), rms (p2mesh)           the mean of the squared distance over the points that are not far, and its root
+      h. (p2mesh)                          the largest SQUARED distance among them (as pc_error's h. keys); NaN, like the means,
+                                           where every point is far
+      edge, pairs                          the edge of the search's cells and the (cell, triangle) pairs listed in them
+    The figures depend on the cloud and the triangle list alone, not on the cells.  per_point=True: -> (dict, (best float64
+    [N] = the squared distances, +inf for a far point; nearest int32 [N] = the smallest index of a triangle at that distance,
+    -1 for a far point)), in the caller's order.
+    samples > 0 adds the opposite direction: `samples` area-weighted points of the mesh (mesh2pc_open3d.sample_points_uniformly
+    with `seed`), rounded to float32, against the cloud by one direction of pc_error_float's search: mse (mesh2p), h. (mesh2p)
+    and h. (sym) = the larger of the two h.  That direction finds sheets the mesh invented where there are no points; a mesh
+    lying exactly on the surface still measures about half the point spacing there, since the samples fall between the points.
+    _edge, _sort_points: the tests' (a forced cell edge; the points taken as they come)."""
+    gate = check_max_dist(max_dist)
+    if isinstance(samples, bool) or int(samples) != samples or samples < 0:
+        raise ValueError("mesh_error: samples = %r must be a count" % (samples,))
+    p, v, t, lo, hi = _mesh_error_input(points, vertices, triangles)
+    figures, best, nearest, _ = _mesh_error_device(p, v, t, lo, hi, gate, _edge, _sort_points)
+    if samples:
+        figures.update(_mesh_to_cloud(p, v, t, int(samples), seed))
+        figures["h. (sym)"] = max(figures["h. (p2mesh)"], figures["h. (mesh2p)"])
+    if per_point:
+        return figures, (best.cpu().numpy(), nearest.cpu().numpy())
+    return figures
+
+
+def _mesh_to_cloud(p, v, t, samples, seed):
+    """samples of the mesh against the cloud: pieces that exist (the sampler, the off-grid target and its search)"""
+    from .dataprocess.mesh2pc_open3d import sample_points_uniformly
+    s = sample_points_uniformly(v.cpu().numpy(), t.cpu().numpy(), samples, seed, device=True).to(torch.float32).contiguous()
+    cloud = p.to(torch.float32).cpu().numpy()
+    target = _OffgridTarget(cloud, s.cpu().numpy(), p.device)
+    ws = torch.empty(int(_lib.hip().pcgc_offgrid_workspace_bytes(target.res, len(cloud))), dtype=torch.uint8, device=p.device)
+    mse, top, _, _ = _offgrid_mse(s, target, None, ws)
+    return {"mse (mesh2p)": mse, "h. (mesh2p)": top}
 
 
 def bpp(total_bytes, n_input_points):
