@@ -73,20 +73,12 @@ __global__ void __launch_bounds__(kScanThreads) clean_neighbors_kernel(const int
       if (dxy > r2 || (unsigned)qx >= (unsigned)res || (unsigned)qy >= (unsigned)res) continue;
       const int hz = isqrt_small(r2 - dxy);
       const int64_t row = cell_of(res, qx, qy, 0);
-      const int64_t b0 = row + max(z - hz, 0), b1 = row + min(z + hz, res - 1);   // the z-run, inside the row
-      for (int64_t w = b0 >> 5; w <= (b1 >> 5); ++w) {
-        const int64_t wbit = w << 5;
-        unsigned word = bits[w];
-        if (wbit < b0) word &= ~0u << (int)(b0 - wbit);          // with res < 32 the word holds other rows too
-        if (wbit + 31 > b1) word &= ~0u >> (int)(wbit + 31 - b1);
-        while (word) {
-          const int b = __ffs(word) - 1;
-          word &= word - 1;
-          const int dz = (int)(wbit + b - row) - z;
-          const int d2 = dxy + dz * dz;                          // <= r2: |dz| <= hz
-          if (d2) atomicAdd(&h[d2], 1u);                         // 0: the voxel itself
-        }
-      }
+      // the z-run, inside the row
+      for_each_in_run(bits, row + max(z - hz, 0), row + min(z + hz, res - 1), [&](int64_t w, unsigned, int b) {
+        const int dz = (int)((w << 5) + b - row) - z;
+        const int d2 = dxy + dz * dz;                            // <= r2: |dz| <= hz
+        if (d2) atomicAdd(&h[d2], 1u);                           // 0: the voxel itself
+      });
     }
   }
   __syncthreads();
@@ -115,6 +107,16 @@ __global__ void __launch_bounds__(kScanThreads) clean_neighbors_kernel(const int
 
 bool clean_size_ok(int bits, int64_t n) { return bits >= 1 && bits <= kCleanMaxBits && n >= 1 && n <= 0x7FFFFFFF; }
 
+struct CleanBuffers { unsigned* occupied; int64_t nblk; size_t bytes; };     // the occupancy bit set alone, its scan blocks
+
+CleanBuffers clean_layout(int bits, void* workspace) {
+  const int res = 1 << bits;
+  const int64_t nblk = scan_blocks((int64_t)res * res * res);
+  Carver c(workspace);
+  unsigned* occupied = c.take<unsigned>(padded_bits_words(nblk));
+  return {occupied, nblk, c.bytes()};
+}
+
 }  // namespace
 }  // namespace pcgc
 
@@ -122,11 +124,7 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_clean_workspace_bytes(int bits, int64_t n) {
-  if (!clean_size_ok(bits, n)) return 0;
-  const int res = 1 << bits;
-  return align256(padded_bits_bytes(scan_blocks((int64_t)res * res * res)));
-}
+size_t pcgc_clean_workspace_bytes(int bits, int64_t n) { return clean_size_ok(bits, n) ? clean_layout(bits, nullptr).bytes : 0; }
 
 int pcgc_clean_neighbors(const int32_t* points, int64_t n, int bits, int k, int radius, int64_t* S, int32_t* cnt, void* workspace,
                          size_t workspace_bytes, pcgc_stream_t stream) {
@@ -135,18 +133,18 @@ int pcgc_clean_neighbors(const int32_t* points, int64_t n, int bits, int k, int 
   PCGC_REQUIRE(radius >= 1 && radius <= kCleanMaxR, "pcgc_clean_neighbors: radius = %d outside 1..%d", radius, kCleanMaxR);
   PCGC_REQUIRE(S || cnt, "pcgc_clean_neighbors: neither S nor cnt is asked for");
   PCGC_REQUIRE(k > 0 || !S, "pcgc_clean_neighbors: S with k = 0");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_clean_workspace_bytes(bits, n), "pcgc_clean_neighbors: workspace too small");
+  const CleanBuffers b = clean_layout(bits, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_clean_neighbors: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int res = 1 << bits;
-  unsigned* occupied = static_cast<unsigned*>(workspace);
-  PCGC_CHECK_HIP(hipMemsetAsync(occupied, 0, padded_bits_bytes(scan_blocks((int64_t)res * res * res)), s));
-  hipLaunchKernelGGL(bits_from_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, res, occupied);
+  PCGC_CHECK_HIP(hipMemsetAsync(b.occupied, 0, padded_bits_bytes(b.nblk), s));
+  hipLaunchKernelGGL(bits_from_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, res, b.occupied);
   // column c of the (2R+1)^2 square is (c / side, c % side), the quotient as (c * magic) >> 20 with magic = ceil(2^20 / side):
   // magic = 2^20 / side + e with 0 <= e < 1, so the product exceeds the exact c * 2^20 / side by c * e < side^2 <= 4225; the
   // exact value lies at least 2^20 / side >= 16131 below the next multiple of 2^20, so the shift gives c / side.  c * magic < 2^27
   const unsigned side = 2 * (unsigned)radius + 1, magic = ((1u << kColumnShift) + side - 1) / side;
   hipLaunchKernelGGL(clean_neighbors_kernel, dim3((unsigned)((n + kCleanWaves - 1) / kCleanWaves)), dim3(kScanThreads), 0, s, points, n,
-                     res, occupied, k, radius, magic, S, cnt);
+                     res, b.occupied, k, radius, magic, S, cnt);
   return launch_ok("clean neighbour kernels");
 }
 

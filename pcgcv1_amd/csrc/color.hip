@@ -147,6 +147,32 @@ bool sizes_ok(int res, int64_t a, int64_t b) {
   return res > 0 && res <= 4096 && a > 0 && b > 0 && a <= 0x7FFFFFFF && b <= 0x7FFFFFFF;
 }
 
+// the rank structure of one cloud, then pcgc_recolor's accumulators per target [n_t, 4] and source colours by rank [n_s]
+struct RecolorBuffers { RankBuffers r; unsigned *acc, *scolors; size_t bytes; };
+
+RecolorBuffers recolor_layout(int res, int64_t n_s, int64_t n_t, void* workspace) {
+  RecolorBuffers b;
+  b.r = rank_layout(res, workspace);
+  Carver& c = b.r.rest;
+  b.acc = c.take<unsigned>((size_t)n_t * 4);
+  b.scolors = c.take<unsigned>((size_t)n_s);
+  b.bytes = c.bytes();
+  return b;
+}
+
+// ... then pcgc_color_mse's colours of B by rank [n_b] and the partial sums [3, kSumBlocks]
+struct ColorMseBuffers { RankBuffers r; unsigned* bcolors; double* partial; size_t bytes; };
+
+ColorMseBuffers color_mse_layout(int res, int64_t n_b, void* workspace) {
+  ColorMseBuffers b;
+  b.r = rank_layout(res, workspace);
+  Carver& c = b.r.rest;
+  b.bcolors = c.take<unsigned>((size_t)n_b);
+  b.partial = c.take<double>(3 * kSumBlocks);
+  b.bytes = c.bytes();
+  return b;
+}
+
 }  // namespace
 }  // namespace pcgc
 
@@ -155,8 +181,7 @@ using namespace pcgc;
 extern "C" {
 
 size_t pcgc_recolor_workspace_bytes(int res, int64_t n_s, int64_t n_t) {
-  if (!sizes_ok(res, n_s, n_t) || n_s > kMaxSource) return 0;
-  return rank_bytes(res) + align256((size_t)n_t * 4 * sizeof(unsigned)) + align256((size_t)n_s * sizeof(unsigned));
+  return sizes_ok(res, n_s, n_t) && n_s <= kMaxSource ? recolor_layout(res, n_s, n_t, nullptr).bytes : 0;
 }
 
 int pcgc_recolor(const int32_t* source_points, const uint8_t* source_colors, int64_t n_s, const int64_t* target_keys, int64_t n_t,
@@ -165,50 +190,47 @@ int pcgc_recolor(const int32_t* source_points, const uint8_t* source_colors, int
   PCGC_REQUIRE(source_points && source_colors && target_keys && target_colors && workspace && sizes_ok(res, n_s, n_t),
                "pcgc_recolor: bad arguments");
   PCGC_REQUIRE(n_s <= kMaxSource, "pcgc_recolor: %lld source points, the 32-bit colour sums hold %lld", (long long)n_s, (long long)kMaxSource);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_recolor_workspace_bytes(res, n_s, n_t), "pcgc_recolor: workspace too small");
+  const RecolorBuffers b = recolor_layout(res, n_s, n_t, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_recolor: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const RankBuffers r = rank_layout(res, workspace);
-  unsigned* acc = reinterpret_cast<unsigned*>(r.rest);
-  unsigned* scolors = reinterpret_cast<unsigned*>(r.rest + align256((size_t)n_t * 4 * sizeof(unsigned)));
+  const RankBuffers& r = b.r;
   const Grid g{r.bits, r.rank, r.n_set, res};
   // the target's rank structure, then S -> T
   int rc = build_rank(r, res, nullptr, target_keys, n_t, s);
   if (rc) return rc;
-  PCGC_CHECK_HIP(hipMemsetAsync(acc, 0, (size_t)n_t * 4 * sizeof(unsigned), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.acc, 0, (size_t)n_t * 4 * sizeof(unsigned), s));
   const int blocks = (int)std::min<int64_t>((n_s + 255) / 256, 4096);
-  hipLaunchKernelGGL(recolor_scatter_kernel, dim3(blocks), dim3(256), 0, s, source_points, source_colors, n_s, g, acc);
+  hipLaunchKernelGGL(recolor_scatter_kernel, dim3(blocks), dim3(256), 0, s, source_points, source_colors, n_s, g, b.acc);
   // the same memory becomes the source's rank structure for the targets that nothing reached
   rc = build_rank(r, res, source_points, nullptr, n_s, s);
   if (rc) return rc;
   hipLaunchKernelGGL(colors_to_rank_order_kernel, dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, s, source_points, source_colors,
-                     n_s, g, scolors);
+                     n_s, g, b.scolors);
   hipLaunchKernelGGL(recolor_final_kernel, dim3((unsigned)((n_t + 255) / 256)), dim3(256), 0, s, target_keys, n_t,
-                     reinterpret_cast<const uint4*>(acc), g, scolors, target_colors, backward_counts);
+                     reinterpret_cast<const uint4*>(b.acc), g, b.scolors, target_colors, backward_counts);
   return launch_ok("recolor kernels");
 }
 
 size_t pcgc_color_mse_workspace_bytes(int res, int64_t n_b) {
-  if (!sizes_ok(res, 1, n_b)) return 0;
-  return rank_bytes(res) + align256((size_t)n_b * sizeof(unsigned)) + align256(3 * kSumBlocks * sizeof(double));
+  return sizes_ok(res, 1, n_b) ? color_mse_layout(res, n_b, nullptr).bytes : 0;
 }
 
 int pcgc_color_mse(const int32_t* points_a, const uint8_t* colors_a, int64_t n_a, const int32_t* points_b, const uint8_t* colors_b,
                    int64_t n_b, int res, double* out3, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
   PCGC_REQUIRE(points_a && colors_a && points_b && colors_b && out3 && workspace && sizes_ok(res, n_a, n_b),
                "pcgc_color_mse: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_color_mse_workspace_bytes(res, n_b), "pcgc_color_mse: workspace too small");
+  const ColorMseBuffers b = color_mse_layout(res, n_b, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_color_mse: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const RankBuffers r = rank_layout(res, workspace);
-  unsigned* bcolors = reinterpret_cast<unsigned*>(r.rest);
-  double* partial = reinterpret_cast<double*>(r.rest + align256((size_t)n_b * sizeof(unsigned)));
+  const RankBuffers& r = b.r;
   const Grid g{r.bits, r.rank, r.n_set, res};
   int rc = build_rank(r, res, points_b, nullptr, n_b, s);
   if (rc) return rc;
   hipLaunchKernelGGL(colors_to_rank_order_kernel, dim3((unsigned)((n_b + 255) / 256)), dim3(256), 0, s, points_b, colors_b, n_b, g,
-                     bcolors);
+                     b.bcolors);
   const int blocks = (int)std::min<int64_t>((n_a + 255) / 256, kSumBlocks);
-  hipLaunchKernelGGL(color_mse_partial_kernel, dim3(blocks), dim3(256), 0, s, points_a, colors_a, n_a, g, bcolors, partial);
-  hipLaunchKernelGGL(color_mse_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, n_a, out3);
+  hipLaunchKernelGGL(color_mse_partial_kernel, dim3(blocks), dim3(256), 0, s, points_a, colors_a, n_a, g, b.bcolors, b.partial);
+  hipLaunchKernelGGL(color_mse_final_kernel, dim3(1), dim3(64), 0, s, b.partial, blocks, n_a, out3);
   return launch_ok("colour mse kernels");
 }
 

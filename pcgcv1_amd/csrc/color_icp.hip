@@ -106,7 +106,7 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_color_gradient_workspace_bytes(int res, int64_t n) { return cloud_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
+size_t pcgc_color_gradient_workspace_bytes(int res, int64_t n) { return cloud_sizes_ok(res, n) ? cell_buffer_layout(res, n, nullptr).bytes : 0; }
 
 int pcgc_color_gradient(const float* points, const float* normals, const int32_t* Y, int64_t n, double h, int ox, int oy, int oz, int res,
                         double radius, int kmin, double* g, uint8_t* valid, int32_t* K, int64_t* Q, int64_t* B, void* workspace,
@@ -118,9 +118,9 @@ int pcgc_color_gradient(const float* points, const float* normals, const int32_t
   PCGC_REQUIRE(std::isfinite(radius) && radius > 0.0 && radius <= kGradMaxRadius && radius <= h,
                "pcgc_color_gradient: radius %g must be positive, at most %g and at most the cell edge %g", radius, kGradMaxRadius, h);
   PCGC_REQUIRE(kmin >= 3 && kmin <= kGradMaxK, "pcgc_color_gradient: kmin %d outside 3..%d", kmin, kGradMaxK);
-  PCGC_REQUIRE(workspace_bytes >= cell_buffer_bytes(res, n), "pcgc_color_gradient: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
   const CellBuffers b = cell_buffer_layout(res, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_color_gradient: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   Target t;
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, points, n, s, &t);
   if (rc) return rc;

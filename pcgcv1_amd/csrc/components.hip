@@ -94,19 +94,9 @@ __global__ void __launch_bounds__(kHookThreads) components_hook_kernel(const int
     const int z0 = max(z - G, 0), z1 = c == own ? z - 1 : min(z + G, res - 1);        // the z-run, inside the row
     if (z1 < z0) continue;
     const int64_t row = cell_of(res, qx, qy, 0);
-    const int64_t b0 = row + z0, b1 = row + z1;
-    for (int64_t w = b0 >> 5; w <= (b1 >> 5); ++w) {
-      const int64_t wbit = w << 5;
-      const unsigned all = bits[w];
-      unsigned word = all;
-      if (wbit < b0) word &= ~0u << (int)(b0 - wbit);             // with res < 32 the word holds other rows too
-      if (wbit + 31 > b1) word &= ~0u >> (int)(wbit + 31 - b1);
-      while (word) {
-        const int b = __ffs(word) - 1;
-        word &= word - 1;
-        root = unite(parent, root, rank[w] + __popc(all & ((1u << b) - 1u)));          // rank_of the cell wbit + b
-      }
-    }
+    for_each_in_run(bits, row + z0, row + z1, [&](int64_t w, unsigned all, int b) {
+      root = unite(parent, root, rank[w] + __popc(all & ((1u << b) - 1u)));            // rank_of the cell w * 32 + b
+    });
   }
 }
 
@@ -179,28 +169,25 @@ __global__ void __launch_bounds__(256) components_gather_kernel(const int32_t* p
 
 bool components_size_ok(int bits, int64_t n) { return bits >= 1 && bits <= kCompMaxBits && n >= 1 && n <= 0x7FFFFFFF; }
 
-// after the rank structure: key [n] int64, parent [n], count [n], the number of roots
-struct ComponentBuffers {
-  int64_t* key;
-  unsigned *parent, *count, *n_roots;
-};
+// the rank structure, then key [n] int64, parent [n], count [n], the number of roots
+struct ComponentBuffers { RankBuffers r; int64_t* key; unsigned *parent, *count, *n_roots; size_t bytes; };
 
-ComponentBuffers components_layout(char* rest, int64_t n) {
+ComponentBuffers components_layout(int bits, int64_t n, void* workspace) {
   ComponentBuffers c;
-  c.key = reinterpret_cast<int64_t*>(rest);
-  rest += align256((size_t)n * sizeof(int64_t));
-  c.parent = reinterpret_cast<unsigned*>(rest);
-  rest += align256((size_t)n * sizeof(unsigned));
-  c.count = reinterpret_cast<unsigned*>(rest);
-  rest += align256((size_t)n * sizeof(unsigned));
-  c.n_roots = reinterpret_cast<unsigned*>(rest);
+  c.r = rank_layout(1 << bits, workspace);
+  Carver& rest = c.r.rest;
+  c.key = rest.take<int64_t>((size_t)n);
+  c.parent = rest.take<unsigned>((size_t)n);
+  c.count = rest.take<unsigned>((size_t)n);
+  c.n_roots = rest.take<unsigned>(1);
+  c.bytes = rest.bytes();
   return c;
 }
 
 template <int L>
-void launch_hook(int64_t n, const ComponentBuffers& c, const RankBuffers& r, int bits, int gap, hipStream_t s) {
+void launch_hook(int64_t n, const ComponentBuffers& c, int bits, int gap, hipStream_t s) {
   hipLaunchKernelGGL(components_hook_kernel<L>, dim3((unsigned)((n * L + kHookThreads - 1) / kHookThreads)), dim3(kHookThreads), 0, s, c.key,
-                     r.n_set, bits, gap, r.bits, r.rank, c.parent);
+                     c.r.n_set, bits, gap, c.r.bits, c.r.rank, c.parent);
 }
 
 }  // namespace
@@ -211,19 +198,18 @@ using namespace pcgc;
 extern "C" {
 
 size_t pcgc_clean_components_workspace_bytes(int bits, int64_t n) {
-  if (!components_size_ok(bits, n)) return 0;
-  return rank_bytes(1 << bits) + align256((size_t)n * sizeof(int64_t)) + 2 * align256((size_t)n * sizeof(unsigned)) + 256;
+  return components_size_ok(bits, n) ? components_layout(bits, n, nullptr).bytes : 0;
 }
 
 int pcgc_clean_components(const int32_t* points, int64_t n, int bits, int gap, int64_t* label, int32_t* size, int64_t* n_components,
                           void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
   PCGC_REQUIRE(points && label && workspace && components_size_ok(bits, n), "pcgc_clean_components: bad arguments");
   PCGC_REQUIRE(gap >= 1 && gap <= kCompMaxGap, "pcgc_clean_components: gap = %d outside 1..%d", gap, kCompMaxGap);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_clean_components_workspace_bytes(bits, n), "pcgc_clean_components: workspace too small");
+  const ComponentBuffers c = components_layout(bits, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= c.bytes, "pcgc_clean_components: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int res = 1 << bits;
-  const RankBuffers r = rank_layout(res, workspace);
-  const ComponentBuffers c = components_layout(r.rest, n);
+  const RankBuffers& r = c.r;
   const int64_t nblk = scan_blocks((int64_t)res * res * res);
   if (int rc = build_rank(r, res, points, nullptr, n, s)) return rc;
   hipLaunchKernelGGL(components_list_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, r.bits, r.block_count, c.key, c.parent, c.count,
@@ -232,8 +218,8 @@ int pcgc_clean_components(const int32_t* points, int64_t n, int bits, int gap, i
   // reached from one neighbour to the next, so few lanes beat many; one lane up to the 25 columns of G = 3, two from the 41
   // of G = 4 to the 145 of G = 8.  The grids are sized for n, an upper bound of the set bits, which the kernels read on the
   // device.
-  if (gap <= 3) launch_hook<1>(n, c, r, bits, gap, s);
-  else launch_hook<2>(n, c, r, bits, gap, s);
+  if (gap <= 3) launch_hook<1>(n, c, bits, gap, s);
+  else launch_hook<2>(n, c, bits, gap, s);
   hipLaunchKernelGGL(components_flatten_kernel, dim3((unsigned)((n + kFlattenThreads - 1) / kFlattenThreads)), dim3(kFlattenThreads), 0, s,
                      r.n_set, c.parent, c.count, c.n_roots);
   hipLaunchKernelGGL(components_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, res, r.bits, r.rank, c.parent,

@@ -272,7 +272,7 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_feature_workspace_bytes(int res, int64_t n) { return feature_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
+size_t pcgc_feature_workspace_bytes(int res, int64_t n) { return feature_sizes_ok(res, n) ? cell_buffer_layout(res, n, nullptr).bytes : 0; }
 
 int pcgc_feature_pairs(const float* kp, const float* normals, int64_t n, double h, int ox, int oy, int oz, int res, double radius,
                        uint32_t* S, int32_t* k, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
@@ -281,9 +281,9 @@ int pcgc_feature_pairs(const float* kp, const float* normals, int64_t n, double 
                "pcgc_feature_pairs: bad arguments");
   PCGC_REQUIRE(window_ok(radius, h, &w), "pcgc_feature_pairs: radius %g must be positive and below %d cells of edge %g", radius,
                kFeatureMaxWindow, h);
-  PCGC_REQUIRE(workspace_bytes >= cell_buffer_bytes(res, n), "pcgc_feature_pairs: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
   const CellBuffers b = cell_buffer_layout(res, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_feature_pairs: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   Target t;
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, kp, n, s, &t);
   if (rc) return rc;
@@ -300,9 +300,9 @@ int pcgc_feature_combine(const float* kp, const float* normals, int64_t n, doubl
                "pcgc_feature_combine: bad arguments");
   PCGC_REQUIRE(window_ok(radius, h, &w), "pcgc_feature_combine: radius %g must be positive and below %d cells of edge %g", radius,
                kFeatureMaxWindow, h);
-  PCGC_REQUIRE(workspace_bytes >= cell_buffer_bytes(res, n), "pcgc_feature_combine: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
   const CellBuffers b = cell_buffer_layout(res, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_feature_combine: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   Target t;
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, kp, n, s, &t);
   if (rc) return rc;

@@ -197,8 +197,18 @@ __global__ void __launch_bounds__(kScanThreads) ingest_rows_kernel(const unsigne
 // ---------------------------------------------------------------------------------------------------------------- host side
 bool ingest_size_ok(int bits, int64_t n) { return bits >= 1 && bits <= kIngestMaxBits && n >= 1 && n <= 0x7FFFFFFF; }
 
-size_t sums_bytes(int64_t n) {
-  return align256((size_t)n * sizeof(int32_t)) + align256((size_t)n * 3 * sizeof(uint32_t)) + align256((size_t)n * 3 * sizeof(long long));
+// the rank structure of the grid, then the per-voxel accumulators
+struct IngestBuffers { RankBuffers r; Sums sums; size_t bytes; };
+
+IngestBuffers ingest_layout(int bits, int64_t n, void* workspace) {
+  IngestBuffers b;
+  b.r = rank_layout(1 << bits, workspace);
+  Carver& c = b.r.rest;
+  b.sums.count = c.take<int32_t>((size_t)n);
+  b.sums.color = c.take<uint32_t>((size_t)n * 3);
+  b.sums.normal = c.take<long long>((size_t)n * 3);
+  b.bytes = c.bytes();
+  return b;
 }
 
 }  // namespace
@@ -229,10 +239,7 @@ int pcgc_ingest_quantize(const double* points, int64_t n, const double* origin, 
   return launch_ok("ingest_quantize_kernel");
 }
 
-size_t pcgc_ingest_workspace_bytes(int bits, int64_t n) {
-  if (!ingest_size_ok(bits, n)) return 0;
-  return rank_bytes(1 << bits) + sums_bytes(n);
-}
+size_t pcgc_ingest_workspace_bytes(int bits, int64_t n) { return ingest_size_ok(bits, n) ? ingest_layout(bits, n, nullptr).bytes : 0; }
 
 int pcgc_ingest_merge(const int64_t* keys, int64_t n, int bits, const uint8_t* colors, const float* normals, int32_t* out_points,
                       int32_t* out_counts, uint8_t* out_colors, float* out_normals, int64_t cap, int64_t* n_out, void* workspace,
@@ -245,16 +252,11 @@ int pcgc_ingest_merge(const int64_t* keys, int64_t n, int bits, const uint8_t* c
                (long long)std::min(n, cells));
   PCGC_REQUIRE(!colors || n <= kMaxColoredRows, "pcgc_ingest_merge: %lld rows with colours; the uint32 colour sums hold %lld",
                (long long)n, (long long)kMaxColoredRows);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_ingest_workspace_bytes(bits, n), "pcgc_ingest_merge: workspace too small");
+  const IngestBuffers b = ingest_layout(bits, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_ingest_merge: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const RankBuffers r = rank_layout(res, workspace);
-  Sums sums;
-  char* w = r.rest;
-  sums.count = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)n * sizeof(int32_t));
-  sums.color = reinterpret_cast<uint32_t*>(w);
-  w += align256((size_t)n * 3 * sizeof(uint32_t));
-  sums.normal = reinterpret_cast<long long*>(w);
+  const RankBuffers& r = b.r;
+  const Sums& sums = b.sums;
   const int rc = build_rank(r, res, nullptr, keys, n, s);       // set bits (keys checked against the grid), scan, rank table
   if (rc) return rc;
   PCGC_CHECK_HIP(hipMemsetAsync(sums.count, 0, (size_t)n * sizeof(int32_t), s));

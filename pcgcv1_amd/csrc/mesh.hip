@@ -271,6 +271,45 @@ const std::vector<int32_t>& offset_table(int r2) {
 
 int radius2(double radius) { return (int)std::floor(radius * radius); }
 
+// pcgc_mesh_voxelize: the bit set of the (resolution + 1)^3 grid, its scan, the min / max partials and the pair they reduce to
+struct VoxelizeBuffers { unsigned* bits; int64_t* block_count; double *partial, *mm; int64_t G, nblk; size_t bytes; };
+
+VoxelizeBuffers voxelize_layout(int resolution, void* workspace) {
+  Carver c(workspace);
+  VoxelizeBuffers b;
+  b.G = resolution + 1;
+  b.nblk = scan_blocks(b.G * b.G * b.G);
+  b.bits = c.take<unsigned>(padded_bits_words(b.nblk));
+  b.block_count = c.take<int64_t>((size_t)b.nblk);
+  b.partial = c.take<double>(2 * kMinMaxBlocks);
+  b.mm = c.take<double>(2);
+  b.bytes = c.bytes();
+  return b;
+}
+
+// pcgc_estimate_normals: bit set and scan of the res^3 grid, the number of cells, per cell its key, normal, covariance and
+// neighbour count, then the offset table of n_table entries
+struct NormalsBuffers {
+  unsigned* bits; int64_t *block_count, *n_cells, *ukeys; float* unormals; int64_t* ucov; int32_t *uk, *dtable;
+  int64_t nblk; size_t bytes;
+};
+
+NormalsBuffers normals_layout(int res, int64_t n, size_t n_table, void* workspace) {
+  Carver c(workspace);
+  NormalsBuffers b;
+  b.nblk = scan_blocks((int64_t)res * res * res);
+  b.bits = c.take<unsigned>(padded_bits_words(b.nblk));
+  b.block_count = c.take<int64_t>((size_t)b.nblk);
+  b.n_cells = c.take<int64_t>(1);
+  b.ukeys = c.take<int64_t>((size_t)n);
+  b.unormals = c.take<float>((size_t)n * 3);
+  b.ucov = c.take<int64_t>((size_t)n * 6);
+  b.uk = c.take<int32_t>((size_t)n);
+  b.dtable = c.take<int32_t>(n_table);
+  b.bytes = c.bytes();
+  return b;
+}
+
 }  // namespace
 }  // namespace pcgc
 
@@ -290,10 +329,7 @@ int pcgc_mesh_sample(const double* vertices, int64_t n_vertices, const int32_t* 
 }
 
 size_t pcgc_mesh_voxelize_workspace_bytes(int resolution) {
-  if (resolution < 1 || resolution > 4095) return 0;
-  const int64_t G = resolution + 1, nblk = scan_blocks(G * G * G);
-  return align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) +
-         align256(2 * kMinMaxBlocks * sizeof(double)) + 256;
+  return resolution >= 1 && resolution <= 4095 ? voxelize_layout(resolution, nullptr).bytes : 0;
 }
 
 int pcgc_mesh_voxelize(const double* points, int64_t n, int resolution, int32_t* out, int64_t cap, int64_t* n_out,
@@ -301,26 +337,18 @@ int pcgc_mesh_voxelize(const double* points, int64_t n, int resolution, int32_t*
   PCGC_REQUIRE(points && out && n_out && n > 0 && resolution >= 1 && resolution <= 4095 && workspace,
                "pcgc_mesh_voxelize: bad arguments");
   PCGC_REQUIRE(cap >= n, "pcgc_mesh_voxelize: capacity %lld below the %lld input points", (long long)cap, (long long)n);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_mesh_voxelize_workspace_bytes(resolution), "pcgc_mesh_voxelize: workspace too small");
+  const VoxelizeBuffers b = voxelize_layout(resolution, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_mesh_voxelize: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t G = resolution + 1, nblk = scan_blocks(G * G * G);
-  char* w = static_cast<char*>(workspace);
-  unsigned* bits = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(nblk));
-  int64_t* block_count = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)nblk * sizeof(int64_t));
-  double* partial = reinterpret_cast<double*>(w);
-  w += align256(2 * kMinMaxBlocks * sizeof(double));
-  double* mm = reinterpret_cast<double*>(w);
-  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, padded_bits_bytes(nblk), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.bits, 0, padded_bits_bytes(b.nblk), s));
   const int64_t m = 3 * n;
   const int nb = (int)std::min<int64_t>(kMinMaxBlocks, (m + 255) / 256);
-  hipLaunchKernelGGL(mesh_minmax_partial_kernel, dim3(nb), dim3(256), 0, s, points, m, partial);
-  hipLaunchKernelGGL(mesh_minmax_final_kernel, dim3(1), dim3(64), 0, s, partial, nb, mm);
-  hipLaunchKernelGGL(mesh_quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, mm, resolution, bits);
-  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
-  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_out);
-  hipLaunchKernelGGL(bits_compact_kernel<true>, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count, G, cap, out,
+  hipLaunchKernelGGL(mesh_minmax_partial_kernel, dim3(nb), dim3(256), 0, s, points, m, b.partial);
+  hipLaunchKernelGGL(mesh_minmax_final_kernel, dim3(1), dim3(64), 0, s, b.partial, nb, b.mm);
+  hipLaunchKernelGGL(mesh_quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points, n, b.mm, resolution, b.bits);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)b.nblk), dim3(kScanThreads), 0, s, b.bits, b.block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.block_count, b.nblk, n_out);
+  hipLaunchKernelGGL(bits_compact_kernel<true>, dim3((unsigned)b.nblk), dim3(kScanThreads), 0, s, b.bits, b.block_count, b.G, cap, out,
                      (int64_t*)nullptr);
   return launch_ok("mesh voxelize kernels");
 }
@@ -332,11 +360,7 @@ int pcgc_normals_table_size(double radius) {
 
 size_t pcgc_normals_workspace_bytes(int res, int64_t n, double radius) {
   if (res < 1 || res > 4096 || n < 0 || !(radius >= 0.0 && radius <= 16.0)) return 0;
-  const int64_t nblk = scan_blocks((int64_t)res * res * res);
-  const size_t nt = offset_table(radius2(radius)).size();
-  return align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) + 256 +
-         align256((size_t)n * sizeof(int64_t)) + align256((size_t)n * 3 * sizeof(float)) +
-         align256((size_t)n * 6 * sizeof(int64_t)) + align256((size_t)n * sizeof(int32_t)) + align256(nt * sizeof(int32_t));
+  return normals_layout(res, n, offset_table(radius2(radius)).size(), nullptr).bytes;
 }
 
 int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radius, int max_nn, float* normals, int64_t* cov,
@@ -344,38 +368,22 @@ int pcgc_estimate_normals(const int32_t* points, int64_t n, int res, double radi
   PCGC_REQUIRE(points && normals && n > 0 && res >= 1 && res <= 4096 && radius >= 0.0 && radius <= 16.0 && max_nn >= 1 &&
                max_nn <= 64 && workspace && (cov == nullptr) == (n_neighbours == nullptr),
                "pcgc_estimate_normals: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_normals_workspace_bytes(res, n, radius), "pcgc_estimate_normals: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
   const std::vector<int32_t>& table = offset_table(radius2(radius));
-  const int64_t nblk = scan_blocks((int64_t)res * res * res);
-  char* w = static_cast<char*>(workspace);
-  unsigned* bits = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(nblk));
-  int64_t* block_count = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)nblk * sizeof(int64_t));
-  int64_t* n_cells = reinterpret_cast<int64_t*>(w);
-  w += 256;
-  int64_t* ukeys = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)n * sizeof(int64_t));
-  float* unormals = reinterpret_cast<float*>(w);
-  w += align256((size_t)n * 3 * sizeof(float));
-  int64_t* ucov = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)n * 6 * sizeof(int64_t));
-  int32_t* uk = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)n * sizeof(int32_t));
-  int32_t* dtable = reinterpret_cast<int32_t*>(w);
-  PCGC_CHECK_HIP(hipMemcpyAsync(dtable, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  PCGC_CHECK_HIP(hipMemsetAsync(bits, 0, padded_bits_bytes(nblk), s));
+  const NormalsBuffers b = normals_layout(res, n, table.size(), workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_estimate_normals: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  PCGC_CHECK_HIP(hipMemcpyAsync(b.dtable, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.bits, 0, padded_bits_bytes(b.nblk), s));
   const unsigned grid = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, bits);
-  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count);
-  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, block_count, nblk, n_cells);
-  hipLaunchKernelGGL(bits_compact_kernel<false>, dim3((unsigned)nblk), dim3(kScanThreads), 0, s, bits, block_count, (int64_t)res, n,
-                     (int32_t*)nullptr, ukeys);
-  hipLaunchKernelGGL(normals_kernel, dim3(grid), dim3(256), 0, s, bits, ukeys, n_cells, res, dtable, (int)table.size(), max_nn,
-                     unormals, cov ? ucov : nullptr, uk);
-  hipLaunchKernelGGL(normals_gather_kernel, dim3(grid), dim3(256), 0, s, points, n, res, ukeys, n_cells, unormals, ucov, uk, normals,
-                     cov, n_neighbours);
+  hipLaunchKernelGGL(bits_from_points_kernel, dim3(grid), dim3(256), 0, s, points, n, res, b.bits);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)b.nblk), dim3(kScanThreads), 0, s, b.bits, b.block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.block_count, b.nblk, b.n_cells);
+  hipLaunchKernelGGL(bits_compact_kernel<false>, dim3((unsigned)b.nblk), dim3(kScanThreads), 0, s, b.bits, b.block_count, (int64_t)res, n,
+                     (int32_t*)nullptr, b.ukeys);
+  hipLaunchKernelGGL(normals_kernel, dim3(grid), dim3(256), 0, s, b.bits, b.ukeys, b.n_cells, res, b.dtable, (int)table.size(), max_nn,
+                     b.unormals, cov ? b.ucov : nullptr, b.uk);
+  hipLaunchKernelGGL(normals_gather_kernel, dim3(grid), dim3(256), 0, s, points, n, res, b.ukeys, b.n_cells, b.unormals, b.ucov, b.uk,
+                     normals, cov, n_neighbours);
   return launch_ok("normal estimation kernels");
 }
 

@@ -276,24 +276,18 @@ struct MeshBuffers {
   int32_t* evaluated;        // [n_points]
   double* partial;           // [2, kMeshBlocks]
   long long* counts;         // [2, kMeshBlocks]
+  size_t bytes;
 };
-
-size_t mesh_bytes(int res, int64_t n_pairs, int64_t n_points) {
-  return cell_buffer_bytes(res, n_pairs) + align256((size_t)n_pairs * sizeof(int32_t)) + align256((size_t)n_points * sizeof(int32_t)) +
-         align256(2 * kMeshBlocks * sizeof(double)) + align256(2 * kMeshBlocks * sizeof(long long));
-}
 
 MeshBuffers mesh_layout(int res, int64_t n_pairs, int64_t n_points, void* workspace) {
   MeshBuffers b;
   b.cells = cell_buffer_layout(res, n_pairs, workspace);
-  char* w = static_cast<char*>(workspace) + cell_buffer_bytes(res, n_pairs);
-  b.tris = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)n_pairs * sizeof(int32_t));
-  b.evaluated = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)n_points * sizeof(int32_t));
-  b.partial = reinterpret_cast<double*>(w);
-  w += align256(2 * kMeshBlocks * sizeof(double));
-  b.counts = reinterpret_cast<long long*>(w);
+  Carver& c = b.cells.rest;
+  b.tris = c.take<int32_t>((size_t)n_pairs);
+  b.evaluated = c.take<int32_t>((size_t)n_points);
+  b.partial = c.take<double>(2 * kMeshBlocks);
+  b.counts = c.take<long long>(2 * kMeshBlocks);
+  b.bytes = c.bytes();
   return b;
 }
 
@@ -325,7 +319,7 @@ int pcgc_meshdist_emit(const double* vertices, int64_t n_vertices, const int32_t
 
 size_t pcgc_meshdist_workspace_bytes(int res, int64_t n_pairs, int64_t n_points) {
   if (res < 1 || res > kOffgridMaxRes || n_pairs < 1 || n_pairs >= 0x7FFFFFFF || n_points < 1 || n_points > 0x7FFFFFFF) return 0;
-  return mesh_bytes(res, n_pairs, n_points);
+  return mesh_layout(res, n_pairs, n_points, nullptr).bytes;
 }
 
 int pcgc_meshdist_prepare(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const int64_t* words,

@@ -6,6 +6,7 @@
 #include <cstddef>
 
 #include "../../include/pcgc.h"
+#include "workspace.h"            // Arena: the workspace plan and the weight blob
 
 namespace pcgc {
 
@@ -23,12 +24,6 @@ static_assert(l64::down_1 == l64::BC(2) + 1 && l64::down_1 + 1 == kSkipLaunches 
               l32::BC(2) + 1 == kSkipLaunchesMid, "the launch numbers fill the tables");
 // per cube and launch: tile-order entries at 64^3 / 32^3, virtual-row words, slots, bytes of the slots' "not written" table
 constexpr size_t kTiles64 = 512, kTiles32 = 256, kVirtWords = 64, kSlots = 1024, kSegVirtBytes = 256;
-
-// Bump allocator over byte offsets from a 256-byte aligned base: the workspace plan and the weight blob
-struct Arena {
-  size_t end = 0;
-  size_t take(size_t bytes, size_t align) { const size_t at = (end + align - 1) / align * align; end = at + bytes; return at; }
-};
 
 // The analysis' responses to an EMPTY cube, in floats from the start of the net's blob of them: an all-zero input cube, the
 // 64^3 set e_in | e_t[3] | e_o[3] (conv_in's output, tensor1_1 | tensor2_1 and the output of each C = 16 block, Q4), the

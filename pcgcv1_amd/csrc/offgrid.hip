@@ -309,41 +309,30 @@ struct OffgridBuffers {
   long long* sums;           // [nq,3]
   int* counts;               // [nq]
   double* partial;           // [4, kOffgridBlocks]
-  int* bad;
+  int* bad;                  // [2] the target's flag (build_target), a register step's
+  double* step_partial;      // [n_sums, kOffgridBlocks]
+  size_t bytes;
 };
 
-size_t offgrid_bytes(int res, int64_t nq) {
-  return rank_bytes(res) + align256((size_t)nq * sizeof(int64_t)) + align256((size_t)(nq + 1) * sizeof(int32_t)) +
-         align256((size_t)nq * 3 * sizeof(long long)) + align256((size_t)nq * sizeof(int)) +
-         align256(4 * kOffgridBlocks * sizeof(double)) + 256;
-}
-
-OffgridBuffers offgrid_layout(int res, int64_t nq, void* workspace) {
+// n_sums = 0: the off-grid measures' workspace.  A register workspace is that and the steps' partial sums behind it, so what
+// pcgc_register_prepare leaves is where both step kernels look for it
+OffgridBuffers offgrid_layout(int res, int64_t nq, int n_sums, void* workspace) {
   OffgridBuffers b;
   b.r = rank_layout(res, workspace);
-  char* w = b.r.rest;
-  b.keys = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)nq * sizeof(int64_t));
-  b.start = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)(nq + 1) * sizeof(int32_t));
-  b.sums = reinterpret_cast<long long*>(w);
-  w += align256((size_t)nq * 3 * sizeof(long long));
-  b.counts = reinterpret_cast<int*>(w);
-  w += align256((size_t)nq * sizeof(int));
-  b.partial = reinterpret_cast<double*>(w);
-  w += align256(4 * kOffgridBlocks * sizeof(double));
-  b.bad = reinterpret_cast<int*>(w);
+  Carver& c = b.r.rest;
+  b.keys = c.take<int64_t>((size_t)nq);
+  b.start = c.take<int32_t>((size_t)nq + 1);
+  b.sums = c.take<long long>((size_t)nq * 3);
+  b.counts = c.take<int>((size_t)nq);
+  b.partial = c.take<double>(4 * kOffgridBlocks);
+  b.bad = c.take<int>(2);
+  b.step_partial = c.take<double>((size_t)n_sums * kOffgridBlocks);
+  b.bytes = c.bytes();
   return b;
 }
 
 int build_target(const OffgridBuffers& b, const Cells& c, const float* q, int64_t nq, hipStream_t s, Target* t) {
   return build_cells(b.r, b.keys, b.start, b.bad, c, q, nq, s, t);
-}
-
-// the off-grid layout as it is, then [n_sums, kOffgridBlocks] doubles; the second word of the flag's 256 bytes is the step's flag
-size_t register_bytes(int res, int64_t nq, int n_sums) {
-  const size_t base = pcgc_offgrid_workspace_bytes(res, nq);
-  return base ? base + align256((size_t)n_sums * kOffgridBlocks * sizeof(double)) : 0;
 }
 
 // a step of either metric against the target pcgc_register_prepare left in the workspace; pointers_ok: the entry point's own
@@ -361,16 +350,15 @@ int register_step(const Terms& terms, bool pointers_ok, const float* p, int64_t 
   for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(pose.R[k]);
   for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(pose.t[k]) && std::isfinite(pose.c[k]);
   PCGC_REQUIRE(finite, "%s: the pose and the centre must be finite", Terms::kName);
-  PCGC_REQUIRE(workspace_bytes >= register_bytes(res, nq, Terms::kSums), "%s: workspace too small", Terms::kName);
+  const OffgridBuffers b = offgrid_layout(res, nq, Terms::kSums, workspace);     // as pcgc_register_prepare left it
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "%s: workspace too small", Terms::kName);
   hipStream_t s = (hipStream_t)stream;
-  const OffgridBuffers b = offgrid_layout(res, nq, workspace);               // as pcgc_register_prepare left it
   const Target t{Cells{h, ox, oy, oz, res}, b.r.bits, b.r.rank, b.start, q};
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + offgrid_bytes(res, nq));
   PCGC_CHECK_HIP(hipMemsetAsync(b.bad + 1, 0, sizeof(int), s));
   const int blocks = (int)std::min<int64_t>((np + 255) / 256, kOffgridBlocks);
-  hipLaunchKernelGGL(register_step_kernel<Terms>, dim3(blocks), dim3(256), 0, s, p, np, t, terms, pose, max_dist * max_dist, partial, best,
-                     n_ties, b.bad + 1);
-  hipLaunchKernelGGL(register_final_kernel, dim3(1), dim3(64), 0, s, partial, blocks, Terms::kSums, b.bad, out);
+  hipLaunchKernelGGL(register_step_kernel<Terms>, dim3(blocks), dim3(256), 0, s, p, np, t, terms, pose, max_dist * max_dist, b.step_partial,
+                     best, n_ties, b.bad + 1);
+  hipLaunchKernelGGL(register_final_kernel, dim3(1), dim3(64), 0, s, b.step_partial, blocks, Terms::kSums, b.bad, out);
   return launch_ok(Terms::kKernels);
 }
 
@@ -381,19 +369,16 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_offgrid_workspace_bytes(int res, int64_t nq) {
-  if (res < 1 || res > kOffgridMaxRes || nq <= 0 || nq >= 0x7FFFFFFF) return 0;
-  return offgrid_bytes(res, nq);
-}
+size_t pcgc_offgrid_workspace_bytes(int res, int64_t nq) { return cloud_sizes_ok(res, nq) ? offgrid_layout(res, nq, 0, nullptr).bytes : 0; }
 
 int pcgc_offgrid_transfer_normals(const float* p, int64_t np, const float* normals_p, const float* q, int64_t nq, double h, int ox,
                                   int oy, int oz, int res, double* normals_q, void* workspace, size_t workspace_bytes,
                                   pcgc_stream_t stream) {
   PCGC_REQUIRE(p && normals_p && q && normals_q && workspace && grid_ok(h, ox, oy, oz, res, np, nq),
                "pcgc_offgrid_transfer_normals: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_offgrid_workspace_bytes(res, nq), "pcgc_offgrid_transfer_normals: workspace too small");
+  const OffgridBuffers b = offgrid_layout(res, nq, 0, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_offgrid_transfer_normals: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const OffgridBuffers b = offgrid_layout(res, nq, workspace);
   Target t;
   const int rc = build_target(b, Cells{h, ox, oy, oz, res}, q, nq, s, &t);
   if (rc) return rc;
@@ -411,9 +396,9 @@ int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, con
                      pcgc_stream_t stream) {
   PCGC_REQUIRE(p && q && out4 && workspace && grid_ok(h, ox, oy, oz, res, np, nq) && (best == nullptr) == (plane == nullptr) &&
                (best == nullptr) == (n_ties == nullptr), "pcgc_offgrid_mse: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_offgrid_workspace_bytes(res, nq), "pcgc_offgrid_mse: workspace too small");
+  const OffgridBuffers b = offgrid_layout(res, nq, 0, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_offgrid_mse: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const OffgridBuffers b = offgrid_layout(res, nq, workspace);
   Target t;
   const int rc = build_target(b, Cells{h, ox, oy, oz, res}, q, nq, s, &t);
   if (rc) return rc;
@@ -424,17 +409,21 @@ int pcgc_offgrid_mse(const float* p, int64_t np, const float* q, int64_t nq, con
   return launch_ok("off-grid mse kernels");
 }
 
-size_t pcgc_register_workspace_bytes(int res, int64_t nq) { return register_bytes(res, nq, PlaneTerms::kSums); }
+size_t pcgc_register_workspace_bytes(int res, int64_t nq) {
+  return cloud_sizes_ok(res, nq) ? offgrid_layout(res, nq, PlaneTerms::kSums, nullptr).bytes : 0;
+}
 
 // pcgc_register_prepare fills the colour step's workspace as it fills the plain step's
-size_t pcgc_register_color_workspace_bytes(int res, int64_t nq) { return register_bytes(res, nq, ColorTerms::kSums); }
+size_t pcgc_register_color_workspace_bytes(int res, int64_t nq) {
+  return cloud_sizes_ok(res, nq) ? offgrid_layout(res, nq, ColorTerms::kSums, nullptr).bytes : 0;
+}
 
 int pcgc_register_prepare(const float* q, int64_t nq, double h, int ox, int oy, int oz, int res, void* workspace,
                           size_t workspace_bytes, pcgc_stream_t stream) {
   PCGC_REQUIRE(q && workspace && grid_ok(h, ox, oy, oz, res, 1, nq), "pcgc_register_prepare: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_register_workspace_bytes(res, nq), "pcgc_register_prepare: workspace too small");
+  const OffgridBuffers b = offgrid_layout(res, nq, PlaneTerms::kSums, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_register_prepare: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const OffgridBuffers b = offgrid_layout(res, nq, workspace);
   Target t;
   const int rc = build_target(b, Cells{h, ox, oy, oz, res}, q, nq, s, &t);
   if (rc) return rc;

@@ -158,21 +158,19 @@ struct CellBuffers {
   int64_t* keys;             // [n]
   int32_t* start;            // [n + 1]
   int* bad;
+  Carver rest;               // what a larger layout puts behind the cells (meshdist.hip)
+  size_t bytes;
 };
-
-size_t cell_buffer_bytes(int res, int64_t n) {
-  return rank_bytes(res) + align256((size_t)n * sizeof(int64_t)) + align256((size_t)(n + 1) * sizeof(int32_t)) + 256;
-}
 
 CellBuffers cell_buffer_layout(int res, int64_t n, void* workspace) {
   CellBuffers b;
   b.r = rank_layout(res, workspace);
-  char* w = b.r.rest;
-  b.keys = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)n * sizeof(int64_t));
-  b.start = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)(n + 1) * sizeof(int32_t));
-  b.bad = reinterpret_cast<int*>(w);
+  b.rest = b.r.rest;
+  Carver& c = b.rest;
+  b.keys = c.take<int64_t>((size_t)n);
+  b.start = c.take<int32_t>((size_t)n + 1);
+  b.bad = c.take<int>(1);
+  b.bytes = c.bytes();
   return b;
 }
 

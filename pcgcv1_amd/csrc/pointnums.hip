@@ -28,6 +28,7 @@
 // compact, rank, scan, gather and the sweep serve both.
 #include <climits>
 #include "common.h"
+#include "workspace.h"
 
 namespace pcgc {
 namespace {
@@ -426,32 +427,25 @@ __global__ void __launch_bounds__(kTile) pn_nquant_kernel(const int32_t* owner, 
 }
 
 struct CurvesWs {
-  uint32_t* seg_key;
-  int32_t* seg_idx;
-  int32_t* sorted_idx;
-  int32_t* gend;
-  int64_t* dA;
-  int64_t* dB;
-  int32_t* pts;
+  int64_t *dA, *dB;          // [total_seg]
+  uint32_t* seg_key;         // [total_seg], as are the next three
+  int32_t *seg_idx, *sorted_idx, *gend;
+  int32_t* pts;              // [max(total_pts, 1)]
+  size_t bytes;
 };
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t curves_layout(int64_t total_seg, int64_t total_pts, char* base, CurvesWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-  char* dA = take(8 * (size_t)total_seg);
-  char* dB = take(8 * (size_t)total_seg);
-  char* k = take(4 * (size_t)total_seg);
-  char* i = take(4 * (size_t)total_seg);
-  char* s = take(4 * (size_t)total_seg);
-  char* g = take(4 * (size_t)total_seg);
-  char* p = take(4 * (size_t)(total_pts > 0 ? total_pts : 1));
-  if (w) {
-    w->dA = (int64_t*)dA; w->dB = (int64_t*)dB; w->seg_key = (uint32_t*)k; w->seg_idx = (int32_t*)i;
-    w->sorted_idx = (int32_t*)s; w->gend = (int32_t*)g; w->pts = (int32_t*)p;
-  }
-  return off;
+CurvesWs curves_layout(int64_t total_seg, int64_t total_pts, void* workspace) {
+  Carver c(workspace);
+  CurvesWs w;
+  w.dA = c.take<int64_t>((size_t)total_seg);
+  w.dB = c.take<int64_t>((size_t)total_seg);
+  w.seg_key = c.take<uint32_t>((size_t)total_seg);
+  w.seg_idx = c.take<int32_t>((size_t)total_seg);
+  w.sorted_idx = c.take<int32_t>((size_t)total_seg);
+  w.gend = c.take<int32_t>((size_t)total_seg);
+  w.pts = c.take<int32_t>((size_t)(total_pts > 0 ? total_pts : 1));
+  w.bytes = c.bytes();
+  return w;
 }
 
 }  // namespace
@@ -474,7 +468,7 @@ int pcgc_pointnums_count(const float* x, const float* logits, const int32_t* k_m
 }
 
 size_t pcgc_pointnums_curves_workspace_bytes(int64_t total_seg, int64_t total_pts) {
-  return curves_layout(total_seg, total_pts, nullptr, nullptr);
+  return curves_layout(total_seg, total_pts, nullptr).bytes;
 }
 
 int pcgc_pointnums_curves(const float* x, const float* logits, const float* thresholds, int B, int cube_size,
@@ -488,10 +482,8 @@ int pcgc_pointnums_curves(const float* x, const float* logits, const float* thre
                    n_seg_blocks >= 0 && n_pts_blocks >= 0 && (n_seg_blocks == 0 || seg_blocks) &&
                    (n_pts_blocks == 0 || pts_blocks),
                "pcgc_pointnums_curves: bad arguments");
-  PCGC_REQUIRE(workspace && workspace_bytes >= pcgc_pointnums_curves_workspace_bytes(total_seg, total_pts),
-               "pcgc_pointnums_curves: workspace too small");
-  CurvesWs w;
-  curves_layout(total_seg, total_pts, (char*)workspace, &w);
+  const CurvesWs w = curves_layout(total_seg, total_pts, workspace);
+  PCGC_REQUIRE(workspace && workspace_bytes >= w.bytes, "pcgc_pointnums_curves: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int64_t vox = (int64_t)cube_size * cube_size * cube_size;
   PCGC_CHECK_HIP(hipMemsetAsync(w.dA, 0, 8 * (size_t)total_seg, s));
@@ -517,7 +509,7 @@ int pcgc_pointnums_curves(const float* x, const float* logits, const float* thre
   return launch_ok("pn_gather_kernel");
 }
 
-size_t pcgc_pointnums_normals_workspace_bytes(int64_t n_vox) { return align_up(4 * (size_t)(n_vox > 0 ? n_vox : 1)); }
+size_t pcgc_pointnums_normals_workspace_bytes(int64_t n_vox) { return align256(4 * (size_t)(n_vox > 0 ? n_vox : 1)); }
 
 int pcgc_pointnums_normals(const int64_t* point_key, const float* normals, int64_t n_points, const int64_t* vox_key,
                            int64_t n_vox, int16_t* vox_normals, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
@@ -539,7 +531,7 @@ int pcgc_pointnums_normals(const int64_t* point_key, const float* normals, int64
 }
 
 size_t pcgc_pointnums_curves_d2_workspace_bytes(int64_t total_seg, int64_t total_pts) {
-  return curves_layout(total_seg, total_pts, nullptr, nullptr);
+  return curves_layout(total_seg, total_pts, nullptr).bytes;
 }
 
 int pcgc_pointnums_curves_d2(const float* x, const float* logits, const float* thresholds, const int16_t* vox_normals, int B,
@@ -553,10 +545,8 @@ int pcgc_pointnums_curves_d2(const float* x, const float* logits, const float* t
                    n_seg_blocks >= 0 && n_pts_blocks >= 0 && (n_seg_blocks == 0 || seg_blocks) &&
                    (n_pts_blocks == 0 || pts_blocks) && (total_pts == 0 || vox_normals) && ((uintptr_t)vox_normals & 7) == 0,
                "pcgc_pointnums_curves_d2: bad arguments");
-  PCGC_REQUIRE(workspace && workspace_bytes >= pcgc_pointnums_curves_d2_workspace_bytes(total_seg, total_pts),
-               "pcgc_pointnums_curves_d2: workspace too small");
-  CurvesWs w;
-  curves_layout(total_seg, total_pts, (char*)workspace, &w);
+  const CurvesWs w = curves_layout(total_seg, total_pts, workspace);
+  PCGC_REQUIRE(workspace && workspace_bytes >= w.bytes, "pcgc_pointnums_curves_d2: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int64_t vox = (int64_t)cube_size * cube_size * cube_size;
   const int2* vn = reinterpret_cast<const int2*>(vox_normals);

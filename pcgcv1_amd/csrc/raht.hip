@@ -17,6 +17,7 @@
 // -ffp-contract=off, no step adds more than two terms, and everything else is integer arithmetic.
 #include <algorithm>
 #include "common.h"
+#include "workspace.h"
 
 namespace pcgc {
 namespace {
@@ -26,8 +27,6 @@ constexpr int kBins = 3 * kMaxDepth + 1;         // subbands 0 .. 3d-1 and the D
 constexpr int kThreads = 256;
 constexpr int kScanSegs = 16;                    // the block-histogram scan: kScanSegs segments of blocks x kBins bins
 constexpr int kTop = 1024;                       // merges (the DC's entry included) that the one-workgroup tree top holds
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ int64_t spread3(int v) {            // bit b of v -> bit 3b
   int64_t x = (int64_t)(v & 0xFFF);

@@ -17,6 +17,7 @@
 // it is used: a bad descriptor or a bad stream ends in a status, never in an access outside the chunk's own bytes.
 #include <algorithm>
 #include "common.h"
+#include "workspace.h"
 
 namespace pcgc {
 namespace {
@@ -30,8 +31,6 @@ constexpr int kMaxSteps = 1 << 20;
 constexpr int kBatch = 8;                        // steps whose symbols the encoder loads ahead
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Chunk {
   int64_t first;      // index of the chunk's first symbol in the whole symbol array
@@ -222,6 +221,19 @@ __global__ void __launch_bounds__(kLanes) decode_kernel(const uint16_t* payload,
   if (lane == 0) status[c] = (states_bad ? 1 : 0) | (rd != nwords ? 2 : 0);
 }
 
+// workspace of pcgc_rans_encode: one int32 byte count per chunk, then one slot per chunk (states + 64 * steps words)
+struct RansBuffers { int32_t* chunk_bytes; char* slots; int64_t slot_bytes; size_t bytes; };
+
+RansBuffers rans_layout(int64_t n_chunks, int steps_per_chunk, void* workspace) {
+  Carver c(workspace);
+  RansBuffers b;
+  b.slot_bytes = kStateBytes + 2 * (int64_t)kLanes * steps_per_chunk;
+  b.chunk_bytes = c.take<int32_t>((size_t)n_chunks);
+  b.slots = c.take_unrounded<char>((size_t)n_chunks * b.slot_bytes);
+  b.bytes = c.bytes();
+  return b;
+}
+
 }  // namespace
 }  // namespace pcgc
 
@@ -229,10 +241,9 @@ using namespace pcgc;
 
 extern "C" {
 
-// workspace of pcgc_rans_encode: one int32 byte count per chunk, then one slot per chunk (states + 64 * steps words)
 size_t pcgc_rans_workspace_bytes(int64_t n_chunks, int steps_per_chunk) {
   if (n_chunks <= 0 || n_chunks > 0x7FFFFFFF || steps_per_chunk < 1 || steps_per_chunk > kMaxSteps) return 0;
-  return align256((size_t)n_chunks * sizeof(int32_t)) + (size_t)n_chunks * (kStateBytes + 2 * (size_t)kLanes * steps_per_chunk);
+  return rans_layout(n_chunks, steps_per_chunk, nullptr).bytes;
 }
 
 static bool tables_fit(int max_entries) { return max_entries >= 3 && max_entries <= kMaxEntries; }
@@ -244,17 +255,15 @@ int pcgc_rans_encode(const int16_t* symbols, int64_t n_symbols, const int64_t* c
                n_chunks <= 0x7FFFFFFF && n_levels > 0 && cdf_total > 0 && out_bytes >= 0 && steps_per_chunk >= 1 &&
                steps_per_chunk <= kMaxSteps, "pcgc_rans_encode: bad arguments");
   PCGC_REQUIRE(tables_fit(max_entries), "pcgc_rans_encode: tables of %d entries (at most %d fit)", max_entries, kMaxEntries);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_rans_workspace_bytes(n_chunks, steps_per_chunk), "pcgc_rans_encode: workspace too small");
+  const RansBuffers b = rans_layout(n_chunks, steps_per_chunk, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_rans_encode: workspace too small");
   PCGC_REQUIRE(((uintptr_t)out & 1) == 0, "pcgc_rans_encode: the output buffer must be 2-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  int32_t* chunk_bytes = static_cast<int32_t*>(workspace);
-  char* slots = static_cast<char*>(workspace) + align256((size_t)n_chunks * sizeof(int32_t));
-  const int64_t slot_bytes = kStateBytes + 2 * (int64_t)kLanes * steps_per_chunk;
   hipLaunchKernelGGL(encode_kernel, dim3((unsigned)n_chunks), dim3(kLanes), (size_t)3 * max_entries * sizeof(int32_t), s, symbols, n_symbols,
-                     chunks, cdfs, cdf_offsets, cdf_total, n_levels, steps_per_chunk, max_entries, slots, slot_bytes, chunk_bytes);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), 0, s, chunk_bytes, n_chunks, offsets);
-  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, slots, slot_bytes, steps_per_chunk, chunk_bytes, chunks, offsets,
-                     static_cast<uint16_t*>(out), out_bytes);
+                     chunks, cdfs, cdf_offsets, cdf_total, n_levels, steps_per_chunk, max_entries, b.slots, b.slot_bytes, b.chunk_bytes);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), 0, s, b.chunk_bytes, n_chunks, offsets);
+  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, b.slots, b.slot_bytes, steps_per_chunk, b.chunk_bytes, chunks,
+                     offsets, static_cast<uint16_t*>(out), out_bytes);
   return launch_ok("rans encode kernels");
 }
 

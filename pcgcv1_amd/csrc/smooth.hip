@@ -97,7 +97,7 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_smooth_workspace_bytes(int res, int64_t n) { return cloud_sizes_ok(res, n) ? cell_buffer_bytes(res, n) : 0; }
+size_t pcgc_smooth_workspace_bytes(int res, int64_t n) { return cloud_sizes_ok(res, n) ? cell_buffer_layout(res, n, nullptr).bytes : 0; }
 
 int pcgc_smooth_step(const float* points, int64_t n, double h, int ox, int oy, int oz, int res, double radius, int kmin, float* out,
                      uint8_t* moved, int32_t* K, int64_t* S, int64_t* Q, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
@@ -107,9 +107,9 @@ int pcgc_smooth_step(const float* points, int64_t n, double h, int ox, int oy, i
   PCGC_REQUIRE(std::isfinite(radius) && radius > 0.0 && radius <= kSmoothMaxRadius && radius <= h,
                "pcgc_smooth_step: radius %g must be positive, at most %g and at most the cell edge %g", radius, kSmoothMaxRadius, h);
   PCGC_REQUIRE(kmin >= 3 && kmin <= kSmoothMaxK, "pcgc_smooth_step: kmin %d outside 3..%d", kmin, kSmoothMaxK);
-  PCGC_REQUIRE(workspace_bytes >= cell_buffer_bytes(res, n), "pcgc_smooth_step: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
   const CellBuffers b = cell_buffer_layout(res, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_smooth_step: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   Target t;
   const int rc = build_cells(b.r, b.keys, b.start, b.bad, Cells{h, ox, oy, oz, res}, points, n, s, &t);
   if (rc) return rc;

@@ -109,26 +109,16 @@ __global__ void __launch_bounds__(kSurfThreads) surface_round_kernel(const int32
           if ((unsigned)qx >= (unsigned)res || (unsigned)qy >= (unsigned)res) continue;
           const int z0 = max(z - G, 0), z1 = min(z + G, res - 1);
           const int64_t row = cell_of(res, qx, qy, 0);
-          const int64_t b0 = row + z0, b1 = row + z1;
-          for (int64_t w = b0 >> 5; w <= (b1 >> 5); ++w) {
-            const int64_t wbit = w << 5;
-            const unsigned all = bits[w];
-            unsigned word = all;
-            if (wbit < b0) word &= ~0u << (int)(b0 - wbit);
-            if (wbit + 31 > b1) word &= ~0u >> (int)(wbit + 31 - b1);
-            while (word) {
-              const int b = __ffs(word) - 1;
-              word &= word - 1;
-              if (wbit + b == own) continue;
-              const int64_t jr = (int64_t)rank[w] + __popc(all & ((1u << b) - 1u));
-              const int sj = in[jr];
-              if (sj == 0) continue;
-              const int64_t j = order[jr];
-              const double c = (nx * (double)normals[j * 3] + ny * (double)normals[j * 3 + 1]) + nz * (double)normals[j * 3 + 2];
-              const double a = fabs(c);
-              if (a > best) { best = a; best_c = c; best_s = sj; }       // ascending keys: the first of equal |c| stays
-            }
-          }
+          for_each_in_run(bits, row + z0, row + z1, [&](int64_t w, unsigned all, int b) {
+            if ((w << 5) + b == own) return;
+            const int64_t jr = (int64_t)rank[w] + __popc(all & ((1u << b) - 1u));
+            const int sj = in[jr];
+            if (sj == 0) return;
+            const int64_t j = order[jr];
+            const double c = (nx * (double)normals[j * 3] + ny * (double)normals[j * 3 + 1]) + nz * (double)normals[j * 3 + 2];
+            const double a = fabs(c);
+            if (a > best) { best = a; best_c = c; best_s = sj; }         // ascending keys: the first of equal |c| stays
+          });
         }
       if (best >= tau.v[st->stage]) {
         s = (int8_t)(best_c >= 0.0 ? best_s : -best_s);
@@ -217,26 +207,16 @@ __global__ void __launch_bounds__(kSurfThreads) surface_implicit_kernel(const in
       const int z0 = max(kz - R, 0), z1 = min(kz + R + 1, res - 1);
       if (z1 < z0) continue;
       const int64_t row = cell_of(res, qx, qy, 0);
-      const int64_t b0 = row + z0, b1 = row + z1;
-      for (int64_t w = b0 >> 5; w <= (b1 >> 5); ++w) {
-        const int64_t wbit = w << 5;
-        const unsigned all = bits[w];
-        unsigned word = all;
-        if (wbit < b0) word &= ~0u << (int)(b0 - wbit);
-        if (wbit + 31 > b1) word &= ~0u >> (int)(wbit + 31 - b1);
-        while (word) {
-          const int b = __ffs(word) - 1;
-          word &= word - 1;
-          const int ddz = 1 - 2 * ((int)(wbit + b - row) - kz);
-          const int d2 = dxy + ddz * ddz;
-          if (d2 > lim) continue;
-          const double* Nq = N + 3 * ((int64_t)rank[w] + __popc(all & ((1u << b) - 1u)));
-          const double t = 1.0 - (double)d2 / denom;
-          const double wt = t * t;
-          num += wt * ((Nq[0] * (double)ddx + Nq[1] * (double)ddy) + Nq[2] * (double)ddz);
-          W += wt;
-        }
-      }
+      for_each_in_run(bits, row + z0, row + z1, [&](int64_t w, unsigned all, int b) {
+        const int ddz = 1 - 2 * ((int)((w << 5) + b - row) - kz);
+        const int d2 = dxy + ddz * ddz;
+        if (d2 > lim) return;
+        const double* Nq = N + 3 * ((int64_t)rank[w] + __popc(all & ((1u << b) - 1u)));
+        const double t = 1.0 - (double)d2 / denom;
+        const double wt = t * t;
+        num += wt * ((Nq[0] * (double)ddx + Nq[1] * (double)ddy) + Nq[2] * (double)ddz);
+        W += wt;
+      });
     }
   f[v] = 0.5 * num / W;
 }
@@ -259,42 +239,13 @@ __device__ __forceinline__ double f_at(const Lattice& L, int x, int y, int z) {
   return r < L.n_vertices ? L.f[r] : 0.0;
 }
 
-// EMIT = false: block_tri[b] = the triangles of scan block b.  EMIT = true: block_tri holds the exclusive prefix and the
-// triangles are written, three edge ids each, in the order of the cells' keys.
-template <bool EMIT>
-__global__ void __launch_bounds__(kScanThreads) surface_triangles_kernel(const unsigned* cbits, Lattice L, int64_t* block_tri,
-                                                                         int64_t n_triangles, int64_t* tri_ids) {
-  unsigned w[kWordsPerThread];
-  const unsigned any = load_words(cbits, blockIdx.x, w);
+// f(cx, cy, cz, inside) for every cell among the calling thread's words w of scan block blockIdx.x that the surface crosses, in
+// key order.  The cell's padded coordinates are its lowest corner's padded vertex coordinates, c + 1 = (c - 1) + 2; bit o of
+// `inside` is set where corner o has f < 0, and a cell with none or all of them inside holds no triangle.
+template <typename F>
+__device__ __forceinline__ void for_each_crossed_cell(const unsigned (&w)[kWordsPerThread], const Lattice& L, F f) {
   const int64_t cside = L.side - 1;
   const int64_t word0 = (int64_t)blockIdx.x * kScanWords + (int64_t)threadIdx.x * kWordsPerThread;
-  unsigned count = 0;
-  if (any) {
-    for (int k = 0; k < kWordsPerThread; ++k) {
-      unsigned x = w[k];
-      while (x) {
-        const int b = __ffs(x) - 1;
-        x &= x - 1;
-        const int64_t key = (word0 + k) * 32 + b;
-        // the cell's padded coordinates are its lowest corner's padded vertex coordinates: c + 1 = (c - 1) + 2
-        const int cx = (int)(key / (cside * cside)), cy = (int)(key / cside % cside), cz = (int)(key % cside);
-        unsigned inside = 0;
-#pragma unroll
-        for (int o = 0; o < 8; ++o)
-          if (f_at(L, cx + (o >> 2), cy + ((o >> 1) & 1), cz + (o & 1)) < 0.0) inside |= 1u << o;
-        if (inside == 0u || inside == 255u) continue;
-        cell_triangles(inside, [&](int, int, int) { ++count; });
-      }
-    }
-  }
-  unsigned total;
-  const unsigned before = block_scan(count, &total);
-  if (!EMIT) {
-    if (threadIdx.x == 0) block_tri[blockIdx.x] = total;
-    return;
-  }
-  if (count == 0) return;
-  int64_t o = block_tri[blockIdx.x] + before;
   for (int k = 0; k < kWordsPerThread; ++k) {
     unsigned x = w[k];
     while (x) {
@@ -304,23 +255,46 @@ __global__ void __launch_bounds__(kScanThreads) surface_triangles_kernel(const u
       const int cx = (int)(key / (cside * cside)), cy = (int)(key / cside % cside), cz = (int)(key % cside);
       unsigned inside = 0;
 #pragma unroll
-      for (int c = 0; c < 8; ++c)
-        if (f_at(L, cx + (c >> 2), cy + ((c >> 1) & 1), cz + (c & 1)) < 0.0) inside |= 1u << c;
+      for (int o = 0; o < 8; ++o)
+        if (f_at(L, cx + (o >> 2), cy + ((o >> 1) & 1), cz + (o & 1)) < 0.0) inside |= 1u << o;
       if (inside == 0u || inside == 255u) continue;
-      auto id = [&](int e) {
-        const int lo = e >> 3, hi = e & 7;
-        return cell_of(L.side, cx + (lo >> 2), cy + ((lo >> 1) & 1), cz + (lo & 1)) * 7 + direction_of(hi ^ lo);
-      };
-      cell_triangles(inside, [&](int e0, int e1, int e2) {
-        if (o < n_triangles) {
-          tri_ids[o * 3] = id(e0);
-          tri_ids[o * 3 + 1] = id(e1);
-          tri_ids[o * 3 + 2] = id(e2);
-        }
-        ++o;
-      });
+      f(cx, cy, cz, inside);
     }
   }
+}
+
+// EMIT = false: block_tri[b] = the triangles of scan block b.  EMIT = true: block_tri holds the exclusive prefix and the
+// triangles are written, three edge ids each, in the order of the cells' keys.
+template <bool EMIT>
+__global__ void __launch_bounds__(kScanThreads) surface_triangles_kernel(const unsigned* cbits, Lattice L, int64_t* block_tri,
+                                                                         int64_t n_triangles, int64_t* tri_ids) {
+  unsigned w[kWordsPerThread];
+  const unsigned any = load_words(cbits, blockIdx.x, w);
+  unsigned count = 0;
+  if (any)
+    for_each_crossed_cell(w, L, [&](int, int, int, unsigned inside) { cell_triangles(inside, [&](int, int, int) { ++count; }); });
+  unsigned total;
+  const unsigned before = block_scan(count, &total);
+  if (!EMIT) {
+    if (threadIdx.x == 0) block_tri[blockIdx.x] = total;
+    return;
+  }
+  if (count == 0) return;
+  int64_t o = block_tri[blockIdx.x] + before;
+  for_each_crossed_cell(w, L, [&](int cx, int cy, int cz, unsigned inside) {
+    auto id = [&](int e) {
+      const int lo = e >> 3, hi = e & 7;
+      return cell_of(L.side, cx + (lo >> 2), cy + ((lo >> 1) & 1), cz + (lo & 1)) * 7 + direction_of(hi ^ lo);
+    };
+    cell_triangles(inside, [&](int e0, int e1, int e2) {
+      if (o < n_triangles) {
+        tri_ids[o * 3] = id(e0);
+        tri_ids[o * 3 + 1] = id(e1);
+        tri_ids[o * 3 + 2] = id(e2);
+      }
+      ++o;
+    });
+  });
 }
 
 // the mesh vertex on lattice edge id = key(a) * 7 + direction
@@ -347,7 +321,7 @@ __global__ void __launch_bounds__(kSurfThreads) surface_index_kernel(const int64
 
 bool surface_size_ok(int bits, int64_t n) { return bits >= 1 && bits <= kSurfMaxBits && n >= 1 && n <= 0x7FFFFFFF; }
 
-// after the occupancy rank structure
+// the occupancy rank structure, then
 struct SurfaceBuffers {
   RankBuffers occ;
   unsigned* order;            // [n] rank -> row
@@ -358,40 +332,28 @@ struct SurfaceBuffers {
   int64_t *n_cells, *n_triangles;
   RankBuffers ver;            // lattice vertices over (res + 3)^3
   double* normals;            // [n, 3] oriented, by rank
+  int64_t cblk, vblk;         // scan blocks of cbits and of ver.bits
+  size_t bytes;
 };
-
-size_t surface_bytes(int bits, int64_t n) {
-  const int res = 1 << bits;
-  const int64_t cblk = scan_blocks((int64_t)(res + 2) * (res + 2) * (res + 2));
-  return rank_bytes(res) + align256((size_t)n * sizeof(unsigned)) + 2 * align256((size_t)n) + 256 + align256(padded_bits_bytes(cblk)) +
-         2 * align256((size_t)cblk * sizeof(int64_t)) + 256 + rank_bytes(res + 3) + align256((size_t)n * 3 * sizeof(double));
-}
 
 SurfaceBuffers surface_layout(int bits, int64_t n, void* workspace) {
   const int res = 1 << bits;
-  const int64_t cblk = scan_blocks((int64_t)(res + 2) * (res + 2) * (res + 2));
   SurfaceBuffers b;
+  b.cblk = scan_blocks((int64_t)(res + 2) * (res + 2) * (res + 2));
+  b.vblk = scan_blocks((int64_t)(res + 3) * (res + 3) * (res + 3));
   b.occ = rank_layout(res, workspace);
-  char* w = b.occ.rest;
-  b.order = reinterpret_cast<unsigned*>(w);
-  w += align256((size_t)n * sizeof(unsigned));
-  for (int k = 0; k < 2; ++k) {
-    b.sign[k] = reinterpret_cast<int8_t*>(w);
-    w += align256((size_t)n);
-  }
-  b.state = reinterpret_cast<OrientState*>(w);
-  w += 256;
-  b.cbits = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(cblk));
-  b.cblock = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)cblk * sizeof(int64_t));
-  b.tblock = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)cblk * sizeof(int64_t));
-  b.n_cells = reinterpret_cast<int64_t*>(w);
+  Carver& c = b.occ.rest;
+  b.order = c.take<unsigned>((size_t)n);
+  for (int k = 0; k < 2; ++k) b.sign[k] = c.take<int8_t>((size_t)n);
+  b.state = c.take<OrientState>(1);
+  b.cbits = c.take<unsigned>(padded_bits_words(b.cblk));
+  b.cblock = c.take<int64_t>((size_t)b.cblk);
+  b.tblock = c.take<int64_t>((size_t)b.cblk);
+  b.n_cells = c.take<int64_t>(2);
   b.n_triangles = b.n_cells + 1;
-  w += 256;
-  b.ver = rank_layout(res + 3, w);
-  b.normals = reinterpret_cast<double*>(b.ver.rest);
+  b.ver = rank_layout(res + 3, c);
+  b.normals = b.ver.rest.take<double>((size_t)n * 3);
+  b.bytes = b.ver.rest.bytes();
   return b;
 }
 
@@ -421,7 +383,7 @@ using namespace pcgc;
 
 extern "C" {
 
-size_t pcgc_surface_workspace_bytes(int bits, int64_t n) { return surface_size_ok(bits, n) ? surface_bytes(bits, n) : 0; }
+size_t pcgc_surface_workspace_bytes(int bits, int64_t n) { return surface_size_ok(bits, n) ? surface_layout(bits, n, nullptr).bytes : 0; }
 
 int pcgc_surface_orient(const int32_t* points, const float* normals, const uint8_t* seed, int64_t n, int bits, int gap, const double* tau,
                         int n_tau, int batch, int8_t* sign, int32_t* rounds, int32_t* readbacks, void* workspace, size_t workspace_bytes,
@@ -434,10 +396,10 @@ int pcgc_surface_orient(const int32_t* points, const float* normals, const uint8
     PCGC_REQUIRE(tau[k] >= 0.0 && tau[k] <= 1.0, "pcgc_surface_orient: stage threshold %d = %g outside [0, 1]", k, tau[k]);
   PCGC_REQUIRE(tau[n_tau - 1] == 0.0, "pcgc_surface_orient: the last stage threshold is %g, it must be 0.0", tau[n_tau - 1]);
   PCGC_REQUIRE(batch >= 1 && batch <= 4096, "pcgc_surface_orient: batch = %d outside 1..4096", batch);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_surface_workspace_bytes(bits, n), "pcgc_surface_orient: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int res = 1 << bits;
   const SurfaceBuffers b = surface_layout(bits, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_surface_orient: workspace too small");
   Tau t;
   t.n = n_tau;
   for (int k = 0; k < kSurfMaxStages; ++k) t.v[k] = k < n_tau ? tau[k] : 0.0;
@@ -473,20 +435,19 @@ int pcgc_surface_orient(const int32_t* points, const float* normals, const uint8
 int pcgc_surface_lattice(const int32_t* points, int64_t n, int bits, int64_t* counts, void* workspace, size_t workspace_bytes,
                          pcgc_stream_t stream) {
   PCGC_REQUIRE(points && counts && workspace && surface_size_ok(bits, n), "pcgc_surface_lattice: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_surface_workspace_bytes(bits, n), "pcgc_surface_lattice: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int res = 1 << bits;
   const SurfaceBuffers b = surface_layout(bits, n, workspace);
-  const int64_t cblk = scan_blocks((int64_t)(res + 2) * (res + 2) * (res + 2)), vblk = scan_blocks((int64_t)(res + 3) * (res + 3) * (res + 3));
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_surface_lattice: workspace too small");
   if (int rc = surface_prepare(b, points, n, res, s)) return rc;
-  PCGC_CHECK_HIP(hipMemsetAsync(b.cbits, 0, padded_bits_bytes(cblk), s));
-  PCGC_CHECK_HIP(hipMemsetAsync(b.ver.bits, 0, padded_bits_bytes(vblk), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.cbits, 0, padded_bits_bytes(b.cblk), s));
+  PCGC_CHECK_HIP(hipMemsetAsync(b.ver.bits, 0, padded_bits_bytes(b.vblk), s));
   hipLaunchKernelGGL(surface_mark_kernel, dim3(blocks_for(n)), dim3(kSurfThreads), 0, s, points, n, res, b.cbits, b.ver.bits);
-  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)cblk), dim3(kScanThreads), 0, s, b.cbits, b.cblock);
-  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.cblock, cblk, b.n_cells);
-  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)vblk), dim3(kScanThreads), 0, s, b.ver.bits, b.ver.block_count);
-  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.ver.block_count, vblk, b.ver.n_set);
-  hipLaunchKernelGGL(rank_write_kernel, dim3((unsigned)vblk), dim3(kScanThreads), 0, s, b.ver.bits, b.ver.block_count, b.ver.rank);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)b.cblk), dim3(kScanThreads), 0, s, b.cbits, b.cblock);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.cblock, b.cblk, b.n_cells);
+  hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)b.vblk), dim3(kScanThreads), 0, s, b.ver.bits, b.ver.block_count);
+  hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.ver.block_count, b.vblk, b.ver.n_set);
+  hipLaunchKernelGGL(rank_write_kernel, dim3((unsigned)b.vblk), dim3(kScanThreads), 0, s, b.ver.bits, b.ver.block_count, b.ver.rank);
   hipLaunchKernelGGL(surface_counts_kernel, dim3(1), dim3(1), 0, s, b.n_cells, b.ver.n_set, counts);
   return launch_ok("lattice kernels");
 }
@@ -497,12 +458,11 @@ int pcgc_surface_implicit(const double* oriented_normals, int64_t n, int bits, i
                "pcgc_surface_implicit: bad arguments");
   PCGC_REQUIRE(radius >= kSurfMinRadius && radius <= kSurfMaxRadius, "pcgc_surface_implicit: radius = %d outside %d..%d", radius,
                kSurfMinRadius, kSurfMaxRadius);
-  PCGC_REQUIRE(workspace_bytes >= pcgc_surface_workspace_bytes(bits, n), "pcgc_surface_implicit: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int res = 1 << bits;
   const SurfaceBuffers b = surface_layout(bits, n, workspace);
-  const int64_t vblk = scan_blocks((int64_t)(res + 3) * (res + 3) * (res + 3));
-  hipLaunchKernelGGL(surface_vertex_list_kernel, dim3((unsigned)vblk), dim3(kScanThreads), 0, s, b.ver.bits, b.ver.block_count, n_vertices,
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_surface_implicit: workspace too small");
+  hipLaunchKernelGGL(surface_vertex_list_kernel, dim3((unsigned)b.vblk), dim3(kScanThreads), 0, s, b.ver.bits, b.ver.block_count, n_vertices,
                      vertex_keys);
   hipLaunchKernelGGL(surface_normals_kernel, dim3(blocks_for(n)), dim3(kSurfThreads), 0, s, oriented_normals, b.order, b.occ.n_set, b.normals);
   hipLaunchKernelGGL(surface_implicit_kernel, dim3(blocks_for(n_vertices)), dim3(kSurfThreads), 0, s, vertex_keys, n_vertices, b.ver.n_set, res,
@@ -514,19 +474,18 @@ int pcgc_surface_triangles(const double* f, int64_t n_vertices, int64_t n, int b
                            int64_t* count, void* workspace, size_t workspace_bytes, pcgc_stream_t stream) {
   PCGC_REQUIRE(f && workspace && surface_size_ok(bits, n) && n_vertices >= 1 && n_triangles >= 0, "pcgc_surface_triangles: bad arguments");
   PCGC_REQUIRE((triangle_ids != nullptr) != (count != nullptr), "pcgc_surface_triangles: give count (first call) or triangle_ids (second)");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_surface_workspace_bytes(bits, n), "pcgc_surface_triangles: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int res = 1 << bits;
   const SurfaceBuffers b = surface_layout(bits, n, workspace);
-  const int64_t cblk = scan_blocks((int64_t)(res + 2) * (res + 2) * (res + 2));
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_surface_triangles: workspace too small");
   const Lattice L = lattice_of(b, res, f, n_vertices);
   if (count) {
-    hipLaunchKernelGGL(surface_triangles_kernel<false>, dim3((unsigned)cblk), dim3(kScanThreads), 0, s, b.cbits, L, b.tblock, (int64_t)0,
+    hipLaunchKernelGGL(surface_triangles_kernel<false>, dim3((unsigned)b.cblk), dim3(kScanThreads), 0, s, b.cbits, L, b.tblock, (int64_t)0,
                        (int64_t*)nullptr);
-    hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.tblock, cblk, b.n_triangles);
+    hipLaunchKernelGGL(grid_block_scan_kernel, dim3(1), dim3(1024), 0, s, b.tblock, b.cblk, b.n_triangles);
     PCGC_CHECK_HIP(hipMemcpyAsync(count, b.n_triangles, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   } else if (n_triangles > 0) {
-    hipLaunchKernelGGL(surface_triangles_kernel<true>, dim3((unsigned)cblk), dim3(kScanThreads), 0, s, b.cbits, L, b.tblock, n_triangles,
+    hipLaunchKernelGGL(surface_triangles_kernel<true>, dim3((unsigned)b.cblk), dim3(kScanThreads), 0, s, b.cbits, L, b.tblock, n_triangles,
                        triangle_ids);
   }
   return launch_ok("triangle kernels");
@@ -538,9 +497,9 @@ int pcgc_surface_mesh(const int64_t* edge_ids, int64_t n_edges, const int64_t* t
   PCGC_REQUIRE(edge_ids && triangle_ids && f && vertices && triangles && workspace && surface_size_ok(bits, n) && n_vertices >= 1 &&
                    n_edges >= 1 && n_edges <= 0x7FFFFFFF && n_triangles >= 1,
                "pcgc_surface_mesh: bad arguments");
-  PCGC_REQUIRE(workspace_bytes >= pcgc_surface_workspace_bytes(bits, n), "pcgc_surface_mesh: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const SurfaceBuffers b = surface_layout(bits, n, workspace);
+  PCGC_REQUIRE(workspace_bytes >= b.bytes, "pcgc_surface_mesh: workspace too small");
   const Lattice L = lattice_of(b, 1 << bits, f, n_vertices);
   hipLaunchKernelGGL(surface_vertices_kernel, dim3(blocks_for(n_edges)), dim3(kSurfThreads), 0, s, edge_ids, n_edges, L, vertices);
   hipLaunchKernelGGL(surface_index_kernel, dim3(blocks_for(n_triangles * 3)), dim3(kSurfThreads), 0, s, edge_ids, n_edges, triangle_ids,

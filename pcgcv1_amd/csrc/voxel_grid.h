@@ -5,13 +5,14 @@
 //   * nearest_d2: the exact squared distance to the nearest occupied cell, by Chebyshev shells;
 //   * for_each_at_distance: every occupied cell at that distance, in a fixed order (the callers' float sums follow it);
 //   * the popcount scan that turns a bit set into per-block offsets of its set bits in key order, and for_each_set_bit,
-//     which lists them;
+//     which lists them, and for_each_in_run, the set bits of a z-run of one column;
 //   * the rank table over that scan: an occupied cell's index among the set bits (rank_of, build_rank);
 //   * find_sorted_key: lower bound in a sorted key list.
 // Everything here has internal linkage: the objects link into one library.
 #pragma once
 #include <algorithm>
 #include "common.h"
+#include "workspace.h"
 
 namespace pcgc {
 namespace {
@@ -195,6 +196,25 @@ __device__ __forceinline__ void for_each_set_bit(const unsigned* bits, const int
   }
 }
 
+// f(w, all, b) for every set bit among bits b0 .. b1 of the set, ascending: bit b of word w, `all` that whole word (the bit's rank
+// is rank[w] + popc(all & ((1u << b) - 1u))).  The z-run of a column is cell_of(res, x, y, z0) .. cell_of(res, x, y, z1), z inside
+// the row; with res < 32 its words hold other rows too, which the masks drop.
+template <typename F>
+__device__ __forceinline__ void for_each_in_run(const unsigned* bits, int64_t b0, int64_t b1, F f) {
+  for (int64_t w = b0 >> 5; w <= (b1 >> 5); ++w) {
+    const int64_t wbit = w << 5;
+    const unsigned all = bits[w];
+    unsigned word = all;
+    if (wbit < b0) word &= ~0u << (int)(b0 - wbit);
+    if (wbit + 31 > b1) word &= ~0u >> (int)(wbit + 31 - b1);
+    while (word) {
+      const int b = __ffs(word) - 1;
+      word &= word - 1;
+      f(w, all, b);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- rank table
 // rank[w] = number of set bits in words 0 .. w-1, one 32-bit entry per word of the padded bit set: the index of an occupied
 // cell among the set bits in key order is two loads, no search (color.hip's colours, offgrid.hip's cell starts).
@@ -221,39 +241,30 @@ __global__ void __launch_bounds__(kScanThreads) rank_write_kernel(const unsigned
   }
 }
 
-// host side: scan blocks of a grid of `cells` cells, bytes of its padded bit set, 256-byte rounding of a workspace part
+// host side: scan blocks of a grid of `cells` cells, words of its padded bit set
 int64_t scan_blocks(int64_t cells) { return (cells + (int64_t)kScanWords * 32 - 1) / ((int64_t)kScanWords * 32); }
 
-size_t padded_bits_bytes(int64_t nblk) { return (size_t)nblk * kScanWords * sizeof(unsigned); }
+size_t padded_bits_words(int64_t nblk) { return (size_t)nblk * kScanWords; }
+size_t padded_bits_bytes(int64_t nblk) { return padded_bits_words(nblk) * sizeof(unsigned); }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the rank structure at the head of a workspace, and what follows it
+// the rank structure of a res^3 grid, and the carver that goes on behind it: a layout that begins with (or holds) a rank
+// structure takes its own regions from `rest` (workspace.h: one layout function; null base = size)
 struct RankBuffers {
   unsigned* bits;
   unsigned* rank;
   int64_t* block_count;
   int64_t* n_set;
-  char* rest;                // what follows the rank structure in the workspace
+  Carver rest;
 };
 
-size_t rank_bytes(int res) {
-  const int64_t nblk = scan_blocks((int64_t)res * res * res);
-  return 2 * align256(padded_bits_bytes(nblk)) + align256((size_t)nblk * sizeof(int64_t)) + 256;
-}
-
-RankBuffers rank_layout(int res, void* workspace) {
+RankBuffers rank_layout(int res, Carver c) {
   const int64_t nblk = scan_blocks((int64_t)res * res * res);
   RankBuffers r;
-  char* w = static_cast<char*>(workspace);
-  r.bits = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(nblk));
-  r.rank = reinterpret_cast<unsigned*>(w);
-  w += align256(padded_bits_bytes(nblk));
-  r.block_count = reinterpret_cast<int64_t*>(w);
-  w += align256((size_t)nblk * sizeof(int64_t));
-  r.n_set = reinterpret_cast<int64_t*>(w);
-  r.rest = w + 256;
+  r.bits = c.take<unsigned>(padded_bits_words(nblk));
+  r.rank = c.take<unsigned>(padded_bits_words(nblk));
+  r.block_count = c.take<int64_t>((size_t)nblk);
+  r.n_set = c.take<int64_t>(1);
+  r.rest = c;
   return r;
 }
 
