@@ -17,6 +17,18 @@ from . import _lib
 from .cells import cell_keys
 
 
+GRID_MAX_RES = 4096               # cells per axis of the largest voxel grid pcgc_d1_mse, pcgc_d2_*, pcgc_color_mse and pcgc_recolor take
+
+
+def check_grid_range(what, *clouds):
+    """ValueError unless every coordinate of every cloud lies within [0, GRID_MAX_RES): beyond it the library has only its
+    "bad arguments" to say.  Host arithmetic on the caller's arrays, before anything touches the device."""
+    lo = min(int(np.min(c)) for c in clouds)
+    hi = max(int(np.max(c)) for c in clouds)
+    if lo < 0 or hi >= GRID_MAX_RES:
+        raise ValueError("%s: coordinates must lie within [0, %d) (got %d .. %d)" % (what, GRID_MAX_RES, lo, hi))
+
+
 def _d1_one_way(a_d, b_d, res, ws):
     out = torch.empty(2, dtype=torch.float64, device=a_d.device)
     _lib.check(_lib.hip().pcgc_d1_mse(_lib.dptr(a_d), a_d.shape[0], _lib.dptr(b_d), b_d.shape[0], res, _lib.dptr(out),
@@ -27,6 +39,7 @@ def _d1_one_way(a_d, b_d, res, ws):
 
 def d1_metrics(points_a, points_b, resolution):
     """resolution = peak value (pc_error -r), e.g. 1023 for a 10-bit cloud.  Returns a dict with the pc_error keys."""
+    check_grid_range("d1_metrics", points_a, points_b)
     dev = _lib.require_gpu()
     res = int(max(int(np.max(points_a)), int(np.max(points_b))) + 1)
     a_d = torch.from_numpy(np.ascontiguousarray(points_a, np.int32)).to(dev)
@@ -60,6 +73,7 @@ def _sorted_keys(points_d, res):
 def d2_metrics(points_a, normals_a, points_b, resolution):
     """Point-to-plane (D2) figures of `pc_error -a A -b B -n A` (myutils/pc_error_wrapper.py:46-51): A carries
     normals, B (the decoded cloud) receives them from A.  Returns the p2plane keys of the wrapper's table."""
+    check_grid_range("d2_metrics", points_a, points_b)
     dev = _lib.require_gpu()
     lib = _lib.hip()
     res = int(max(int(np.max(points_a)), int(np.max(points_b))) + 1)
@@ -109,6 +123,7 @@ def color_metrics(points_a, colors_a, points_b, colors_b):
     nearest points of B and yuv = BT.709 of rgb / 255, "c[i],PSNR1" = -10 log10 of it, the 2 forms with A and B swapped,
     the F forms the larger mse (smaller PSNR) per channel (include/pcgc.h, pcgc_color_mse; pinned against the pc_error
     binary in tests/golden/pc_error_color.npz).  The tool's h.c[i] lines are not produced."""
+    check_grid_range("color_metrics", points_a, points_b)
     lib = _lib.hip()
     res = int(max(int(np.max(points_a)), int(np.max(points_b))) + 1)
     pa, ca = _colored_cloud(points_a, colors_a, res, "color_metrics: cloud A")

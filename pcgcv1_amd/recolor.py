@@ -35,8 +35,7 @@ def recolor(source_points, source_colors, target_points, resolution=None, return
     the order of target_points.  resolution: edge of the grid (default: the largest coordinate of either cloud + 1).
     return_counts=True also returns |B(t)| per target point (int32; 0 = coloured from its own nearest source points)."""
     import torch
-    dev = _lib.require_gpu()
-    lib = _lib.hip()
+    from .metrics import GRID_MAX_RES, check_grid_range
     src = np.ascontiguousarray(np.asarray(source_points)[:, :3], np.int32)
     col = np.asarray(source_colors)
     tgt = np.asarray(target_points)
@@ -49,13 +48,17 @@ def recolor(source_points, source_colors, target_points, resolution=None, return
     if resolution is None:
         resolution = int(max(int(src.max()), int(np.rint(np.max(tgt))))) + 1
     res = int(resolution)
-    if int(src.min()) < 0 or int(src.max()) >= res or not (1 <= res <= 4096):
-        raise ValueError("recolor: source coordinates must lie within [0, resolution = %d), resolution <= 4096" % res)
+    # the grid's limit by name first (a target beyond it shows in the default resolution), then the caller's own resolution
+    check_grid_range("recolor", src, [0, res - 1])
+    if int(src.max()) >= res:
+        raise ValueError("recolor: source coordinates must lie within [0, resolution = %d), resolution <= %d" % (res, GRID_MAX_RES))
     skeys = (src[:, 0].astype(np.int64) * res + src[:, 1]) * res + src[:, 2]
     if len(np.unique(skeys)) != len(skeys):
         raise ValueError("recolor: the source cloud holds duplicate points (pass unique voxels)")
     cells, inv = target_cells(tgt, res)
     tkeys = (cells[:, 0].astype(np.int64) * res + cells[:, 1]) * res + cells[:, 2]           # ascending: np.unique's order
+    dev = _lib.require_gpu()
+    lib = _lib.hip()
     s_d = torch.from_numpy(src).to(dev)
     c_d = torch.from_numpy(np.ascontiguousarray(col)).to(dev)
     k_d = torch.from_numpy(tkeys).to(dev)

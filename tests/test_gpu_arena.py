@@ -672,6 +672,79 @@ for name in ("relu_bwd", "relu_bwd copy", "vrn_merge", "vrn_bwd_split", "vrn_bwd
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# The voxel-grid metrics (tail.hip D1 / D2, color.hip, mesh.hip): workspaces carved by hand (pcgc_d1_*, pcgc_d2_*: sums of size_t
+# terms) or by a Carver layout, a bit set whose scan "reads no bound" because it is padded to whole scan blocks.  res 51: 132 651
+# cells, two scan blocks of 131 072 bits, the second one barely begun; a few hundred points in two clusters that reach the first
+# and the last cell.  (tests/test_gpu_grid_range.py runs the same entry points at the top of their range.)
+# ----------------------------------------------------------------------------------------------------------------------
+GRID_RES = 51
+
+
+def _grid_cloud(seed):
+    """int32 [n,3] in a seeded order: a cluster through the last cell of the grid, a smaller one through the first"""
+    rng = _rng("grid cloud", seed)
+    p = np.concatenate([GRID_RES - 1 - rng.integers(0, 12, (300, 3)), rng.integers(0, 6, (40, 3)), [[0, 0, 0]], [[GRID_RES - 1] * 3]])
+    p = np.unique(p, axis=0)
+    return torch.from_numpy(p[rng.permutation(len(p))].astype(np.int32)), rng
+
+
+def _sorted_keys(p):
+    p = p.to(I64)
+    return torch.sort((p[:, 0] * GRID_RES + p[:, 1]) * GRID_RES + p[:, 2])[0].contiguous()
+
+
+def _grid_metric(name):
+    def make():
+        L, res = lib(), GRID_RES
+        (a, rng), (b, _) = _grid_cloud(1), _grid_cloud(2)
+        na, nb, kb = int(a.shape[0]), int(b.shape[0]), _sorted_keys(b)
+        ca, cb = (torch.from_numpy(rng.integers(0, 256, (n, 3)).astype(np.uint8)) for n in (na, nb))
+        if name == "d1_mse":
+            nbytes = int(L.pcgc_d1_workspace_bytes(res))
+            return (lambda t: L.pcgc_d1_mse(P(t["pa"]), na, P(t["pb"]), nb, res, P(t["out2"]), P(t["workspace"]), nbytes, S())), \
+                [In("pa", a), In("pb", b), Out("out2", (2,), F64), Scratch("workspace", nbytes)]
+        if name == "d2_transfer_normals":
+            nbytes = int(L.pcgc_d2_workspace_bytes(res, nb))
+            return (lambda t: L.pcgc_d2_transfer_normals(P(t["p"]), na, P(t["normals_p"]), P(t["qkeys"]), nb, res, P(t["normals_q"]),
+                                                         P(t["workspace"]), nbytes, S())), \
+                [In("p", a), In("normals_p", _f(rng, (na, 3))), In("qkeys", kb), Out("normals_q", (nb, 3), F32), Scratch("workspace", nbytes)]
+        if name == "d2_mse":
+            nbytes = int(L.pcgc_d2_workspace_bytes(res, nb))
+            return (lambda t: L.pcgc_d2_mse(P(t["p"]), na, P(t["qkeys"]), nb, P(t["normals_q"]), res, P(t["out2"]), P(t["workspace"]), nbytes, S())), \
+                [In("p", a), In("qkeys", kb), In("normals_q", _f(rng, (nb, 3))), Out("out2", (2,), F64), Scratch("workspace", nbytes)]
+        if name == "recolor":
+            nbytes = int(L.pcgc_recolor_workspace_bytes(res, na, nb))
+            return (lambda t: L.pcgc_recolor(P(t["source_points"]), P(t["source_colors"]), na, P(t["target_keys"]), nb, res, P(t["target_colors"]),
+                                             P(t["backward_counts"]), P(t["workspace"]), nbytes, S())), \
+                [In("source_points", a), In("source_colors", ca), In("target_keys", kb), Out("target_colors", (nb, 3), U8),
+                 Out("backward_counts", (nb,), I32), Scratch("workspace", nbytes)]
+        if name == "color_mse":
+            nbytes = int(L.pcgc_color_mse_workspace_bytes(res, nb))
+            return (lambda t: L.pcgc_color_mse(P(t["points_a"]), P(t["colors_a"]), na, P(t["points_b"]), P(t["colors_b"]), nb, res, P(t["out3"]),
+                                               P(t["workspace"]), nbytes, S())), \
+                [In("points_a", a), In("colors_a", ca), In("points_b", b), In("colors_b", cb), Out("out3", (3,), F64), Scratch("workspace", nbytes)]
+        if name == "mesh_voxelize":                            # resolution 50: the grid of resolution + 1 = 51 cells per axis
+            n = 500
+            pts = torch.from_numpy(rng.uniform(-3.0, 4.0, (n, 3)))
+            nbytes = int(L.pcgc_mesh_voxelize_workspace_bytes(res - 1))
+            return (lambda t: L.pcgc_mesh_voxelize(P(t["points"]), n, res - 1, P(t["out"]), n, P(t["n_out"]), P(t["workspace"]), nbytes, S())), \
+                [In("points", pts), Out("out", (n, 3), I32), Out("n_out", (1,), I64), Scratch("workspace", nbytes)]
+        if name == "estimate_normals":
+            nbytes = int(L.pcgc_normals_workspace_bytes(res, na, 10.0))
+            return (lambda t: L.pcgc_estimate_normals(P(t["points"]), na, res, 10.0, 20, P(t["normals"]), P(t["cov"]), P(t["n_neighbours"]),
+                                                      P(t["workspace"]), nbytes, S())), \
+                [In("points", a), Out("normals", (na, 3), F32), Out("cov", (na, 6), I64), Out("n_neighbours", (na,), I32),
+                 Scratch("workspace", nbytes)]
+        raise KeyError(name)
+    return make
+
+
+GRID_METRICS = ("d1_mse", "d2_transfer_normals", "d2_mse", "recolor", "color_mse", "mesh_voxelize", "estimate_normals")
+for name in GRID_METRICS:
+    row("%s res%d" % (name, GRID_RES), _grid_metric(name))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 def _with_env(monkeypatch, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -705,6 +778,12 @@ def test_the_table_names_every_hot_path_entry_point():
                "vrn_bwd_split_signs", "abs_max", "add_inplace", "laplace_likelihood_bwd", "factorized_likelihood_bwd", "bce_bwd", "sum_log",
                "adam_step"):
         assert fn in names, fn
+
+
+def test_the_table_names_the_voxel_grid_metrics():
+    names = [p.values[0] for p in ROWS]
+    for fn in GRID_METRICS:
+        assert "%s res%d" % (fn, GRID_RES) in names, fn
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -40,7 +40,7 @@ def test_sample_and_voxelize_bit_exact(mesh):
             got = m2p.sample_points_uniformly(v, t, n, seed, r, cdf=cdf)
             want = ref.sample(v, t, n, seed, r)
             assert got.shape == (n, 3) and np.array_equal(_bits(got), _bits(want)), (mesh, n, r is None)
-            for res in (255, 1023):
+            for res in (255, 1023, 2047, 4095):               # 4095: the top of the range, a grid of 2^36 cells
                 q = m2p.voxelize(got, res)
                 assert q.dtype == np.int32 and np.array_equal(q, ref.voxelize(want, res)), (mesh, n, res)
     if mesh == "quad_soup":                                  # zero-area triangles are never sampled
